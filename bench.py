@@ -34,9 +34,14 @@ it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 
 The scenes of a step are independent after the decoder, so scene i runs on HIP stream i % `--streams` (default 2).
 
-Extra objects on the JSON line (rank 0, N = 1): "stages" (where the step's time goes: forward stages + backward on one
-stream, the library's kernels grouped by stage), "roofline" (dominant kernel on the seeded synthetic scenes of SURVEY 8d,
-HIP-event timed, algorithmic bytes of section 8d; `bound` says what binds it; `valu_useful_frac` = useful FMA lane-ops /
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, runs the W warm-up steps, times the K steps, writes
+the last timed step's outputs when `--dump-outputs DIR` is given, and prints the line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step) and `config`.  Everything else is measured only
+with `--full`.
+
+Extra objects on the JSON line with `--full`: "memory_per_rank" (any N); on rank 0 with N = 1 "stages" (where the step's
+time goes: forward stages + backward on one stream, the library's kernels grouped by stage), "roofline" (dominant kernel
+on the seeded synthetic scenes of SURVEY 8d, HIP-event timed, algorithmic bytes of section 8d; `bound` says what binds it; `valu_useful_frac` = useful FMA lane-ops /
 issued lane-slots), "cpu_baseline" (the CPU oracle of the raster AND the fixture-pinned fp32 restatement of the
 reference's encoder, both on this box's host cores; `parity_vs_oracle` with the committed fp64 arbitration),
 "independent_tensors_step", "raster_only", "single_stream", "forward_only", "mesh_eval" (configs[4]: 48 views @1024x1024 +
@@ -106,10 +111,22 @@ def parse():
                          "accumulate_grad_batches=2: loss / 2, DDP `no_sync()` on the first micro-batch, all-reduce + clip + AdamW on the "
                          "second); 1 (default, the headline) reduces and updates on EVERY timed step -- the dearer definition")
     ap.add_argument("--no-optimizer", action="store_true", help="--step pipeline: forward + loss + backward only (rounds 1-3's step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: the per-rank memory report, the step's stage breakdown, "
+                         "the other step definitions, the raster legs, the roofline (with its own rocprofv3 passes), the side objects "
+                         "and the CPU baselines (the --no-* options below trim that set).  Without it a run is the headline only: "
+                         "set-up, warm-up, the timed steps, --dump-outputs, the JSON line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-side-legs", action="store_true", help="skip the side objects (attention, encoder, rays, ...)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: the step's output maps, loss "
+                         "terms and gradients) as DIR/<name>.npy, float32 (float64 where the tensor is), under 64 MB in all: an "
+                         "array larger than its share is replaced by a fixed, seeded sample of its elements (flattened)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_spawn(args):
@@ -169,7 +186,7 @@ def fine_subsets(scenes):
         return [(torch.sigmoid(sc["opacity"].detach()).squeeze(-1) > FINE_OPACITY).nonzero().squeeze(-1) for sc in scenes]
 
 
-def step(scenes, settings, gc, ga, n_streams=1, fine_idx=None, after=None, api="loop"):
+def step(scenes, settings, gc, ga, n_streams=1, fine_idx=None, after=None, api="loop", capture=None):
     """All forwards of the batch, then one backward through every view (as loss.backward() does).
     Per scene: the coarse views (network.py:487-497) and, with `fine_idx`, the fine views over the masked subset with
     refined SH coefficients (network.py:508-525; the refinement itself -- `forward_fine` -- is a side leg, here the
@@ -179,7 +196,8 @@ def step(scenes, settings, gc, ga, n_streams=1, fine_idx=None, after=None, api="
     `after(outs, grads)` names the roots of a second backward call that runs after the raster's (the encoder's output
     and its gradient).
     api = "views": the views of a scene and pass go through ONE multi-view call (one autograd node; activations and
-    subset gathers once per scene, as `lara_amd.renderer.Renderer.render_views` does) instead of one call per view."""
+    subset gathers once per scene, as `lara_amd.renderer.Renderer.render_views` does) instead of one call per view.
+    `capture` (a dict): receives the rendered maps and the scenes' gradients (`--dump-outputs`)."""
     from lara_amd import GaussianRasterizer, rasterize_gaussians_views
     from lara_amd import rasterizer as _rz
     outs, grads = [], []
@@ -239,6 +257,9 @@ def step(scenes, settings, gc, ga, n_streams=1, fine_idx=None, after=None, api="
         more_outs, more_grads = [], []
         after(more_outs, more_grads)
         torch.autograd.backward(more_outs, more_grads)
+    if capture is not None:
+        capture["raster_maps"] = [o.detach() for o in outs]
+        capture["grad_surfels"] = [v.grad for sc in scenes for _, v in sorted(sc.items())]
     for sc in scenes:
         for v in sc.values():
             v.grad = None
@@ -1302,9 +1323,17 @@ def make_pipeline_step(args, device, rank, world, plumbing):
         info["micro_batch"] += 1
         with (model.no_sync() if (not last and hasattr(model, "no_sync")) else contextlib.nullcontext()):
             out = model(batch, feat_vol, with_fine=with_fine)
-            loss, _ = lara_loss(batch, out, 2000, ms_ssim=ms_ssim)       # past iteration 1000: distortion + normal terms are on (loss.py:48)
+            loss, stats = lara_loss(batch, out, 2000, ms_ssim=ms_ssim)   # past iteration 1000: distortion + normal terms are on (loss.py:48)
             (loss if acc == 1 else loss / acc).backward()
         pipe.join_streams()
+        cap = info.get("capture")
+        if cap is not None:     # --dump-outputs: what this step hands its caller (references only; read after the timed steps)
+            cap.update({k: v.detach() for k, v in out.items()})
+            cap["loss"] = loss.detach()
+            cap.update({f"loss_{k}": v for k, v in stats.items()})
+            # (clip_grad_norm_ scales these in place below: the gradients the update consumes)
+            cap["grad_params"] = [p.grad for p in params]
+            cap["grad_feat_vol"] = feat_vol.grad
         if last:
             update()
         else:
@@ -1485,7 +1514,8 @@ def make_training_step(args, device, rank, world, plumbing):
         scenes, settings, gc, ga = build_batch(args, device, rank)
         fine_idx = None if args.no_fine else fine_subsets(scenes)
         frames = args.scenes * args.views * (1 if args.no_fine else 2)
-        raster = lambda after: step(scenes, settings, gc, ga, args.streams, fine_idx, after, api=args.raster_api)
+        raster = lambda after: step(scenes, settings, gc, ga, args.streams, fine_idx, after, api=args.raster_api,
+                                    capture=info.get("capture"))
         enc = None
         if args.step == "train":
             from lara_amd.encoder_train import VolTransformer
@@ -1517,6 +1547,10 @@ def make_training_step(args, device, rank, world, plumbing):
             return
         info["_out"] = model(feats)             # 1. encoder forward (DDP: also arms the reducer's hooks)
         raster(_enc_roots)                      # 2. raster forwards; 3. raster backward; 4. encoder backward (+ all-reduce)
+        cap = info.get("capture")
+        if cap is not None:                     # --dump-outputs
+            cap["encoder_out"] = info["_out"].detach()
+            cap["grad_encoder_params"] = [p.grad for p in enc.parameters()]
         for p in enc.parameters():
             p.grad = None
         info["_out"] = None
@@ -1539,8 +1573,45 @@ def _roots(after):
     return outs, grads
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20     # all of `--dump-outputs` together, under its promised 64 MB
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: {name: tensor or list of tensors} -> path/<name>.npy.  float64 tensors stay float64, every other
+    dtype is written as float32 (integers as float64).  A list is one flat array (its tensors flattened, in order).  Each
+    array gets an equal share of the byte budget; one that holds more elements is written as the sample at sorted indices
+    drawn by a generator seeded with the name's CRC32 -- the same elements in every run of the same arguments."""
+    import zlib
+    import numpy as np
+    items = []
+    for name, ts in sorted(arrays.items()):
+        ts = [t.detach() for t in (ts if isinstance(ts, (list, tuple)) else [ts]) if t is not None]
+        if ts:
+            items.append((name, ts))
+    share = DUMP_BUDGET_BYTES // 8 // max(1, len(items))    # elements per array, counted at float64's 8 bytes
+    os.makedirs(path, exist_ok=True)
+    for name, ts in items:
+        dtype = np.float64 if ts[0].dtype == torch.float64 or not ts[0].is_floating_point() else np.float32
+        total = sum(t.numel() for t in ts)
+        if len(ts) == 1 and total <= share:
+            a = ts[0].double().cpu().numpy()
+        elif total <= share:
+            a = torch.cat([t.reshape(-1).double().cpu() for t in ts]).numpy()
+        else:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, total, share))
+            parts, off = [], 0
+            for t in ts:
+                sel = idx[(idx >= off) & (idx < off + t.numel())] - off
+                parts.append(t.reshape(-1)[torch.from_numpy(sel).to(t.device)].double().cpu())
+                off += t.numel()
+            a = torch.cat(parts).numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(dtype))
+
+
 def main():
     args = parse()
+    if not args.full:       # a plain run measures the headline only
+        args.no_roofline = args.no_side_legs = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_spawn(args)
     # Exactly ONE line on stdout, the JSON: libraries that print there on their own (RCCL's version banner at communicator
@@ -1588,14 +1659,19 @@ def main():
     if world > 1:
         dist.barrier()
     sync()
+    capture_at = args.steps - 1 if args.dump_outputs and rank == 0 else -1
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == capture_at:
+            info["capture"] = {}
         full_step()
     sync()
     if world > 1:
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
+    if capture_at >= 0:
+        dump_outputs(args.dump_outputs, info.pop("capture"))
     joined = world
     if world > 1:
         from lara_amd import dp
@@ -1604,7 +1680,7 @@ def main():
         dist.all_reduce(cnt)
         joined = int(cnt.item())        # ranks that actually joined the job
     memory = None
-    if not plumbing:
+    if not plumbing and args.full:
         from lara_amd import rasterizer
         # Per rank: where the device memory sits once the timed steps have run (VERDICT r5 weak #8 -- the first 8-GPU run says
         # at once whether 4 scenes per GPU fit after the raster's capacity has followed the pair counts).  Gathered to rank 0.

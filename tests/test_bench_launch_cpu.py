@@ -10,6 +10,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -43,6 +45,50 @@ def test_bench_single_rank_plumbing_has_no_collective():
     out = _run(["--steps", "2", "--warmup", "1"], {})
     assert out["n_gpus"] == 1 and out["config"]["grad_allreduce"] is None
     assert out["config"]["frames_per_step"] == 4 * 8 * 2
+
+
+def test_dump_outputs_writes_the_last_step_the_same_in_every_run(tmp_path):
+    """`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy in float32 / float64, identical from run to
+    run with the same arguments (plumbing step: the encoder stand-in's output and its parameters' gradients)."""
+    runs = []
+    for d in ("a", "b"):
+        out = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)], {})
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert set(runs[0]) == {"encoder_out.npy", "grad_encoder_params.npy"}
+    assert runs[0]["encoder_out.npy"].shape == (8, 64) and runs[0]["grad_encoder_params.npy"].shape == (64 * 256 + 256 + 256 * 64 + 64,)
+    for name, a in runs[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, name
+        assert np.array_equal(a, runs[1][name]), name
+
+
+def test_dump_outputs_samples_large_arrays_within_the_budget(tmp_path):
+    """An array larger than its share of the 64 MB is written as a fixed, seeded sample of its elements; a list of tensors
+    is one flat array; float64 stays float64, every other floating dtype is written as float32."""
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(20_000_000, generator=g)
+    arrays = {"big": big, "parts": [torch.randn(3, 5, generator=g), torch.randn(7, generator=g).bfloat16()],
+              "wide": torch.randn(2, 3, dtype=torch.float64, generator=g), "absent": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big.npy", "parts.npy", "wide.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 2 ** 20
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert a["big.npy"].dtype == np.float32 and 0 < a["big.npy"].size < big.numel()
+    assert np.isin(a["big.npy"], big.numpy()).all()
+    assert np.array_equal(a["big.npy"], np.load(tmp_path / "b" / "big.npy"))
+    want = torch.cat([arrays["parts"][0].reshape(-1), arrays["parts"][1].float()]).numpy()
+    assert a["parts.npy"].dtype == np.float32 and np.array_equal(a["parts.npy"], want)
+    assert a["wide.npy"].dtype == np.float64 and np.array_equal(a["wide.npy"], arrays["wide"].numpy())
+
+
+def test_steps_below_one_is_an_error():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=dict(os.environ, LARA_BENCH_PLUMBING="1"),
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode != 0 and "--steps" in p.stderr
 
 
 def test_world_size_mismatch_is_an_error():

@@ -1,21 +1,18 @@
 """`lara_amd.dataset`: the adapter around the REFERENCE's own dataset class (dataLoader/gobjverse.py:17-146).  The
 class itself is not restated anywhere in this repository; tests/golden/loader_ref.npz holds items it returned on a
 small in-memory scene store (tests/golden/make_loader_fixture.py).  Checked here: `skip_cpu_rays` removes the CPU
-`build_rays` work from the reference class without changing any other field (needs /root/reference: build container
-only), and `collate_to_device` rebuilds both ray maps on the GPU equal to the reference's CPU rays."""
+`build_rays` work from the reference class without changing any other field (tests/golden/loader_hooked_ref.npz: its
+items with the hook, tests/golden/make_loader_hook_fixture.py), and `collate_to_device` rebuilds both ray maps on the GPU
+equal to the reference's CPU rays."""
 import os
-import random
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from tests.helpers_store import make_store
-
 FX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loader_ref.npz")
-REF = "/root/reference"
+FX_HOOKED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loader_hooked_ref.npz")
 
 
 def _fixture_item(fx, tag, index):
@@ -38,43 +35,33 @@ def test_skip_cpu_rays_swaps_and_returns_the_original():
     assert isinstance(out, np.ndarray) and out.size == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "dataLoader")), reason="needs the reference checkout (build container only)")
 def test_reference_class_with_the_hook_returns_the_same_items_minus_the_rays():
+    """loader_hooked_ref.npz: the reference class's items with `skip_cpu_rays` applied to its module
+    (tests/golden/make_loader_hook_fixture.py), same store and seeds as loader_ref.npz (its items without the hook)."""
     from lara_amd import dataset
-    store = make_store(seed=5)
-    saved = {k: sys.modules.get(k) for k in ("h5py", "cv2", "dataLoader", "dataLoader.gobjverse", "dataLoader.utils")}
-    h5 = types.ModuleType("h5py")
-    h5.File = lambda path, mode="r": store
-    pkg = types.ModuleType("dataLoader")       # bare package: only the loader module itself is executed
-    pkg.__path__ = [os.path.join(REF, "dataLoader")]
-    sys.modules.update({"h5py": h5, "dataLoader": pkg})
-    sys.modules.setdefault("cv2", types.ModuleType("cv2"))
-    sys.modules.pop("dataLoader.gobjverse", None)
-    sys.path.insert(0, REF)
-    try:
-        import dataLoader.gobjverse as ref
-        orig = dataset.skip_cpu_rays(ref)
-        fx = np.load(FX)
-        cfg = types.SimpleNamespace(data_root="mem", split="test", img_size=(32, 32), n_group=4, n_scenes=100, load_normal=True)
-        ds = ref.gobjverse(cfg)
-        for index in (0, len(ds) - 1):
-            random.seed(100 + index)
-            torch.manual_seed(200 + index)
-            it = ds[index]
-            assert it["tar_rays"].size == 0 and it["tar_rays_down"].size == 0
-            want = _fixture_item(fx, "test4", index)
-            for k, v in want.items():
-                if k in dataset.RAY_KEYS or k == "meta":
-                    continue
-                np.testing.assert_array_equal(np.asarray(it[k]), v, err_msg=k)
-        ref.build_rays = orig
-    finally:
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    fx, hooked = np.load(FX), np.load(FX_HOOKED)
+    mod = types.ModuleType("loader_module")
+    mod.build_rays = None
+    dataset.skip_cpu_rays(mod)
+    stub = mod.build_rays(np.eye(4)[None], np.eye(3)[None], 32, 32, 1.0 / 16)      # what the hook makes the class ship
+    idx = (0, int(fx["test4.len"]) - 1)
+    assert int(hooked["test4.len"]) == int(fx["test4.len"])
+    got, want = [_fixture_item(hooked, "test4", i) for i in idx], [_fixture_item(fx, "test4", i) for i in idx]
+    for it, ref in zip(got, want):
+        assert set(it) == set(ref)
+        for k in dataset.RAY_KEYS:
+            assert ref[k].size > 0 and it[k].dtype == stub.dtype and it[k].shape == stub.shape == (0,), k
+        assert it["meta"] == ref["meta"]
+        for k, v in ref.items():
+            if k in dataset.RAY_KEYS or k == "meta":
+                continue
+            np.testing.assert_array_equal(np.asarray(it[k]), v, err_msg=k)
+    # ... and the worker-side collate of the hooked items is the batch of the items with the CPU rays
+    a, b = dataset.collate_cpu(got), dataset.collate_cpu(want)
+    assert set(a) == set(b)
+    for k in a:
+        if torch.is_tensor(a[k]):
+            assert torch.equal(a[k], b[k]), k
 
 
 @pytest.mark.gpu

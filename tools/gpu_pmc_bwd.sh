@@ -12,7 +12,7 @@ for SET in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"; do
   i=$((i+1))
   timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc $SET -d $OUT/pmcb_${TAG}_$i -o pmc -- \
-      python $REPO/bench.py --steps 1 --warmup 0 --scenes 1 --no-cpu-baseline --no-roofline > $OUT/pmcb_${TAG}_$i.log 2>&1
+      python $REPO/bench.py --full --steps 1 --warmup 0 --scenes 1 --no-cpu-baseline --no-roofline > $OUT/pmcb_${TAG}_$i.log 2>&1
 done
 find $OUT/pmcb_${TAG}_* -type f -size +8M -delete
 python - <<PY

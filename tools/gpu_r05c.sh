@@ -7,8 +7,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd $REPO
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_init.json 2> $OUT/${TAG}_bench_init.err; echo "bench init rc=$?"
-timeout 600 python bench.py --steps 20 --warmup 5 --regime trained > $OUT/${TAG}_bench_trained.json 2> $OUT/${TAG}_bench_trained.err; echo "bench trained rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_init.json 2> $OUT/${TAG}_bench_init.err; echo "bench init rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 --regime trained > $OUT/${TAG}_bench_trained.json 2> $OUT/${TAG}_bench_trained.err; echo "bench trained rc=$?"
 bash tools/gpu_pmc_enc.sh $TAG > $OUT/${TAG}_pmc_enc.log 2>&1; echo "pmc enc rc=$?"
 bash tools/gpu_pmc_train.sh $TAG > $OUT/${TAG}_encoder_train_pmc.txt 2>&1; echo "pmc train rc=$?"
 bash tools/gpu_r05_enc_stats.sh $TAG cur > $OUT/${TAG}_enc_stats.log 2>&1; echo "enc stats rc=$?"

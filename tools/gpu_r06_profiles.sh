@@ -8,8 +8,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd $REPO
-timeout 700 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_init.json 2> $OUT/${TAG}_bench_init.err; echo "bench init rc=$?"
-timeout 700 python bench.py --steps 20 --warmup 5 --regime trained > $OUT/${TAG}_bench_trained.json 2> $OUT/${TAG}_bench_trained.err; echo "bench trained rc=$?"
+timeout 700 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_init.json 2> $OUT/${TAG}_bench_init.err; echo "bench init rc=$?"
+timeout 700 python bench.py --full --steps 20 --warmup 5 --regime trained > $OUT/${TAG}_bench_trained.json 2> $OUT/${TAG}_bench_trained.err; echo "bench trained rc=$?"
 bash tools/gpu_profile.sh $TAG > $OUT/${TAG}_profile.log 2>&1; echo "profile rc=$?"
 bash tools/gpu_traffic.sh $TAG > $OUT/${TAG}_traffic.log 2>&1; echo "traffic rc=$?"
 ONLY_RASTER=1 bash tools/gpu_profile.sh ${TAG}_trained "--regime trained" > $OUT/${TAG}_trained_profile.log 2>&1; echo "profile trained rc=$?"
