@@ -141,7 +141,8 @@ int lara2dgs_get_state_layout(int32_t P, int32_t H, int32_t W, int64_t capacity,
 /* Replaces `_C.rasterize_gaussians(bg, means3D, colors_precomp, opacities, scales, rotations,
  * scale_modifier, transMat_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree,
  * campos, prefiltered, debug)` as called from GaussianRasterizer.forward
- * (renderer_2dgs.py:209-218).
+ * (renderer_2dgs.py:209-218).  The one-view form of lara2dgs_forward_views (below): the same call with n_views = 1,
+ * `state` / `scratch` of lara2dgs_state_bytes / lara2dgs_scratch_bytes bytes.
  *   means3D [P,3]; exactly one of shs [P,M,3] / colors_precomp [P,3]; opacities [P];
  *   either scales [P,2] + rotations [P,4] (w,x,y,z) or transmat_precomp [P,9]; unused = NULL.
  *   out_color [3,H,W]; out_allmap [7,H,W] (depth-sum, alpha, normal xyz, median depth,
@@ -152,7 +153,8 @@ int lara2dgs_forward(const lara2dgs_view *view, const float *means3D, const floa
                      float *out_allmap, int32_t *out_radii, void *state, void *scratch,
                      void *stream);
 
-/* Replaces `_C.rasterize_gaussians_backward(...)`.  `state` is the buffer a forward with forward_only = 0 filled (a view
+/* Replaces `_C.rasterize_gaussians_backward(...)`; the one-view form of lara2dgs_backward_views (below), with the
+ * gradient arrays passed one by one instead of in one buffer.  `state` is the buffer a forward with forward_only = 0 filled (a view
  * with forward_only = 1 is LARA2DGS_E_INVALID here); the backward WRITES to it (it
  * re-orders the work-item list `bwd_items` in place and sets header[22]): one backward at a time per state buffer.
  * dL_dallmap may be NULL = no gradient on any of the seven maps (LaRa's fine pass, lightning/loss.py:35-47: the loss reads its

@@ -157,70 +157,6 @@ int lara2dgs_get_state_layout(int32_t P, int32_t H, int32_t W, int64_t capacity,
     return LARA2DGS_OK;
 }
 
-int lara2dgs_forward(const lara2dgs_view *view, const float *means3D, const float *shs,
-                     const float *colors_precomp, const float *opacities, const float *scales,
-                     const float *rotations, const float *transmat_precomp, float *out_color,
-                     float *out_allmap, int32_t *out_radii, void *state, void *scratch,
-                     void *stream) {
-    ViewDev v;
-    if (!make_view(view, v)) return LARA2DGS_E_INVALID;
-    if (!out_color || !out_allmap || !state || !scratch) return LARA2DGS_E_INVALID;
-    if (v.P > 0) {
-        if (!means3D || !opacities || !out_radii) return LARA2DGS_E_INVALID;
-        if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
-        const bool has_sr = scales && rotations;
-        if (has_sr == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
-        if (shs && v.M < (v.deg + 1) * (v.deg + 1)) return LARA2DGS_E_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    StateView st = carve_state(v, state);
-    ScratchLayout SL;
-    ScratchView sc = carve_scratch(v, scratch, SL);
-    // tile_count + tile_fill start at zero (the header is initialised by tile_scan, the first kernel to use it)
-    hipError_t e = hipMemsetAsync(sc.tile_count, 0, (size_t)(SL.sub_start - SL.tile_count), s);
-    if (e != hipSuccess) { l2d_set_hip_error(e); return LARA2DGS_E_LAUNCH; }
-    int rc = launch_preprocess_fwd(v, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                   transmat_precomp, st, sc, out_radii, s);
-    if (rc) return rc;
-    rc = launch_binning(v, st, sc, s);
-    if (rc) return rc;
-    return launch_composite_fwd(v, st, sc, out_color, out_allmap, s);
-}
-
-int lara2dgs_backward(const lara2dgs_view *view, const float *means3D, const float *shs,
-                      const float *colors_precomp, const float *scales, const float *rotations,
-                      const float *transmat_precomp, const int32_t *radii, const float *dL_dcolor,
-                      const float *dL_dallmap, void *state, void *scratch,
-                      float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dcolors,
-                      float *dL_dopacities, float *dL_dscales, float *dL_drotations,
-                      float *dL_dtransmat, void *stream) {
-    ViewDev v;
-    if (!make_view(view, v)) return LARA2DGS_E_INVALID;
-    if (!dL_dcolor || !state || !scratch) return LARA2DGS_E_INVALID;      // (dL_dallmap NULL = zero: the colour-only backward)
-    if (v.fwd_only) return LARA2DGS_E_INVALID;      // a forward-only call kept nothing for a backward
-    if (v.P == 0) return LARA2DGS_OK;
-    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities) return LARA2DGS_E_INVALID;
-    if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
-    if (shs && !dL_dshs) return LARA2DGS_E_INVALID;
-    if (colors_precomp && !dL_dcolors) return LARA2DGS_E_INVALID;
-    const bool has_sr = scales && rotations;
-    if (has_sr == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
-    if (has_sr && (!dL_dscales || !dL_drotations)) return LARA2DGS_E_INVALID;
-    if (transmat_precomp && !dL_dtransmat) return LARA2DGS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    StateView st = carve_state(v, state);
-    ScratchLayout SL;
-    ScratchView sc = carve_scratch(v, scratch, SL);
-    // one launch: the validity bitmap zeroed + the work items ordered dearest first (by what they cost the forward)
-    int rc = launch_bwd_order(v, st, sc, s, nullptr, sc.pair_valid, SL.total - SL.pair_valid);
-    if (rc) return rc;
-    rc = launch_composite_bwd(v, st, sc, dL_dcolor, dL_dallmap, s);
-    if (rc) return rc;
-    return launch_preprocess_bwd(v, means3D, shs, colors_precomp, scales, rotations, transmat_precomp,
-                                 radii, st, sc, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,
-                                 dL_dopacities, dL_dscales, dL_drotations, dL_dtransmat, s);
-}
-
 int lara2dgs_mark_visible(int32_t P, const float *means3D, const float *viewmatrix,
                           const float *projmatrix, uint8_t *present, void *stream) {
     (void)projmatrix;  // kept for signature parity with the reference; the test only needs view z
@@ -265,7 +201,6 @@ int lara2dgs_profile_collect(char *names, int names_len, float *ms, int max_entr
 
 // ---- multi-view calls ---------------------------------------------------------------------------------------------
 namespace {
-#define HIP_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { l2d_set_hip_error(e__); return LARA2DGS_E_LAUNCH; } } while (0)
 
 bool views_agree(int n, const lara2dgs_view *views) {
     for (int i = 1; i < n; i++) {
@@ -311,6 +246,12 @@ bool strides_ok(const lara2dgs_view &v0, int64_t state_stride, int64_t scratch_s
            state_stride >= lara2dgs_state_bytes(v0.P, v0.image_height, v0.image_width, v0.capacity, v0.forward_only) &&
            scratch_stride >= lara2dgs_scratch_bytes(v0.P, v0.image_height, v0.image_width, v0.capacity, v0.forward_only);
 }
+
+// a one-view call's strides: its own state and scratch sizes (nothing past view 0 is addressed)
+void one_view_strides(const lara2dgs_view &v, int64_t &state_stride, int64_t &scratch_stride) {
+    state_stride = align_up(lara2dgs_state_bytes(v.P, v.image_height, v.image_width, v.capacity, v.forward_only), 256);
+    scratch_stride = align_up(lara2dgs_scratch_bytes(v.P, v.image_height, v.image_width, v.capacity, v.forward_only), 256);
+}
 }  // namespace
 
 extern "C" {
@@ -322,10 +263,11 @@ int lara2dgs_get_grad_layout(int32_t P, int32_t sh_coeffs, int32_t has_shs, int3
     return LARA2DGS_OK;
 }
 
-// Every kernel of a multi-view call is ONE launch over the cameras on the caller's stream (workgroup z index = view; chunks of
+// Every kernel of a call is ONE launch over the cameras on the caller's stream (workgroup z index = view; chunks of
 // L2D_MAX_VIEWS): the surfels' inputs come from HBM once for the n cameras, and one view's tail of long tile lists is filled by
-// the next view's workgroups.  (Rounds 2-4 also kept a per-view path dealt to side streams -- "lanes" -- with two process-wide
-// setters; it measured slower in every configuration once the kernels were batched and is gone: the library keeps no settings.)
+// the next view's workgroups.  A one-view call is the case n = 1.  (Rounds 2-4 also kept a per-view path dealt to side streams
+// -- "lanes" -- with two process-wide setters; it measured slower in every configuration once the kernels were batched and is
+// gone: the library keeps no settings.)
 static int forward_views_impl(int32_t n_views, const lara2dgs_view *views, const float *means3D,
                            const float *shs, const float *colors_precomp, const float *opacities,
                            const float *scales, const float *rotations, const float *transmat_precomp,
@@ -346,24 +288,19 @@ static int forward_views_impl(int32_t n_views, const lara2dgs_view *views, const
     if (!strides_ok(v0, state_stride, scratch_stride)) return LARA2DGS_E_INVALID;
     hipStream_t caller = (hipStream_t)stream;
     const int64_t HW = (int64_t)v0.image_height * v0.image_width;
-    if (v0.P == 0) {    // nothing to bin: every view is its background (the per-view entry point knows how)
-        int rc = LARA2DGS_OK;
-        for (int i = 0; i < n_views && rc == LARA2DGS_OK; i++)
-            rc = lara2dgs_forward(&views[i], means3D, shs, colors_precomp, opacities, scales, rotations, transmat_precomp,
-                                  out_color + i * 3 * HW, out_allmap + i * 7 * HW, out_radii,
-                                  (char *)state + i * state_stride, (char *)scratch + i * scratch_stride, stream);
-        return rc;
+    if (!out_color || !out_allmap) return LARA2DGS_E_INVALID;
+    if (v0.P > 0) {     // (with no surfels nothing is binned: every view gets its background through the same launches)
+        if (!means3D || !opacities || !out_radii) return LARA2DGS_E_INVALID;
+        if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
+        if ((scales && rotations) == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
     }
-    if (!out_color || !out_allmap || !means3D || !opacities || !out_radii) return LARA2DGS_E_INVALID;
-    if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
-    if ((scales && rotations) == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
     std::vector<ViewDev> vd(n_views);
     std::vector<StateView> st(n_views);
     std::vector<ScratchView> sc(n_views);
     std::vector<int32_t *> rad(n_views);
     for (int i = 0; i < n_views; i++) {
         if (!make_view(&views[i], vd[i])) return LARA2DGS_E_INVALID;
-        if (shs && vd[i].M < (vd[i].deg + 1) * (vd[i].deg + 1)) return LARA2DGS_E_INVALID;
+        if (v0.P > 0 && shs && vd[i].M < (vd[i].deg + 1) * (vd[i].deg + 1)) return LARA2DGS_E_INVALID;
         st[i] = carve_state(vd[i], (char *)state + i * state_stride);
         ScratchLayout SL;
         sc[i] = carve_scratch(vd[i], (char *)scratch + i * scratch_stride, SL);
@@ -377,18 +314,18 @@ static int forward_views_impl(int32_t n_views, const lara2dgs_view *views, const
         vb.n = n_views - i0 < L2D_MAX_VIEWS ? n_views - i0 : L2D_MAX_VIEWS;
         vb.state_stride = state_stride; vb.scratch_stride = scratch_stride;
         for (int k = 0; k < vb.n; k++) vb.bg[k] = vd[i0 + k].bg;
-        rc = launch_preprocess_fwd_views(vd[i0], vb.n, &vd[i0], means3D, shs, colors_precomp, opacities, scales, rotations,
-                                         transmat_precomp, &st[i0], &sc[i0], &rad[i0], caller);
-        if (rc == LARA2DGS_OK && !subset) rc = launch_binning(vd[i0], st[i0], sc[i0], caller, &vb);
+        rc = launch_preprocess_fwd_views(vd[i0], vb.n, &vd[i0], n_views > 1, means3D, shs, colors_precomp, opacities, scales,
+                                         rotations, transmat_precomp, &st[i0], &sc[i0], &rad[i0], caller);
+        if (rc == LARA2DGS_OK && !subset) rc = launch_binning(vd[i0], st[i0], sc[i0], caller, vb);
         if (rc == LARA2DGS_OK && subset) {
             ViewDev cv = vd[i0];      // the coarse call's view i0: its surfel count, capacity and mode decide its state's layout
             cv.P = subset->coarse_P; cv.cap = (unsigned)subset->coarse_capacity; cv.fwd_only = subset->coarse_forward_only != 0;
             const StateView cst = carve_state(cv, (char *)const_cast<void *>(subset->coarse_state) + (int64_t)i0 * subset->coarse_state_stride);
-            rc = launch_binning_subset(vd[i0], st[i0], sc[i0], caller, &vb, cst, subset->coarse_state_stride, subset->inv);
+            rc = launch_binning_subset(vd[i0], st[i0], sc[i0], caller, vb, cst, subset->coarse_state_stride, subset->inv);
         }
         if (rc == LARA2DGS_OK)
             rc = launch_composite_fwd(vd[i0], st[i0], sc[i0], out_color + (int64_t)i0 * 3 * HW, out_allmap + (int64_t)i0 * 7 * HW,
-                                      caller, &vb);
+                                      caller, vb);
     }
     return rc;
 }
@@ -413,28 +350,17 @@ int lara2dgs_forward_views_subset(int32_t n_views, const lara2dgs_view *views, c
                               out_allmap, out_radii, state, state_stride, scratch, scratch_stride, stream, subset);
 }
 
-int lara2dgs_backward_views(int32_t n_views, const lara2dgs_view *views, const float *means3D,
-                            const float *shs, const float *colors_precomp, const float *scales,
-                            const float *rotations, const float *transmat_precomp, const int32_t *radii,
-                            const float *dL_dcolor, const float *dL_dallmap, void *state,
-                            int64_t state_stride, void *scratch, int64_t scratch_stride,
-                            float *grad_out, void *stream) {
-    if (n_views <= 0 || !views || !state || !scratch || !grad_out) return LARA2DGS_E_INVALID;
-    if (!views_agree(n_views, views)) return LARA2DGS_E_INVALID;
+// The backward of a call whose arguments the entry point has checked (a gradient pointer is null where its section is absent).
+static int backward_views_impl(int32_t n_views, const lara2dgs_view *views, const float *means3D, const float *shs,
+                               const float *colors_precomp, const float *scales, const float *rotations,
+                               const float *transmat_precomp, const int32_t *radii, const float *dL_dcolor,
+                               const float *dL_dallmap, void *state, int64_t state_stride, void *scratch,
+                               int64_t scratch_stride, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs,
+                               float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations,
+                               float *dL_dtransmat, void *stream) {
     const lara2dgs_view &v0 = views[0];
-    if (v0.forward_only) return LARA2DGS_E_INVALID;      // a forward-only call kept nothing for a backward
-    if (!strides_ok(v0, state_stride, scratch_stride)) return LARA2DGS_E_INVALID;
-    if (!dL_dcolor) return LARA2DGS_E_INVALID;      // (dL_dallmap NULL = zero: the colour-only backward)
-    const bool has_sh = shs != nullptr, has_col = colors_precomp != nullptr, has_sr = scales && rotations,
-               has_tm = transmat_precomp != nullptr;
-    lara2dgs_grad_layout G;
-    grad_layout(v0.P, v0.sh_coeffs, has_sh, has_col, has_sr, has_tm, &G);
     hipStream_t caller = (hipStream_t)stream;
-    if (v0.P == 0 || G.total == 0) return LARA2DGS_OK;
     const int64_t HW = (int64_t)v0.image_height * v0.image_width;
-    auto at = [&](float *base, int64_t off) { return off < 0 ? (float *)nullptr : base + off; };
-    if (!means3D || !radii) return LARA2DGS_E_INVALID;
-    if (has_sh == has_col || has_sr == has_tm) return LARA2DGS_E_INVALID;
     std::vector<ViewDev> vd(n_views);
     std::vector<StateView> st(n_views);
     std::vector<ScratchView> sc(n_views);
@@ -455,17 +381,90 @@ int lara2dgs_backward_views(int32_t n_views, const lara2dgs_view *views, const f
         vb.n = n_views - i0 < L2D_MAX_VIEWS ? n_views - i0 : L2D_MAX_VIEWS;
         vb.state_stride = state_stride; vb.scratch_stride = scratch_stride;
         for (int k = 0; k < vb.n; k++) vb.bg[k] = vd[i0 + k].bg;
-        rc = launch_bwd_order(vd[i0], st[i0], sc[i0], caller, &vb, sc[i0].pair_valid, SL[i0].total - SL[i0].pair_valid);
+        rc = launch_bwd_order(vd[i0], st[i0], sc[i0], caller, vb, sc[i0].pair_valid, SL[i0].total - SL[i0].pair_valid);
         if (rc == LARA2DGS_OK)
-            rc = launch_composite_bwd(vd[i0], st[i0], sc[i0], dL_dcolor + (int64_t)i0 * 3 * HW, dL_dallmap ? dL_dallmap + (int64_t)i0 * 7 * HW : nullptr, caller, &vb);
+            rc = launch_composite_bwd(vd[i0], st[i0], sc[i0], dL_dcolor + (int64_t)i0 * 3 * HW, dL_dallmap ? dL_dallmap + (int64_t)i0 * 7 * HW : nullptr, caller, vb);
         if (rc == LARA2DGS_OK)
-            rc = launch_preprocess_bwd_views(vd[i0], vb.n, &vd[i0], i0 > 0, means3D, shs, colors_precomp, scales, rotations,
-                                             transmat_precomp, &rad[i0], &st[i0], &sc[i0], at(grad_out, G.means3D),
-                                             at(grad_out, G.means2D), at(grad_out, G.shs), at(grad_out, G.colors),
-                                             at(grad_out, G.opacities), at(grad_out, G.scales), at(grad_out, G.rotations),
-                                             at(grad_out, G.transmat), caller);
+            rc = launch_preprocess_bwd_views(vd[i0], vb.n, &vd[i0], n_views > 1, i0 > 0, means3D, shs, colors_precomp, scales,
+                                             rotations, transmat_precomp, &rad[i0], &st[i0], &sc[i0], dL_dmeans3D, dL_dmeans2D,
+                                             dL_dshs, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dtransmat, caller);
     }
     return rc;
+}
+
+int lara2dgs_backward_views(int32_t n_views, const lara2dgs_view *views, const float *means3D,
+                            const float *shs, const float *colors_precomp, const float *scales,
+                            const float *rotations, const float *transmat_precomp, const int32_t *radii,
+                            const float *dL_dcolor, const float *dL_dallmap, void *state,
+                            int64_t state_stride, void *scratch, int64_t scratch_stride,
+                            float *grad_out, void *stream) {
+    if (n_views <= 0 || !views || !state || !scratch || !grad_out) return LARA2DGS_E_INVALID;
+    if (!views_agree(n_views, views)) return LARA2DGS_E_INVALID;
+    const lara2dgs_view &v0 = views[0];
+    if (v0.forward_only) return LARA2DGS_E_INVALID;      // a forward-only call kept nothing for a backward
+    if (!strides_ok(v0, state_stride, scratch_stride)) return LARA2DGS_E_INVALID;
+    if (!dL_dcolor) return LARA2DGS_E_INVALID;      // (dL_dallmap NULL = zero: the colour-only backward)
+    const bool has_sh = shs != nullptr, has_col = colors_precomp != nullptr, has_sr = scales && rotations,
+               has_tm = transmat_precomp != nullptr;
+    lara2dgs_grad_layout G;
+    grad_layout(v0.P, v0.sh_coeffs, has_sh, has_col, has_sr, has_tm, &G);
+    if (v0.P == 0 || G.total == 0) return LARA2DGS_OK;
+    if (!means3D || !radii) return LARA2DGS_E_INVALID;
+    if (has_sh == has_col || has_sr == has_tm) return LARA2DGS_E_INVALID;
+    auto at = [&](int64_t off) { return off < 0 ? (float *)nullptr : grad_out + off; };
+    return backward_views_impl(n_views, views, means3D, shs, colors_precomp, scales, rotations, transmat_precomp, radii,
+                               dL_dcolor, dL_dallmap, state, state_stride, scratch, scratch_stride, at(G.means3D),
+                               at(G.means2D), at(G.shs), at(G.colors), at(G.opacities), at(G.scales), at(G.rotations),
+                               at(G.transmat), stream);
+}
+
+// The one-view calls: the views calls with n = 1.
+int lara2dgs_forward(const lara2dgs_view *view, const float *means3D, const float *shs,
+                     const float *colors_precomp, const float *opacities, const float *scales,
+                     const float *rotations, const float *transmat_precomp, float *out_color,
+                     float *out_allmap, int32_t *out_radii, void *state, void *scratch,
+                     void *stream) {
+    ViewDev v;
+    if (!make_view(view, v)) return LARA2DGS_E_INVALID;
+    if (!out_color || !out_allmap || !state || !scratch) return LARA2DGS_E_INVALID;
+    if (v.P > 0) {
+        if (!means3D || !opacities || !out_radii) return LARA2DGS_E_INVALID;
+        if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
+        const bool has_sr = scales && rotations;
+        if (has_sr == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
+        if (shs && v.M < (v.deg + 1) * (v.deg + 1)) return LARA2DGS_E_INVALID;
+    }
+    int64_t sst, qst;
+    one_view_strides(*view, sst, qst);
+    return forward_views_impl(1, view, means3D, shs, colors_precomp, opacities, scales, rotations, transmat_precomp, out_color,
+                              out_allmap, out_radii, state, sst, scratch, qst, stream, nullptr);
+}
+
+int lara2dgs_backward(const lara2dgs_view *view, const float *means3D, const float *shs,
+                      const float *colors_precomp, const float *scales, const float *rotations,
+                      const float *transmat_precomp, const int32_t *radii, const float *dL_dcolor,
+                      const float *dL_dallmap, void *state, void *scratch,
+                      float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dcolors,
+                      float *dL_dopacities, float *dL_dscales, float *dL_drotations,
+                      float *dL_dtransmat, void *stream) {
+    ViewDev v;
+    if (!make_view(view, v)) return LARA2DGS_E_INVALID;
+    if (!dL_dcolor || !state || !scratch) return LARA2DGS_E_INVALID;      // (dL_dallmap NULL = zero: the colour-only backward)
+    if (v.fwd_only) return LARA2DGS_E_INVALID;      // a forward-only call kept nothing for a backward
+    if (v.P == 0) return LARA2DGS_OK;
+    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities) return LARA2DGS_E_INVALID;
+    if ((shs == nullptr) == (colors_precomp == nullptr)) return LARA2DGS_E_INVALID;
+    if (shs && !dL_dshs) return LARA2DGS_E_INVALID;
+    if (colors_precomp && !dL_dcolors) return LARA2DGS_E_INVALID;
+    const bool has_sr = scales && rotations;
+    if (has_sr == (transmat_precomp != nullptr)) return LARA2DGS_E_INVALID;
+    if (has_sr && (!dL_dscales || !dL_drotations)) return LARA2DGS_E_INVALID;
+    if (transmat_precomp && !dL_dtransmat) return LARA2DGS_E_INVALID;
+    int64_t sst, qst;
+    one_view_strides(*view, sst, qst);
+    return backward_views_impl(1, view, means3D, shs, colors_precomp, scales, rotations, transmat_precomp, radii, dL_dcolor,
+                               dL_dallmap, state, sst, scratch, qst, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,
+                               dL_dopacities, dL_dscales, dL_drotations, dL_dtransmat, stream);
 }
 
 }  // extern "C"

@@ -770,10 +770,10 @@ subset_compact_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint
 
 }  // namespace
 
-int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vb, StateView cst,
+int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb, StateView cst,
                           long long coarse_stride, const int32_t *inv) {
-    const unsigned nz = vb ? (unsigned)vb->n : 1u;
-    const long long sst = vb ? vb->state_stride : 0, qst = vb ? vb->scratch_stride : 0;
+    const unsigned nz = (unsigned)vb.n;
+    const long long sst = vb.state_stride, qst = vb.scratch_stride;
     {
         L2D_PROF("tile_scan", s);
         hipLaunchKernelGGL(tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, s, v, sc.tile_count, sc.sub_start,
@@ -795,10 +795,10 @@ int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStr
     return LARA2DGS_OK;
 }
 
-int launch_binning(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vb) {
-    // vb != nullptr: the binning of ALL views of a multi-view call in three launches (blockIdx.z = view; st / sc are view 0's)
-    const unsigned nz = vb ? (unsigned)vb->n : 1u;
-    const long long sst = vb ? vb->state_stride : 0, qst = vb ? vb->scratch_stride : 0;
+int launch_binning(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb) {
+    // the binning of ALL views of the batch in three launches (blockIdx.z = view; st / sc are view 0's)
+    const unsigned nz = (unsigned)vb.n;
+    const long long sst = vb.state_stride, qst = vb.scratch_stride;
     {
         L2D_PROF("tile_scan", s);
         hipLaunchKernelGGL(tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, s, v, sc.tile_count, sc.sub_start,

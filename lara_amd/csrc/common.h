@@ -34,10 +34,10 @@ struct ViewDev {
     uint32_t *counts_out;  // host-visible uint32[4] of view 0 (view z: + 4 z), or null: lara2dgs_view.counts_out
 };
 
-// A multi-view call carves the views' `state` / `scratch` buffers out of one allocation each at a constant stride, and all
-// views agree in every size: the binning and composite kernels of ALL views are then ONE launch each -- blockIdx.z = view, every
-// state / scratch / output pointer advanced by view * stride (0 and gridDim.z = 1 for a single view).  Only the background
-// colours are separate tensors per view.
+// A call carves the views' `state` / `scratch` buffers out of one allocation each at a constant stride, and all views agree
+// in every size: the binning and composite kernels of ALL views are then ONE launch each -- blockIdx.z = view, every state /
+// scratch / output pointer advanced by view * stride (a one-view call is the batch of n = 1).  Only the background colours
+// are separate tensors per view.
 struct ViewBatch {
     int n;                      // views of this launch (<= L2D_MAX_VIEWS)
     long long state_stride, scratch_stride;   // bytes between consecutive views' buffers
@@ -145,32 +145,23 @@ static inline void scratch_layout(int P, int H, int W, int64_t cap, int fwd_only
 }
 
 // ---- launchers (one per .hip translation unit) -------------------------------------------------
-int launch_preprocess_fwd(const ViewDev &v, const float *means3D, const float *shs,
-                          const float *colors_precomp, const float *opacities, const float *scales,
-                          const float *rotations, const float *transmat_precomp, StateView st,
-                          ScratchView sc, int32_t *radii, hipStream_t s);
-int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, const float *means3D, const float *shs,
+// multi: the call has more than one view (its profile labels end in `_views`); the launch covers views[0, n)
+int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, bool multi, const float *means3D, const float *shs,
                                 const float *colors_precomp, const float *opacities, const float *scales,
                                 const float *rotations, const float *transmat_precomp, const StateView *st,
                                 const ScratchView *sc, int32_t *const *radii, hipStream_t s);
-int launch_binning(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vb = nullptr);
+int launch_binning(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb);
 // the lists of a subset of the surfels a coarse call has binned, by filtering its lists (binning.hip); cst = view 0 of the coarse state
-int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vb, StateView cst,
+int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb, StateView cst,
                           long long coarse_stride, const int32_t *inv);
 int launch_composite_fwd(const ViewDev &v, StateView st, ScratchView sc, float *out_color, float *out_allmap,
-                         hipStream_t s, const ViewBatch *vb = nullptr);
+                         hipStream_t s, const ViewBatch &vb);
 // re-orders the backward's work items by what they cost the forward AND zero-fills [zero_base, zero_base + zero_bytes) (per view at
 // the scratch stride): the one launch in front of composite_bwd
-int launch_bwd_order(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vb, void *zero_base, int64_t zero_bytes);
+int launch_bwd_order(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb, void *zero_base, int64_t zero_bytes);
 int launch_composite_bwd(const ViewDev &v, StateView st, ScratchView sc, const float *dL_dcolor,
-                         const float *dL_dallmap, hipStream_t s, const ViewBatch *vb = nullptr);
-int launch_preprocess_bwd(const ViewDev &v, const float *means3D, const float *shs,
-                          const float *colors_precomp, const float *scales, const float *rotations,
-                          const float *transmat_precomp, const int32_t *radii, StateView st,
-                          ScratchView sc, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs,
-                          float *dL_dcolors, float *dL_dopacities, float *dL_dscales,
-                          float *dL_drotations, float *dL_dtransmat, hipStream_t s);
-int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, int accumulate, const float *means3D,
+                         const float *dL_dallmap, hipStream_t s, const ViewBatch &vb);
+int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, bool multi, int accumulate, const float *means3D,
                                 const float *shs, const float *colors_precomp, const float *scales, const float *rotations,
                                 const float *transmat_precomp, const int32_t *const *radii, const StateView *st,
                                 const ScratchView *sc, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs,

@@ -279,15 +279,15 @@ composite_fwd_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint2
                      float *__restrict__ ckpt, uint2 *__restrict__ pair_mask, uint32_t *__restrict__ tile_maxc,
                      uint32_t *__restrict__ seg_cost,
                      float *__restrict__ out_color, float *__restrict__ out_allmap, const ViewBatch vb) {
-    {   // this workgroup's view (blockIdx.z; a single-view launch has strides 0)
+    {   // this workgroup's view (blockIdx.z)
         const long long sst = vb.state_stride, HWb = (long long)v.H * v.W * 4;
         header = l2d_view_ptr(header, sst); ranges = l2d_view_ptr(ranges, sst); point_list = l2d_view_ptr(point_list, sst);
         geom = l2d_view_ptr(geom, sst); tile_order = l2d_view_ptr(tile_order, sst); cullbox = l2d_view_ptr(cullbox, sst);
         final_T = l2d_view_ptr(final_T, sst); n_contrib = l2d_view_ptr(n_contrib, sst); seg_base = l2d_view_ptr(seg_base, sst);
         seg_cnt = l2d_view_ptr(seg_cnt, sst); ckpt = l2d_view_ptr(ckpt, sst); pair_mask = l2d_view_ptr(pair_mask, sst);
         tile_maxc = l2d_view_ptr(tile_maxc, sst); seg_cost = l2d_view_ptr(seg_cost, sst);
-        out_color = l2d_view_ptr(out_color, vb.n ? 3 * HWb : 0); out_allmap = l2d_view_ptr(out_allmap, vb.n ? 7 * HWb : 0);
-        if (vb.n) v.bg = vb.bg[blockIdx.z];
+        out_color = l2d_view_ptr(out_color, 3 * HWb); out_allmap = l2d_view_ptr(out_allmap, 7 * HWb);
+        v.bg = vb.bg[blockIdx.z];
     }
     constexpr int CHUNK = FWD_CHUNK;
     static_assert(L2D_SEG % FWD_CHUNK == 0, "segment boundaries must fall on round boundaries");
@@ -677,8 +677,8 @@ composite_bwd_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint2
         ckpt = l2d_view_ptr(ckpt, sst); pair_mask = l2d_view_ptr(pair_mask, sst); pair_pos = l2d_view_ptr(pair_pos, sst);
         tile_maxc = l2d_view_ptr(tile_maxc, sst);
         pair_grad = l2d_view_ptr(pair_grad, qst); pair_valid = l2d_view_ptr(pair_valid, qst);
-        dL_dcolor = l2d_view_ptr(dL_dcolor, vb.n ? 3 * HWb : 0); dL_dallmap = l2d_view_ptr(dL_dallmap, vb.n ? 7 * HWb : 0);
-        if (vb.n) v.bg = vb.bg[blockIdx.z];
+        dL_dcolor = l2d_view_ptr(dL_dcolor, 3 * HWb); dL_dallmap = l2d_view_ptr(dL_dallmap, 7 * HWb);
+        v.bg = vb.bg[blockIdx.z];
     }
     constexpr int WIN = SLAB_WIN;
     constexpr int POOL = MAPS ? SLAB_POOL : SLAB_POOL_COLOR, SF = MAPS ? SLAB_F : SLAB_F_COLOR;
@@ -1310,11 +1310,9 @@ bwd_order_kernel(ViewDev v, uint32_t *__restrict__ header, uint2 *__restrict__ b
 }  // namespace
 
 int launch_composite_fwd(const ViewDev &v, StateView st, ScratchView sc, float *out_color, float *out_allmap,
-                         hipStream_t s, const ViewBatch *vbp) {
+                         hipStream_t s, const ViewBatch &vb) {
     (void)sc;
-    ViewBatch vb{};
-    if (vbp) vb = *vbp;
-    const unsigned nz = vbp ? (unsigned)vb.n : 1u;    // blockIdx.z = view (st / out_* are view 0's)
+    const unsigned nz = (unsigned)vb.n;    // blockIdx.z = view (st / out_* are view 0's)
     {
         L2D_PROF(v.fwd_only ? "composite_fwd_only" : "composite_fwd", s);
         auto kern = v.fwd_only ? composite_fwd_kernel<false> : composite_fwd_kernel<true>;
@@ -1326,21 +1324,19 @@ int launch_composite_fwd(const ViewDev &v, StateView st, ScratchView sc, float *
     return LARA2DGS_OK;
 }
 
-int launch_bwd_order(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch *vbp, void *zero_base, int64_t zero_bytes) {
+int launch_bwd_order(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s, const ViewBatch &vb, void *zero_base, int64_t zero_bytes) {
     (void)sc;
     L2D_PROF("bwd_order", s);
     const int64_t zb = (zero_bytes + 15) / 16 * 16;      // (the region is 256-byte aligned and padded: rounding up stays inside it)
     const unsigned zw = zb > 0 ? (unsigned)((zb / 16 + 8191) / 8192 < 128 ? (zb / 16 + 8191) / 8192 : 128) : 0u;
-    hipLaunchKernelGGL(bwd_order_kernel, dim3(1 + zw, 1, vbp ? (unsigned)vbp->n : 1u), dim3(1024), 0, s, v, st.header, st.bwd_items, st.seg_cnt,
-                       st.seg_cost, vbp ? vbp->state_stride : 0ll, (char *)zero_base, (long long)zb, vbp ? vbp->scratch_stride : 0ll);
+    hipLaunchKernelGGL(bwd_order_kernel, dim3(1 + zw, 1, (unsigned)vb.n), dim3(1024), 0, s, v, st.header, st.bwd_items, st.seg_cnt,
+                       st.seg_cost, vb.state_stride, (char *)zero_base, (long long)zb, vb.scratch_stride);
     L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
 int launch_composite_bwd(const ViewDev &v, StateView st, ScratchView sc, const float *dL_dcolor,
-                         const float *dL_dallmap, hipStream_t s, const ViewBatch *vbp) {
-    ViewBatch vb{};
-    if (vbp) vb = *vbp;
+                         const float *dL_dallmap, hipStream_t s, const ViewBatch &vb) {
     {
         L2D_PROF(dL_dallmap ? "composite_bwd" : "composite_bwd_color", s);
         // one workgroup per (tile, segment); the count lives on the device (header[3]), so launch
@@ -1348,7 +1344,7 @@ int launch_composite_bwd(const ViewDev &v, StateView st, ScratchView sc, const f
         const unsigned grid = (unsigned)v.tiles + v.cap / L2D_SEG;
         // dL_dallmap == NULL: the gradient on the seven maps is zero -> the colour-only kernel
         auto kern = dL_dallmap ? composite_bwd_kernel<true> : composite_bwd_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3(grid, 1, vbp ? (unsigned)vb.n : 1u), dim3(256), 0, s, v, st.header, st.ranges,
+        hipLaunchKernelGGL(kern, dim3(grid, 1, (unsigned)vb.n), dim3(256), 0, s, v, st.header, st.ranges,
                            st.point_list, (const float4 *)st.geom, st.tile_order,
                            (const float4 *)st.cullbox, st.final_T, st.n_contrib, st.seg_base, st.seg_cnt, st.bwd_order,
                            st.bwd_items, st.ckpt, st.pair_mask, st.tile_maxc, dL_dcolor, dL_dallmap, st.pair_pos, sc.pair_grad,

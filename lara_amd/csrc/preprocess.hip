@@ -313,21 +313,6 @@ preprocess_fwd_block(const ViewDev &v, const int block, const float *__restrict_
     }
 }
 
-template <int DEG>
-__global__ void __launch_bounds__(256)
-preprocess_fwd_kernel(ViewDev v, const float *__restrict__ means3D, const float *__restrict__ shs,
-                      const float *__restrict__ colors_precomp, const float *__restrict__ opacities,
-                      const float2 *__restrict__ scales, const float4 *__restrict__ rotations,
-                      const float *__restrict__ transmat_precomp, float4 *__restrict__ geom,
-                      float4 *__restrict__ cullbox, uint4 *__restrict__ rect_out,
-                      uint32_t *__restrict__ tile_count, uint32_t *__restrict__ block_tot,
-                      int32_t *__restrict__ radii, const int use_lds) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    __shared__ uint32_t wsum[4];
-    preprocess_fwd_block<DEG>(v, (int)blockIdx.x, means3D, shs, colors_precomp, opacities, scales, rotations, transmat_precomp,
-                              geom, cullbox, rect_out, tile_count, block_tot, radii, use_lds, hist, wsum);
-}
-
 // ONE launch for the n cameras of a multi-view call ("shared preprocess inputs, per-camera T").
 // The camera is the FAST index of the workgroup id: the n workgroups that process the same 256 surfels run next to
 // each other, so the surfels' 88 input bytes come from HBM once and from L2 n - 1 times.
@@ -609,32 +594,11 @@ write_surfel_grad(const ViewDev &v, const int idx, const SurfelGrad<DEG> &G, con
     }
 }
 
-template <int DEG>
-__global__ void __launch_bounds__(256)
-preprocess_bwd_kernel(ViewDev v, const float *__restrict__ means3D, const float *__restrict__ shs,
-                      const float *__restrict__ colors_precomp, const float2 *__restrict__ scales,
-                      const float4 *__restrict__ rotations, const float *__restrict__ transmat_precomp,
-                      const int32_t *__restrict__ radii, const float4 *__restrict__ geom,
-                      const uint32_t *__restrict__ pair_base,
-                      const float4 *__restrict__ pair_grad, const uint8_t *__restrict__ pair_valid,
-                      float *__restrict__ dL_dmeans3D,
-                      float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs,
-                      float *__restrict__ dL_dcolors, float *__restrict__ dL_dopacities,
-                      float2 *__restrict__ dL_dscales, float4 *__restrict__ dL_drots,
-                      float *__restrict__ dL_dtransmat) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= v.P) return;
-    SurfelGrad<DEG> G;
-    surfel_backward<DEG>(v, idx, means3D, shs, colors_precomp, scales, rotations, transmat_precomp, radii, geom, pair_base,
-                         pair_grad, pair_valid, G);
-    write_surfel_grad<DEG>(v, idx, G, colors_precomp == nullptr, colors_precomp != nullptr, transmat_precomp != nullptr,
-                           dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacities, dL_dscales, dL_drots, dL_dtransmat);
-}
-
-// ONE launch for the n views of a multi-view call: a thread walks its surfel through the views in order, adds each
-// view's contribution in registers (view 0, then + view 1, ...: the order and the roundings of adding the per-view
-// gradient tensors one after the other) and writes the summed gradient once -- the surfel's inputs are read once, no
-// per-view gradient tensors, no summation pass.
+// ONE launch for the n views of a call: a thread walks its surfel through the views in order, adds each view's
+// contribution in registers (view 0, then + view 1, ...: the order and the roundings of adding the per-view gradient
+// tensors one after the other) and writes the summed gradient once -- the surfel's inputs are read once, no per-view
+// gradient tensors, no summation pass.  FOLD = false (one view, no running sum to continue) writes view 0's gradient
+// directly: the running sum and the view loop hold twice the registers of that write (DEG 3: 256 VGPRs against 170).
 struct BwdViews {
     int n;
     const float *viewmatrix[L2D_MAX_VIEWS], *projmatrix[L2D_MAX_VIEWS], *campos[L2D_MAX_VIEWS];
@@ -644,18 +608,26 @@ struct BwdViews {
     const uint8_t *pair_valid[L2D_MAX_VIEWS];
 };
 
-template <int DEG>
+template <int DEG, bool FOLD>
 __global__ void __launch_bounds__(256)
 preprocess_bwd_views_kernel(ViewDev v, BwdViews bv, const int accumulate, const float *__restrict__ means3D,
                             const float *__restrict__ shs, const float *__restrict__ colors_precomp,
                             const float2 *__restrict__ scales, const float4 *__restrict__ rotations,
-                            const float *__restrict__ transmat_precomp, float *dL_dmeans3D, float *dL_dmeans2D,
-                            float *dL_dshs, float *dL_dcolors, float *dL_dopacities, float2 *dL_dscales, float4 *dL_drots,
-                            float *dL_dtransmat) {
+                            const float *__restrict__ transmat_precomp, float *__restrict__ dL_dmeans3D,
+                            float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs, float *__restrict__ dL_dcolors,
+                            float *__restrict__ dL_dopacities, float2 *__restrict__ dL_dscales,
+                            float4 *__restrict__ dL_drots, float *__restrict__ dL_dtransmat) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= v.P) return;
     const bool has_sh = colors_precomp == nullptr, has_col = !has_sh, has_tm = transmat_precomp != nullptr;
     SurfelGrad<DEG> A;
+    if (!FOLD) {    // one view (v is its ViewDev), nothing to continue: its gradient straight to the outputs
+        surfel_backward<DEG>(v, idx, means3D, shs, colors_precomp, scales, rotations, transmat_precomp, bv.radii[0],
+                             bv.geom[0], bv.pair_base[0], bv.pair_grad[0], bv.pair_valid[0], A);
+        write_surfel_grad<DEG>(v, idx, A, has_sh, has_col, has_tm, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,
+                               dL_dopacities, dL_dscales, dL_drots, dL_dtransmat);
+        return;
+    }
     if (accumulate) {   // (a call with more than L2D_MAX_VIEWS views: continue the running sums of the launch before)
         A.zero();
         A.dopac = dL_dopacities[idx];
@@ -685,34 +657,7 @@ preprocess_bwd_views_kernel(ViewDev v, BwdViews bv, const int accumulate, const 
 
 }  // namespace
 
-int launch_preprocess_fwd(const ViewDev &v, const float *means3D, const float *shs,
-                          const float *colors_precomp, const float *opacities, const float *scales,
-                          const float *rotations, const float *transmat_precomp, StateView st,
-                          ScratchView sc, int32_t *radii, hipStream_t s) {
-    if (v.P == 0) return LARA2DGS_OK;
-    const dim3 grid((v.P + 255) / 256), block(256);
-    const int use_lds = v.tiles <= L2D_LDS_HIST_TILES;
-    const size_t lds_bytes = use_lds ? (size_t)v.tiles * 4 : 0;
-#define L2D_PRE(DEG)                                                                             \
-    hipLaunchKernelGGL(preprocess_fwd_kernel<DEG>, grid, block, lds_bytes, s, v, means3D, shs,   \
-                       colors_precomp, opacities, (const float2 *)scales,                        \
-                       (const float4 *)rotations, transmat_precomp, st.geom, st.cullbox,         \
-                       sc.rect, sc.tile_count, sc.block_tot, radii, use_lds)
-    {
-        L2D_PROF("preprocess_fwd", s);
-        switch (colors_precomp ? 0 : v.deg) {
-        case 0: L2D_PRE(0); break;
-        case 1: L2D_PRE(1); break;
-        case 2: L2D_PRE(2); break;
-        default: L2D_PRE(3); break;
-        }
-    }
-#undef L2D_PRE
-    L2D_CHECK_LAUNCH();
-    return LARA2DGS_OK;
-}
-
-int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, const float *means3D, const float *shs,
+int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, bool multi, const float *means3D, const float *shs,
                                 const float *colors_precomp, const float *opacities, const float *scales,
                                 const float *rotations, const float *transmat_precomp, const StateView *st,
                                 const ScratchView *sc, int32_t *const *radii, hipStream_t s) {
@@ -734,7 +679,7 @@ int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, c
                        colors_precomp, opacities, (const float2 *)scales, (const float4 *)rotations,     \
                        transmat_precomp, use_lds)
     {
-        L2D_PROF("preprocess_fwd_views", s);
+        L2D_PROF(multi ? "preprocess_fwd_views" : "preprocess_fwd", s);
         switch (colors_precomp ? 0 : v.deg) {
         case 0: L2D_PREV(0); break;
         case 1: L2D_PREV(1); break;
@@ -743,35 +688,6 @@ int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, c
         }
     }
 #undef L2D_PREV
-    L2D_CHECK_LAUNCH();
-    return LARA2DGS_OK;
-}
-
-int launch_preprocess_bwd(const ViewDev &v, const float *means3D, const float *shs,
-                          const float *colors_precomp, const float *scales, const float *rotations,
-                          const float *transmat_precomp, const int32_t *radii, StateView st,
-                          ScratchView sc, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs,
-                          float *dL_dcolors, float *dL_dopacities, float *dL_dscales,
-                          float *dL_drotations, float *dL_dtransmat, hipStream_t s) {
-    if (v.P == 0) return LARA2DGS_OK;
-    const dim3 grid((v.P + 255) / 256), block(256);
-#define L2D_PREB(DEG)                                                                            \
-    hipLaunchKernelGGL(preprocess_bwd_kernel<DEG>, grid, block, 0, s, v, means3D, shs,           \
-                       colors_precomp, (const float2 *)scales, (const float4 *)rotations,        \
-                       transmat_precomp, radii, (const float4 *)st.geom, st.pair_base,           \
-                       (const float4 *)sc.pair_grad, (const uint8_t *)sc.pair_valid,                 \
-                       dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacities,             \
-                       (float2 *)dL_dscales, (float4 *)dL_drotations, dL_dtransmat)
-    {
-        L2D_PROF("preprocess_bwd", s);
-        switch (colors_precomp ? 0 : v.deg) {
-        case 0: L2D_PREB(0); break;
-        case 1: L2D_PREB(1); break;
-        case 2: L2D_PREB(2); break;
-        default: L2D_PREB(3); break;
-        }
-    }
-#undef L2D_PREB
     L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
@@ -785,7 +701,7 @@ int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, ui
     return LARA2DGS_OK;
 }
 
-int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, int accumulate, const float *means3D,
+int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, bool multi, int accumulate, const float *means3D,
                                 const float *shs, const float *colors_precomp, const float *scales, const float *rotations,
                                 const float *transmat_precomp, const int32_t *const *radii, const StateView *st,
                                 const ScratchView *sc, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs,
@@ -801,13 +717,14 @@ int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, i
         bv.pair_grad[i] = (const float4 *)sc[i].pair_grad; bv.pair_valid[i] = (const uint8_t *)sc[i].pair_valid;
     }
     const dim3 grid((v.P + 255) / 256), block(256);
-#define L2D_PREBV(DEG)                                                                                         \
-    hipLaunchKernelGGL(preprocess_bwd_views_kernel<DEG>, grid, block, 0, s, v, bv, accumulate, means3D, shs,   \
-                       colors_precomp, (const float2 *)scales, (const float4 *)rotations, transmat_precomp,   \
-                       dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacities, (float2 *)dL_dscales,      \
-                       (float4 *)dL_drotations, dL_dtransmat)
+    const bool fold = n > 1 || accumulate;
+#define L2D_PREBV(DEG)                                                                                                  \
+    hipLaunchKernelGGL((fold ? preprocess_bwd_views_kernel<DEG, true> : preprocess_bwd_views_kernel<DEG, false>), grid, \
+                       block, 0, s, v, bv, accumulate, means3D, shs, colors_precomp, (const float2 *)scales,            \
+                       (const float4 *)rotations, transmat_precomp, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,      \
+                       dL_dopacities, (float2 *)dL_dscales, (float4 *)dL_drotations, dL_dtransmat)
     {
-        L2D_PROF("preprocess_bwd_views", s);
+        L2D_PROF(multi ? "preprocess_bwd_views" : "preprocess_bwd", s);
         switch (colors_precomp ? 0 : v.deg) {
         case 0: L2D_PREBV(0); break;
         case 1: L2D_PREBV(1); break;

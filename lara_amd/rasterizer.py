@@ -416,7 +416,7 @@ def _make_view(rs: GaussianRasterizationSettings, P: int, M: int, cap: int, devi
 
 
 def _validate(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_degree):
-    """Shape / device checks shared by the per-view and the multi-view operator; returns the kernel-ready tensors."""
+    """Shape / device checks of the operator; returns the kernel-ready tensors."""
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
@@ -451,112 +451,8 @@ def _needs_state(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-def _forward_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, forward_only=False):
-    """Validate, allocate, enqueue the forward; returns once its pair count is known and it fits (see the workspace policy).
-    `forward_only`: nothing is kept for a backward and the returned `state` is the short one."""
-    lib = load_library()
-    device, P, M, (means3D_c, sh_c, col_c, opa_c, sc_c, rot_c, tm_c) = _validate(
-        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.sh_degree)
-    H, W = int(rs.image_height), int(rs.image_width)
-    fo = int(bool(forward_only))
-    with torch.cuda.device(device):
-        view, keep = _make_view(rs, P, M, 0, device)
-        view.forward_only = fo
-        color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-        allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((P,), dtype=torch.int32, device=device)
-
-        def enqueue(cap, counts_ptr):
-            view.capacity = cap
-            view.counts_out = counts_ptr
-            state = _alloc_bytes(lib.lara2dgs_state_bytes(_sizing_P(P), H, W, cap, fo), device)
-            scratch = _get_scratch(device, lib.lara2dgs_scratch_bytes(_sizing_P(P), H, W, cap, fo))
-            rc = lib.lara2dgs_forward(ctypes.byref(view), _ptr(means3D_c), _ptr(sh_c), _ptr(col_c),
-                                      _ptr(opa_c), _ptr(sc_c), _ptr(rot_c), _ptr(tm_c),
-                                      color.data_ptr(), allmap.data_ptr(), radii.data_ptr(),
-                                      state.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
-            _check(rc, "lara2dgs_forward")
-            return state, (lambda: state[:64].view(torch.int32)), None
-
-        state, cap, _, D = _run_forward(_bucket(device, P, H, W), 1, enqueue, bool(rs.debug))
-    return dict(color=color, radii=radii, allmap=allmap, state=state, cap=cap, D=D, M=M, keep=keep,
-                inputs=(means3D_c, sh_c, col_c, sc_c, rot_c, tm_c))
-
-
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                cov3Ds_precomp, raster_settings):
-        rs = raster_settings
-        r = _forward_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs)
-        color, radii, allmap, M, keep = r["color"], r["radii"], r["allmap"], r["M"], r["keep"]
-        means3D_c, sh_c, col_c, sc_c, rot_c, tm_c = r["inputs"]
-
-        ctx.raster_settings = rs
-        ctx.M = M
-        ctx.prefiltered_bits = int(bool(rs.prefiltered)) | (2 if _cull_transparent else 0)   # as the forward ran
-        ctx.state, ctx.cap, ctx.D = r["state"], r["cap"], r["D"]
-        ctx.flags = (sh_c is not None, col_c is not None, sc_c is not None, tm_c is not None)
-        ctx.shapes = (sh.shape if sh_c is not None else None, opacities.shape)
-        empty = means3D_c.new_empty(0)
-        ctx.save_for_backward(means3D_c,
-                              sh_c if sh_c is not None else empty,
-                              col_c if col_c is not None else empty,
-                              sc_c if sc_c is not None else empty,
-                              rot_c if rot_c is not None else empty,
-                              tm_c if tm_c is not None else empty,
-                              radii, *keep)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)      # (else autograd zero-fills a gradient for the int32 `radii` on every backward)
-        return color, radii, allmap
-
-    @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_allmap):
-        lib = load_library()
-        (means3D, sh, col, sc, rot, tm, radii, bg, vm, pm, cp) = ctx.saved_tensors
-        has_sh, has_col, has_sr, has_tm = ctx.flags
-        rs = ctx.raster_settings
-        device = means3D.device
-        P = means3D.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
-        state, cap = ctx.state, ctx.cap
-        with torch.cuda.device(device):
-            if grad_color is None:
-                grad_color = torch.zeros((3, H, W), dtype=torch.float32, device=device)
-            grad_color = _prep(grad_color, "grad_color", device)
-            if grad_allmap is not None:       # (None = no gradient on the maps: the library's colour-only backward)
-                grad_allmap = _prep(grad_allmap, "grad_allmap", device)
-            view = _View(P, int(rs.sh_degree), ctx.M, H, W, float(rs.tanfovx), float(rs.tanfovy),
-                         float(rs.scale_modifier), ctx.prefiltered_bits, int(bool(rs.debug)), 0,
-                         cap, bg.data_ptr(), vm.data_ptr(), pm.data_ptr(), cp.data_ptr(), None)
-            new = lambda *s: torch.empty(s, dtype=torch.float32, device=device)
-            g_means3D = new(P, 3)
-            g_means2D = new(P, 3)
-            g_opac = new(P, 1)
-            g_sh = new(P, ctx.M, 3) if has_sh else None
-            g_col = new(P, 3) if has_col else None
-            g_sc = new(P, 2) if has_sr else None
-            g_rot = new(P, 4) if has_sr else None
-            g_tm = new(P, 9) if has_tm else None
-            scratch = _get_scratch(device, lib.lara2dgs_scratch_bytes(_sizing_P(P), H, W, cap, 0))
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = lib.lara2dgs_backward(
-                ctypes.byref(view), _ptr(means3D), _ptr(sh if has_sh else None),
-                _ptr(col if has_col else None), _ptr(sc if has_sr else None),
-                _ptr(rot if has_sr else None), _ptr(tm if has_tm else None), radii.data_ptr(),
-                grad_color.data_ptr(), _ptr(grad_allmap), state.data_ptr(), scratch.data_ptr(),
-                g_means3D.data_ptr(), g_means2D.data_ptr(), _ptr(g_sh), _ptr(g_col),
-                g_opac.data_ptr(), _ptr(g_sc), _ptr(g_rot), _ptr(g_tm), stream)
-            _check(rc, "lara2dgs_backward")
-        if has_sh and ctx.shapes[0] is not None:
-            g_sh = g_sh.view(ctx.shapes[0])
-        g_opac = g_opac.view(ctx.shapes[1])
-        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
-        return g_means3D, (g_means2D if ctx.needs_input_grad[1] else None), g_sh, g_col, g_opac, g_sc, g_rot, g_tm, None
-
-
 # ---------------------------------------------------------------------------------------------
-# opt-in: all views of a scene in one call (SURVEY.md section 8f-2)
+# the operator: the n views of a scene in one call; one view is the case n = 1
 # ---------------------------------------------------------------------------------------------
 def _views_array(settings, P, M, cap, device, prefiltered_bits=None):
     arr = (_View * len(settings))()
@@ -571,11 +467,13 @@ def _views_array(settings, P, M, cap, device, prefiltered_bits=None):
 
 
 def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, forward_only=False,
-                        subset=None):
-    """The n views of a scene in one library call (see `_forward_impl`); `state` holds the n per-view states at stride `sb`.
-    `subset` = (state, state stride, capacity, surfel count of an earlier call with the same cameras, ascending row indices of this
-    call's surfels in that call's): the lists are filtered out of the earlier call's instead of scattered and sorted again
-    (`lara2dgs_forward_views_subset`)."""
+                        subset=None, batched=True):
+    """Validate, allocate, enqueue the forward of the n views of a scene in one library call; returns once its pair count is
+    known and it fits (see the workspace policy).  `state` holds the n per-view states at stride `sb`.  `forward_only`: nothing
+    is kept for a backward and the returned `state` is the short one.  `subset` = (state, state stride, capacity, surfel count
+    of an earlier call with the same cameras, ascending row indices of this call's surfels in that call's): the lists are
+    filtered out of the earlier call's instead of scattered and sorted again (`lara2dgs_forward_views_subset`).
+    `batched=False` (one view): the outputs come without the leading view dimension."""
     lib = load_library()
     rs0 = settings[0]
     n = len(settings)
@@ -590,9 +488,10 @@ def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotation
     fo = int(bool(forward_only))
     with torch.cuda.device(device):
         views, keep = _views_array(settings, P, M, 0, device)
-        color = torch.empty((n, 3, H, W), dtype=torch.float32, device=device)
-        allmap = torch.empty((n, 7, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((n, P), dtype=torch.int32, device=device)
+        lead = (n,) if batched else ()
+        color = torch.empty(lead + (3, H, W), dtype=torch.float32, device=device)
+        allmap = torch.empty(lead + (7, H, W), dtype=torch.float32, device=device)
+        radii = torch.empty(lead + (P,), dtype=torch.int32, device=device)
         sub = None
         if subset is not None and P > 0:
             c_state, c_sb, c_cap, c_P, idx = subset
@@ -628,13 +527,16 @@ def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotation
 class _RasterizeViews(torch.autograd.Function):
     """ONE autograd node for the n views of a scene: same surfels, n cameras (the reference's loop at
     lightning/network.py:486-497 issues n nodes).  Per-camera state is carved from one allocation; every kernel is one
-    launch over the cameras and the gradient comes back already summed over the views."""
+    launch over the cameras and the gradient comes back already summed over the views.  The reference's one-view operator
+    is the node of one view with `batched=False`."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=None,
+                batched=True):
         settings = tuple(settings)
         rs0 = settings[0]
-        r = _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=subset)
+        r = _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=subset,
+                                batched=batched)
         color, radii, allmap, M, keep = r["color"], r["radii"], r["allmap"], r["M"], r["keep"]
         means3D_c, sh_c, col_c, sc_c, rot_c, tm_c = r["inputs"]
         ctx.state, ctx.cap, ctx.strides, ctx.D = r["state"], r["cap"], r["strides"], r["D"]
@@ -648,7 +550,7 @@ class _RasterizeViews(torch.autograd.Function):
                               sc_c if sc_c is not None else empty, rot_c if rot_c is not None else empty,
                               tm_c if tm_c is not None else empty, radii, *keep)
         ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)      # (else autograd zero-fills a gradient for the int32 `radii` [n, P] on every backward)
+        ctx.set_materialize_grads(False)      # (else autograd zero-fills a gradient for the int32 `radii` on every backward)
         return color, radii, allmap
 
     @staticmethod
@@ -700,7 +602,7 @@ class _RasterizeViews(torch.autograd.Function):
         return (sec(G.means3D, 3, (P, 3)), sec(G.means2D, 3, (P, 3)) if ctx.needs_input_grad[1] else None, g_sh,
                 sec(G.colors, 3, (P, 3)) if has_col else None, g_opac,
                 sec(G.scales, 2, (P, 2)) if has_sr else None, sec(G.rotations, 4, (P, 4)) if has_sr else None,
-                sec(G.transmat, 9, (P, 9)) if has_tm else None, None, None)
+                sec(G.transmat, 9, (P, 9)) if has_tm else None, None, None, None)
 
 
 def rasterize_gaussians_views(settings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
@@ -756,10 +658,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         _as_f32(t) for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
     if not _needs_state(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
         # inference (evaluation.py:129 / tools/meshExtractor.py:85 run under no_grad): a forward-only call, no autograd node
-        r = _forward_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, True)
+        r = _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, (raster_settings,), True,
+                                batched=False)
         return r["color"], r["radii"], r["allmap"]
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales,
-                                     rotations, cov3Ds_precomp, raster_settings)
+    return _RasterizeViews.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                 (raster_settings,), None, False)
 
 
 class GaussianRasterizer(nn.Module):
@@ -846,8 +749,8 @@ def forward_with_state(raster_settings, means3D, opacities, shs=None, colors_pre
     """One forward returning its ``state`` too: ``dict(color, radii, allmap, state, cap, D, views, ...)`` -- the training-mode
     forward's full state, or (``forward_only``) the short one of an inference call."""
     with torch.no_grad():
-        r = _forward_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                          raster_settings, forward_only)
+        r = _forward_views_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, (raster_settings,),
+                                forward_only, batched=False)
     P = means3D.shape[0]
     r["views"] = state_views(r["state"], P, int(raster_settings.image_height),      # (the layout is the real P's; the buffer is sized for _sizing_P)
                              int(raster_settings.image_width), r["cap"], forward_only)
