@@ -170,10 +170,8 @@ def _forward_inference(image_feats, eps_block, eps_final, R, out_dim, pos_embed,
         raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
     lib = _lib()
     dev = image_feats.device
-    n_layers = len(layer_params) // _NLP
     B, V, cond_dim = image_feats.shape[:3]
     S = image_feats.shape[3] * image_feats.shape[4] * image_feats.shape[5]
-    M = B * R ** 3
     # `b v c d h w -> (b d h w) v c` (network.py:145-150) and the bf16 cast in one pass: per scene, the
     # [v c, d h w] matrix transposed
     feats = image_feats.detach().float().contiguous()
@@ -181,6 +179,17 @@ def _forward_inference(image_feats, eps_block, eps_final, R, out_dim, pos_embed,
     with torch.cuda.device(dev):
         _check(lib.lara_batched_transpose(B, V * cond_dim, S, feats.data_ptr(), cond_bf.data_ptr(), 1, _stream(dev)),
                "lara_batched_transpose")
+    return _inference_from_cond(cond_bf, B, cond_dim, eps_block, eps_final, R, out_dim, pos_embed, norm_w, norm_b, deconv_w, deconv_b,
+                                *layer_params)
+
+
+def _inference_from_cond(cond_bf, B, cond_dim, eps_block, eps_final, R, out_dim, pos_embed, norm_w, norm_b, deconv_w, deconv_b,
+                         *layer_params):
+    """`_forward_inference` from the bf16 operand [B R^3, V, cond_dim] on."""
+    lib = _lib()
+    dev = cond_bf.device
+    n_layers = len(layer_params) // _NLP
+    M = B * R ** 3
     x = volume_to_tokens(pos_embed.detach().float()).repeat(B, 1)       # network.py:152
     ws = _workspace(dev, "fwd", lib.lara_groupblock_workspace_bytes(B, R))
     with torch.cuda.device(dev):
@@ -278,6 +287,37 @@ class _CondFn(torch.autograd.Function):
                    "lara_batched_transpose")
         sw.dkv_all = sw.flat = None
         return (d_feats if ctx.feat_dtype == torch.float32 else d_feats.to(ctx.feat_dtype)), None
+
+
+class _FeatCondFn(torch.autograd.Function):
+    """`_CondFn` fused with the feature volume (lara_amd.featvol): the forward writes the bf16 operand [B R^3, V, C + E] straight
+    from the image features (layout LARA_FEATVOL_TOKENS), the backward runs the feature-volume backward on dcond itself -- no fp32
+    volume and no transpose in either direction."""
+
+    @staticmethod
+    def forward(ctx, img_feats, ln_w, ln_b, mlp_w, mlp_b, embed, prep, sweep):
+        from .featvol import TOKENS
+        prep.params(ln_w, ln_b, mlp_w, mlp_b, embed)
+        sweep.cond_bf = prep.forward(TOKENS)
+        ctx.sweep, ctx.prep = sweep, prep
+        return torch.zeros(1, dtype=torch.float32, device=img_feats.device)
+
+    @staticmethod
+    def backward(ctx, g_token):
+        from .featvol import TOKENS
+        lib, sw = _lib(), ctx.sweep
+        if not any(ctx.needs_input_grad[:6]):
+            return (None,) * 8
+        dev = sw.dev
+        dcond = torch.empty(sw.cond_bf.shape, dtype=torch.float32, device=dev)
+        lddkv = sw.n_layers * 512
+        with torch.cuda.device(dev):
+            wkv_all_t = torch.cat([f["wkv"] for f in sw.fs], 0).t().contiguous()
+            _check(lib.lara_gemm_nt_bf16(sw.dkv_all.shape[0], sw.cond_dim, lddkv, sw.dkv_all.data_ptr(), wkv_all_t.data_ptr(),
+                                         dcond.data_ptr(), 1, _stream(dev)), "lara_gemm_nt_bf16")
+        sw.dkv_all = sw.flat = None
+        dx, d_lnw, d_lnb, d_w, d_b, d_e = ctx.prep.backward(dcond, TOKENS, ctx.needs_input_grad[5])
+        return dx, d_lnw, d_lnb, d_w, d_b, d_e, None, None
 
 
 class _StartFn(torch.autograd.Function):
@@ -406,9 +446,12 @@ class _HeadFn(torch.autograd.Function):
 
 def _forward_per_block(module, image_feats):
     B, V, C = image_feats.shape[:3]
-    R, n_layers = module.vol_low_res, len(module.layers)
-    sweep = _Sweep(B, R, C, n_layers, float(module.layers[0].norm1.eps), image_feats.device)
-    token = _CondFn.apply(image_feats, sweep)
+    sweep = _Sweep(B, module.vol_low_res, C, len(module.layers), float(module.layers[0].norm1.eps), image_feats.device)
+    return _sweep_from(module, sweep, _CondFn.apply(image_feats, sweep))
+
+
+def _sweep_from(module, sweep, token):
+    B, R = sweep.B, module.vol_low_res
     x = _StartFn.apply(module.pos_embed, token, B, R)
     for l, layer in enumerate(module.layers):
         x = _BlockFn.apply(x, sweep, l, *layer.flat_params())
@@ -473,3 +516,22 @@ class VolTransformer(nn.Module):
         flat = [p for layer in self.layers for p in layer.flat_params()]
         return _forward_inference(image_feats, float(self.layers[0].norm1.eps), float(self.norm.eps), self.vol_low_res, self.out_dim,
                                  self.pos_embed, self.norm.weight, self.norm.bias, self.deconv.weight, self.deconv.bias, *flat)
+
+    def forward_from_image_features(self, feat_volume, batch, img_feats: torch.Tensor, n_views_sel=None) -> torch.Tensor:
+        """``self(feat_volume(batch, img_feats, n_views_sel))`` with the feature volume (a ``lara_amd.featvol.FeatureVolume``) as
+        ONE autograd node in place of the operand transpose: its kernels write the bf16 operand directly and its backward reads
+        dcond directly (network.py:352-379, :448-455)."""
+        prep = feat_volume.prepare(batch, img_feats, n_views_sel)
+        if prep.V != 4 or feat_volume.R != self.n_groups[0]:
+            raise RuntimeError("kernels are specialised for one image-feature voxel per group and 4 input views")
+        B, C = prep.B, prep.C + prep.E
+        args = feat_volume._args(prep.V)
+        if torch.is_grad_enabled():
+            sweep = _Sweep(B, self.vol_low_res, C, len(self.layers), float(self.layers[0].norm1.eps), img_feats.device)
+            return _sweep_from(self, sweep, _FeatCondFn.apply(img_feats, *args, prep, sweep))
+        from .featvol import TOKENS
+        prep.params(*args)
+        flat = [p for layer in self.layers for p in layer.flat_params()]
+        return _inference_from_cond(prep.forward(TOKENS), B, C, float(self.layers[0].norm1.eps), float(self.norm.eps), self.vol_low_res,
+                                    self.out_dim, self.pos_embed, self.norm.weight, self.norm.bias, self.deconv.weight,
+                                    self.deconv.bias, *flat)

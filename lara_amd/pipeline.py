@@ -181,9 +181,10 @@ class LaRaPipeline(nn.Module):
     configs/base.yaml (network.py:306-343): grid_reso = vol_embedding_reso, n_offset_groups, K, sh_degree."""
 
     def __init__(self, vol_decoder, decoder, grid_reso=32, n_offset_groups=32, sh_degree=1, white_bkgd=True, n_views=4,
-                 scene_size=0.5, n_streams=2):
+                 scene_size=0.5, n_streams=2, feat_volume=None):
         super().__init__()
         self.vol_decoder, self.decoder = vol_decoder, decoder
+        self.feat_volume = feat_volume    # lara_amd.featvol.FeatureVolume: the step from the image features (forward_from_image_features)
         self.K = decoder.K
         self.n_views, self.scene_size, self.n_offset_groups = n_views, scene_size, n_offset_groups
         self.gs_render = Renderer(sh_degree=sh_degree, white_background=white_bkgd, radius=1)
@@ -262,6 +263,19 @@ class LaRaPipeline(nn.Module):
         if feat_vol.dim() == 6 and feat_vol.shape[1] != self.n_views:
             raise NotImplementedError(f"lara_amd.pipeline: the image-feature volume holds {feat_vol.shape[1]} views, the pipeline is built for {self.n_views}")
         return self._step(batch, lambda: self.gaussians(feat_vol), feat_vol.device, feat_vol.shape[0], with_fine)
+
+    def forward_from_image_features(self, batch, img_feats, with_fine=True):
+        """The step from the image encoder's features [B * n_views, C, h, w] on (network.py:448-532): ``feat_volume`` builds the
+        image-feature volume; with the HIP ``VolTransformer`` as ``vol_decoder`` it writes the encoder's operand directly, as one
+        autograd node (``VolTransformer.forward_from_image_features``), with any other encoder it hands over the volume."""
+        if self.feat_volume is None:
+            raise RuntimeError("lara_amd.pipeline: forward_from_image_features needs LaRaPipeline(..., feat_volume=FeatureVolume(...))")
+        from .encoder_train import VolTransformer as HipVolTransformer
+        if isinstance(self.vol_decoder, HipVolTransformer):
+            make = lambda: self.gaussians_from_volume(self.vol_decoder.forward_from_image_features(self.feat_volume, batch, img_feats, self.n_views))
+        else:
+            make = lambda: self.gaussians(self.feat_volume(batch, img_feats, self.n_views))
+        return self._step(batch, make, img_feats.device, batch["tar_rays_down"].shape[0], with_fine)
 
     def forward_from_volume(self, batch, volume_feat_up, with_fine=True, autocast=True):
         """The step from the encoder's OUTPUT on (network.py:458-532): what tests hold against the reference's own
