@@ -253,8 +253,12 @@ class LaRaPipeline(nn.Module):
             self.stage_events.append((name, e))
 
     # -- the step ------------------------------------------------------------------------------------------------
-    def forward(self, batch, feat_vol, with_fine=True, n_views_sel=None):
-        """`n_views_sel`: the number of INPUT views, which the reference draws at random in {2, 3, 4} when
+    def forward(self, batch, feat_vol, with_fine=True, n_views_sel=None, return_buffer=False):
+        """`return_buffer`: the output gains ``render_pkg`` in the reference's layout (network.py:482-483, :514-515): per scene
+        the coarse tuple (centers, shs, opacity, scaling, rotation), then with ``with_fine`` the fine tuple (centers[mask],
+        shs_fine, opacity, scaling, rotation, mask) -- the step's own tensors, ``mask`` the one the fine pass used (after
+        ``check_mask``); ``evaluation.py`` hands ``render_pkg[1]`` to ``lara_amd.mesh.MeshExtractor``.
+        `n_views_sel`: the number of INPUT views, which the reference draws at random in {2, 3, 4} when
         ``cfg.train.use_rand_views`` is set (network.py:437-441).  The fused sampler / fine decoder and the encoder's K|V layout
         are built for ``self.n_views`` (4: configs/base.yaml); any other count is rejected here rather than mis-indexed --
         run such a step through ``tools/reference_style.py: network_forward``-style torch operators instead."""
@@ -263,9 +267,9 @@ class LaRaPipeline(nn.Module):
                                       f"{n_views_sel} (cfg.train.use_rand_views): not supported by the fused fine stage")
         if feat_vol.dim() == 6 and feat_vol.shape[1] != self.n_views:
             raise NotImplementedError(f"lara_amd.pipeline: the image-feature volume holds {feat_vol.shape[1]} views, the pipeline is built for {self.n_views}")
-        return self._step(batch, lambda: self.gaussians(feat_vol), feat_vol.device, feat_vol.shape[0], with_fine)
+        return self._step(batch, lambda: self.gaussians(feat_vol), feat_vol.device, feat_vol.shape[0], with_fine, return_buffer)
 
-    def forward_from_image_features(self, batch, img_feats, with_fine=True):
+    def forward_from_image_features(self, batch, img_feats, with_fine=True, return_buffer=False):
         """The step from the image encoder's features [B * n_views, C, h, w] on (network.py:448-532): ``feat_volume`` builds the
         image-feature volume; with the HIP ``VolTransformer`` as ``vol_decoder`` it writes the encoder's operand directly, as one
         autograd node (``VolTransformer.forward_from_image_features``), with any other encoder it hands over the volume."""
@@ -276,24 +280,24 @@ class LaRaPipeline(nn.Module):
             make = lambda: self.gaussians_from_volume(self.vol_decoder.forward_from_image_features(self.feat_volume, batch, img_feats, self.n_views))
         else:
             make = lambda: self.gaussians(self.feat_volume(batch, img_feats, self.n_views))
-        return self._step(batch, make, img_feats.device, batch["tar_rays_down"].shape[0], with_fine)
+        return self._step(batch, make, img_feats.device, batch["tar_rays_down"].shape[0], with_fine, return_buffer)
 
-    def forward_from_images(self, batch, with_fine=True):
+    def forward_from_images(self, batch, with_fine=True, return_buffer=False):
         """The whole step from the input pixels (network.py:435-532): ``image_encoder`` reads ``batch['tar_rgb'][:, :n_views]`` in
         place and its features go to ``forward_from_image_features``."""
         if self.image_encoder is None:
             raise RuntimeError("lara_amd.pipeline: forward_from_images needs LaRaPipeline(..., image_encoder=DinoViT(...))")
         if self.feat_volume is None:
             raise RuntimeError("lara_amd.pipeline: forward_from_images needs LaRaPipeline(..., feat_volume=FeatureVolume(...))")
-        return self.forward_from_image_features(batch, self.image_encoder.image_features(batch, self.n_views), with_fine)
+        return self.forward_from_image_features(batch, self.image_encoder.image_features(batch, self.n_views), with_fine, return_buffer)
 
-    def forward_from_volume(self, batch, volume_feat_up, with_fine=True, autocast=True):
+    def forward_from_volume(self, batch, volume_feat_up, with_fine=True, autocast=True, return_buffer=False):
         """The step from the encoder's OUTPUT on (network.py:458-532): what tests hold against the reference's own
         `Network.forward` run with the same volume features (tests/golden/network_ref.npz)."""
         return self._step(batch, lambda: self.gaussians_from_volume(volume_feat_up, autocast), volume_feat_up.device,
-                          volume_feat_up.shape[0], with_fine)
+                          volume_feat_up.shape[0], with_fine, return_buffer)
 
-    def _step(self, batch, make_gaussians, dev, B, with_fine):
+    def _step(self, batch, make_gaussians, dev, B, with_fine, return_buffer=False):
         if dev.type != "cuda":
             raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
         n_sel = self.n_views
@@ -336,6 +340,8 @@ class LaRaPipeline(nn.Module):
         # [B,P,C] buffer and an accumulation for every use)
         sc = {k: g[k].unbind(0) for k in ("centers", "shs", "opacity", "scaling", "rotation")}
         per_scene = [None] * B
+        buffers = [[(sc["centers"][i], sc["shs"][i], sc["opacity"][i], sc["scaling"][i], sc["rotation"][i])] for i in range(B)] \
+            if return_buffer else None                                          # network.py:482-483
         coarse_raster = [[] for _ in range(B)]       # the coarse calls' own outputs: the fine calls filter their lists (`subset_of`)
         for i in range(B):                                                      # network.py:473-497
             s = sides[i % len(sides)]
@@ -374,6 +380,8 @@ class LaRaPipeline(nn.Module):
                                             co["image"], co["acc_map"], co["depth"], row_views=V)
                     sh_res = forward_fine(self.decoder, vol_rows[i], torch.einsum("lcb->blc", pf), folded)
                     shs_f = sh_res.view(-1, *g["shs"].shape[-2:]) + shs_sel
+                    if return_buffer:                                           # network.py:514-515
+                        buffers[i].append((centers_f, shs_f, sc["opacity"][i], sc["scaling"][i], sc["rotation"][i], masks[i]))
                     self._mark("sampler+forward_fine")
                     co.update(self.gs_render.render_views(
                         cams_of[i], batch["tar_rays"][i], centers_f, shs_f, opacity_f, scaling_f, rotation_f, dev,
@@ -387,10 +395,14 @@ class LaRaPipeline(nn.Module):
                 cur.wait_stream(s)
         if sides[0] is not None:
             hand_over(per_scene, cur)       # made on the scene streams, read by the stack below on the caller's
+            if buffers is not None:
+                hand_over(buffers, cur)     # the fine tuples' tensors (made on the scene streams) go to the caller
         if bufs is not None:
             out = {k: _AssembleScenes.apply(bufs[k], *[o[k] for o in outs]) for k in outs[0]}       # network.py:529, without the copy
         else:
             out = {k: torch.stack([o[k] for o in outs]) for k in outs[0]}       # network.py:529
+        if return_buffer:
+            out["render_pkg"] = [t for scene in buffers for t in scene]
         self._mark("outputs")
         return out
 

@@ -5,8 +5,9 @@ of its 48 views to the host and feeds Open3D's CPU ``ScalableTSDFVolume``.  Open
 and block semantics (include/lara_tsdf.h): by default a view is integrated only into the 16^3-voxel blocks within
 sdf_trunc of its back-projected depth samples, as ``ScalableTSDFVolume`` does (``block_sparse=False``: every voxel, as
 ``UniformTSDFVolume``).  ``extract_triangle_mesh()`` runs marching cubes on the device and returns welded vertices,
-triangles and vertex colours; ``to_open3d_mesh()`` wraps them for the reference's Open3D post-processing (the cluster
-filter, meshExtractor.py:112-135, stays reference code).  No CPU path."""
+triangles and vertex colours; the post-processing (crop, cluster filter, meshExtractor.py:112-135) and the writer are
+``lara_amd.mesh.clean_mesh`` / ``write_obj`` on the device, ``to_open3d_mesh()`` still hands the mesh to Open3D where it is
+installed.  No CPU path."""
 from __future__ import annotations
 
 import ctypes
