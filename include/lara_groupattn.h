@@ -166,7 +166,13 @@ int lara_voltrans_head_backward(int32_t scenes, int32_t R, const float *x, const
 /* Building blocks of the above, exported for the parity tests:
  *   dst[N, Kc] += A[M, N]^T . B[M, Kc]   (bf16 operands, M % 16 == 0, N and Kc even)
  *   LayerNorm(256) backward: dx = dLN(dy; x, gamma) (+ skip); dgamma, dbeta accumulated
- *   backward of the per-group attention core: (q, k|v, dO) -> dq [G*8, 256], dk|dv [G*4, 512], bf16 */
+ *   backward of the per-group attention core: (q, k|v, dO) -> dq [G*8, 256], dk|dv [G*4, 512], bf16
+ *   where lara_groupblock_forward_train keeps each stage inside `saved`: byte offsets of
+ *     xn1, q, kv, o, x1, xn2, z, h, x2, xn3, stats            (n = 11, in this order)
+ *   xn1 q o xn2 xn3: bf16 [M, 256] (xn3 has one more, zeroed, row M); kv: bf16 [M/2, 512]; z h: bf16 [M, 512];
+ *   x1 x2: fp32 [M, 256]; stats: fp32 [M, 2] = (mean, rstd) of norm3's rows.  Host code only; returns 0, or
+ *   LARA2DGS_E_INVALID for a shape the training entry points refuse, a null `offsets` or n != 11. */
+int lara_groupblock_save_offsets(int32_t scenes, int32_t R, int64_t *offsets, int32_t n);
 int64_t lara_gemm_tn_workspace_bytes(void);
 int lara_gemm_tn_bf16(int32_t M, int32_t N, int32_t Kc, const uint16_t *A, const uint16_t *B, float *dst,
                       void *workspace, void *stream);

@@ -142,7 +142,8 @@ gemm_bf16_tn_kernel(const TnP p) {
     // Four register sets: three 16-row slices are in flight while one is multiplied.  With ~3 waves per SIMD
     // (64 accumulator + ~100 vector registers) one slice of look-ahead left the matrix cores waiting on HBM
     // latency most of the time.
-    const int steps = max(0, (m_end - m_start + 15) >> 4), full = steps & ~3;  // (a split may start beyond M)
+    const int rows = max(0, m_end - m_start);  // (a split may start beyond M)
+    const int steps = rows >> 4, full = steps & ~3, tail = rows & 15;
     if (full > 0) {
         load(m_start, a0, b0);
         load(m_start + 16, a1, b1);
@@ -161,6 +162,21 @@ gemm_bf16_tn_kernel(const TnP p) {
     }
     for (int i = full; i < steps; i++) {  // at most three left-over slices (the last split of a ragged M)
         load(m_start + 16 * i, a0, b0);
+        mma(a0, b0);
+    }
+    if (tail) {
+        // M is no multiple of 16 (an odd number of voxel groups; 4 key rows per group): the last slice of the last split.  Rows
+        // beyond M are read from row M - 1 and enter the product as zeros.
+        const int m0 = m_start + 16 * steps;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const int row = m0 + 8 * kh + e, rc = min(row, p.M - 1);
+            const uint32_t bo = (GATHER ? (uint32_t)nb[rc] : (uint32_t)rc * ldb2) + bcol;
+            const uint32_t av = __builtin_amdgcn_raw_buffer_load_b32(ra, (int)((uint32_t)rc * lda2 + (uint32_t)an * 2u), 0, 0);
+            const uint32_t bv = __builtin_amdgcn_raw_buffer_load_b32(rb, (int)bo, 0, 0);
+            a0[e] = row < p.M ? av : 0u;
+            b0[e] = row < p.M ? bv : 0u;
+        }
         mma(a0, b0);
     }
     // accumulator (ta, tb)[reg]: A column nbase + 2 i + ta with i = (reg&3) + 8 (reg>>2) + 4 kh, B column
@@ -1001,7 +1017,8 @@ inline bool tn_ring_shape(int M, int N, int Kc, int lda, int ldb, const float *d
 // dst[N, T*Kc] += A^T . B; `part` holds TN_PART_BYTES
 int gemm_tn(const unsigned short *A, int lda, int N, const unsigned short *B, int ldb, int Kc, int T, const int *nbr,
             int M, float *dst, float *part, hipStream_t s) {
-    if ((M & 15) || (N & 1) || (Kc & 1) || (T > 1 && (Kc & 127))) return LARA2DGS_E_INVALID;
+    // (any M: the direct kernel masks the rows of a last, partial 16-row slice; the gathered table is read 16 entries at a time)
+    if (M <= 0 || (nbr && M < 16) || (N & 1) || (Kc & 1) || (T > 1 && (Kc & 127))) return LARA2DGS_E_INVALID;
     // 32-bit byte offsets and 24-bit row multiplies in the kernel
     if ((size_t)(M + 1) * lda * 2 >= (1ull << 32) || (size_t)(M + 1) * ldb * 2 >= (1ull << 32) || M >= (1 << 24) || ldb >= (1 << 23))
         return LARA2DGS_E_INVALID;
@@ -1325,6 +1342,14 @@ int64_t lara_groupblock_save_bytes(int32_t scenes, int32_t R) {
     return (int64_t)save_layout((int64_t)scenes * R * R * R).total;
 }
 
+int lara_groupblock_save_offsets(int32_t scenes, int32_t R, int64_t *offsets, int32_t n) {
+    if (scenes < 0 || R < 4 || (R & 1) || !offsets || n != 11) return LARA2DGS_E_INVALID;
+    const SaveWs L = save_layout((int64_t)scenes * R * R * R);
+    const size_t at[11] = {L.xn1, L.q, L.kv, L.o, L.x1, L.xn2, L.z, L.h, L.x2, L.xn3, L.stats};
+    for (int i = 0; i < 11; i++) offsets[i] = (int64_t)at[i];
+    return LARA2DGS_OK;
+}
+
 int lara_groupblock_forward_train(int32_t scenes, int32_t R, int32_t cond_dim, const float *x_in, float *x_out,
                                   const uint16_t *cond_bf16, const lara_groupblock_weights *w, void *saved,
                                   void *stream) {
@@ -1566,7 +1591,7 @@ int lara_gemm_nt_bf16(int32_t M, int32_t N, int32_t K, const uint16_t *A, const 
 
 int lara_gemm_tn_bf16(int32_t M, int32_t N, int32_t Kc, const uint16_t *A, const uint16_t *B, float *dst,
                       void *workspace, void *stream) {
-    if (M <= 0 || N <= 0 || Kc <= 0 || !A || !B || !dst || !workspace) return LARA2DGS_E_INVALID;
+    if (M <= 0 || (M & 15) || N <= 0 || Kc <= 0 || !A || !B || !dst || !workspace) return LARA2DGS_E_INVALID;
     return gemm_tn(A, N, N, B, Kc, Kc, 1, nullptr, M, dst, (float *)workspace, (hipStream_t)stream);
 }
 

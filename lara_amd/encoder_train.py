@@ -55,6 +55,8 @@ def _lib():
         lib.lara_batched_transpose.argtypes = [i32, i32, i32, vp, vp, i32, vp]
         lib.lara_groupblock_save_bytes.restype = i64
         lib.lara_groupblock_save_bytes.argtypes = [i32, i32]
+        lib.lara_groupblock_save_offsets.restype = ctypes.c_int
+        lib.lara_groupblock_save_offsets.argtypes = [i32, i32, ctypes.POINTER(i64), i32]
         lib.lara_groupblock_forward_train.restype = ctypes.c_int
         lib.lara_groupblock_forward_train.argtypes = [i32, i32, i32, vp, vp, vp, ctypes.POINTER(_BlockWeights), vp, vp]
         lib.lara_voltrans_head_backward_workspace_bytes.restype = i64

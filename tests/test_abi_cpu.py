@@ -34,6 +34,27 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.lara2dgs_abi_version() == rasterizer.ABI_VERSION
 
 
+def test_block_save_offsets_follow_the_save_area(hip_lib):
+    """lara_groupblock_save_offsets (host code only): eleven increasing, 256-byte aligned offsets inside
+    lara_groupblock_save_bytes; a wrong count or an unsupported shape is refused."""
+    fn = hip_lib.lara_groupblock_save_offsets
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
+    hip_lib.lara_groupblock_save_bytes.restype = ctypes.c_int64
+    hip_lib.lara_groupblock_save_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    for scenes, R in ((1, 4), (3, 6), (4, 32)):
+        M = scenes * R ** 3
+        offs = (ctypes.c_int64 * 11)()
+        assert fn(scenes, R, offs, 11) == 0
+        o = list(offs)
+        assert o[0] == 0 and o == sorted(set(o)) and all(v % 256 == 0 for v in o)
+        sizes = [M * 512] * 4 + [M * 1024, M * 512, M * 1024, M * 1024, M * 1024, M * 512 + 512, M * 8]   # xn1 q kv o x1 xn2 z h x2 xn3 stats
+        assert all(b - a >= n for a, b, n in zip(o, o[1:] + [hip_lib.lara_groupblock_save_bytes(scenes, R)], sizes))
+    for bad in ((1, 4, 10), (1, 4, 12), (1, 5, 11), (1, 2, 11), (-1, 4, 11)):
+        assert fn(bad[0], bad[1], offs, bad[2]) == -1
+    assert fn(1, 4, None, 11) == -1
+
+
 def test_sizes_and_layout_are_consistent(hip_lib):
     P, H, W = 524288, 512, 512
     cap = rasterizer.binning_capacity(P)
