@@ -15,9 +15,11 @@ copies of two float maps and ``np.round(... * 255)`` (:118-141).  Here:
 
 Limits.  SSIM: `pytorch_msssim` is absent from the reference tree and from the build image (version not pinned): the kernel
 follows the published algorithm (11-tap sigma-1.5 Gaussian, 'valid', K = (0.01, 0.03)) and is held to a float64 restatement
-(tests/eval_restate.py) -- PARITY with the package itself is UNPINNED, as for the MS-SSIM term (lara_amd/loss.py).  LPIPS needs
-pretrained networks that are not available here: it is NOT computed; ``Evaluator`` takes optional callables and writes null
-otherwise.  Writing the jpg strip and the mp4 (cv2 / imageio) is left to the caller.  No CPU path: tensors must live on the GPU.
+(tests/eval_restate.py) -- PARITY with the package itself is UNPINNED, as for the MS-SSIM term (lara_amd/loss.py).  LPIPS
+(evaluation.py:48-49, :89-90) runs on the device through `lara_amd.lpips` when ``Evaluator`` is given ``lara_amd.lpips.LPIPS``
+instances (the pretrained weights are the caller's to load; parity with the `lpips` package is unpinned too); it also takes any
+other callables, and writes null without either.  Writing the jpg strip and the mp4 (cv2 / imageio) is left to the caller.  No
+CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -145,7 +147,7 @@ def scene_scores(batch, output, n_views, novel_view_only=True, eval_depth=(), pr
     them (the reference scores scene 0 of a batch of one; here every scene gets its row).  ``n_views``: the input views
     the "novel views only" crop drops (``cfg.n_views``); if it leaves no columns there are no image scores (:83: psnr and
     ssim are None).  ``eval_depth``: the thresholds (``cfg.infer.eval_depth``; empty = no depth scores, :97).  One kernel
-    pass, one device-to-host copy.  SSIM parity with `pytorch_msssim` is unpinned; LPIPS is not computed (module docstring)."""
+    pass, one device-to-host copy.  SSIM parity with `pytorch_msssim` is unpinned; LPIPS is `lara_amd.lpips.scene_lpips`'s."""
     eval_depth = list(eval_depth)
     image, tar = output[f"image{prex}"], batch["tar_rgb"]
     V = tar.shape[1]
@@ -342,9 +344,10 @@ def render_turntable(renderer, gs_params, cams, chunk=8, bg=None):
 
 class Evaluator:
     """Accumulates scenes as the lists of evaluation.py:51-52 and writes the JSON of :164-176 (same keys, same means).
-    ``lpips``: optional callables {'vgg': f, 'alex': f} with f(img_gt * 2 - 1, images * 2 - 1) -> scalar on [1, 3, H, W']
-    tensors (:89-90); without them the LPIPS entries are written as null -- LPIPS is not computed by this package.  SSIM parity
-    with `pytorch_msssim` is unpinned (module docstring)."""
+    ``lpips``: optional {'vgg': f, 'alex': f}.  A `lara_amd.lpips.LPIPS` instance scores the whole batch where the tensors lie
+    (`lara_amd.lpips.scene_lpips`: no permuted copies, one host read per batch for all such networks); any other callable is used
+    as f(img_gt * 2 - 1, images * 2 - 1) -> scalar on [1, 3, H, W'] tensors (:89-90); without them the LPIPS entries are written
+    as null.  SSIM parity with `pytorch_msssim` and LPIPS parity with `lpips` are unpinned (module docstrings)."""
 
     def __init__(self, n_views, novel_view_only=True, eval_depth=(), lpips=None, prex="_fine"):
         self.n_views, self.novel_view_only, self.eval_depth, self.prex = int(n_views), bool(novel_view_only), list(eval_depth), prex
@@ -370,13 +373,20 @@ class Evaluator:
         if names is None:
             names = [str(s).split(".")[0] for s in batch["meta"]["scene"]]            # evaluation.py:63
         skip = self.n_views if self.novel_view_only else 0
+        from .lpips import LPIPS, scene_lpips
+        ours = {k: f for k, f in self.lpips.items() if isinstance(f, LPIPS)}
+        theirs = {k: f for k, f in self.lpips.items() if k not in ours}
+        with_image = bool(scores) and scores[0]["psnr"] is not None
+        on_device = scene_lpips(ours, output[f"image{self.prex}"], batch["tar_rgb"], skip) if ours and with_image else None
         for b, (name, s) in enumerate(zip(names, scores)):
             lp = {}
-            if s["psnr"] is not None and self.lpips:
+            if s["psnr"] is not None and theirs:
                 W = batch["tar_rgb"].shape[3]
                 img = output[f"image{self.prex}"][b].permute(2, 0, 1)[None][..., W * skip:]
                 gt = batch["tar_rgb"][b].permute(1, 0, 2, 3).reshape(output[f"image{self.prex}"][b].shape).permute(2, 0, 1)[None][..., W * skip:]
-                lp = {k: float(f(gt * 2 - 1, img * 2 - 1)) for k, f in self.lpips.items()}
+                lp = {k: float(f(gt * 2 - 1, img * 2 - 1)) for k, f in theirs.items()}
+            if on_device is not None:
+                lp.update(on_device[b])
             self.add_scores(name, s["psnr"], s["ssim"], s["depth_acc"], lp.get("vgg"), lp.get("alex"))
         return scores
 
