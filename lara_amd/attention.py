@@ -13,27 +13,10 @@ require grad raises (no silent fallback to torch).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        lib.lara_groupattn_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_groupattn_workspace_bytes.argtypes = [i32]
-        lib.lara_groupattn_forward.restype = ctypes.c_int
-        lib.lara_groupattn_forward.argtypes = [i32, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
+from ._native import call, query, require_device
 
 
 class GroupCrossAttention(nn.Module):
@@ -70,23 +53,16 @@ class GroupCrossAttention(nn.Module):
     def forward(self, patches: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
         if patches.requires_grad or cond.requires_grad:
             raise RuntimeError("lara_amd.GroupCrossAttention is forward-only in this round")
-        if not patches.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(patches)
         G = patches.shape[0]
         if patches.shape[1:] != (8, self.embed_dim) or cond.shape != (G, 4, self.cond_dim):
             raise RuntimeError("expected patches [G,8,256] and cond [G,4,cond_dim]")
-        lib = _lib()
         x = patches.float().contiguous()
         cond_bf16 = cond.to(torch.bfloat16).contiguous()
         y = torch.empty_like(x)
-        need = lib.lara_groupattn_workspace_bytes(G)
+        need = query("lara_groupattn_workspace_bytes", G)
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.lara_groupattn_forward(
-                G, self.cond_dim, x.data_ptr(), cond_bf16.data_ptr(), self.ln_weight.data_ptr(),
-                self.ln_bias.data_ptr(), float(self.eps), self.wq.data_ptr(), self.wkv.data_ptr(),
-                self.wo.data_ptr(), y.data_ptr(), self._ws.data_ptr(),
-                torch.cuda.current_stream(x.device).cuda_stream)
-        _check(rc, "lara_groupattn_forward")
+        call("lara_groupattn_forward", x.device, G, self.cond_dim, x, cond_bf16, self.ln_weight, self.ln_bias, float(self.eps),
+             self.wq, self.wkv, self.wo, y, self._ws)
         return y

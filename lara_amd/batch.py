@@ -9,25 +9,11 @@ this environment), aligned to the first view exactly as the loader does (gobjver
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        lib.lara_build_rays_out.restype = ctypes.c_int
-        lib.lara_build_rays_out.argtypes = [i32, i32, i32, ctypes.c_float, vp, vp, vp, vp]
-        _configured = True
-    return lib
+from ._native import call, require_device
 
 
 def fov_to_ixt(fov: torch.Tensor, reso) -> torch.Tensor:
@@ -44,8 +30,7 @@ def build_rays(c2ws: torch.Tensor, ixts: torch.Tensor, H: int, W: int, scale: fl
     """``build_rays`` of dataLoader/utils.py:21-34 on the device: c2ws [V,4,4], ixts [V,3,3] ->
     rays [V, int(H*scale), int(W*scale), 6] (origin, unnormalised direction), fp32.  ``ixts`` is
     not modified (the reference scales it in place; its callers pass copies)."""
-    if not c2ws.is_cuda:
-        raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+    require_device(c2ws)
     V = c2ws.shape[0]
     if c2ws.shape != (V, 4, 4) or ixts.shape != (V, 3, 3):
         raise RuntimeError("expected c2ws [V,4,4] and ixts [V,3,3]")
@@ -53,11 +38,8 @@ def build_rays(c2ws: torch.Tensor, ixts: torch.Tensor, H: int, W: int, scale: fl
     k = ixts.detach().float().contiguous().to(c.device)
     Hs, Ws = int(H * scale), int(W * scale)
     rays = torch.empty(V, Hs, Ws, 6, dtype=torch.float32, device=c.device)
-    with torch.cuda.device(c.device):
-        # the output size is computed once, here, as the reference does (double precision), and handed over
-        rc = _lib().lara_build_rays_out(V, Hs, Ws, float(scale), c.data_ptr(), k.data_ptr(), rays.data_ptr(),
-                                    torch.cuda.current_stream(c.device).cuda_stream)
-    _check(rc, "lara_build_rays_out")
+    # the output size is computed once, here, as the reference does (double precision), and handed over
+    call("lara_build_rays_out", c.device, V, Hs, Ws, float(scale), c, k, rays)
     return rays
 
 

@@ -10,45 +10,18 @@ autocast the reference trains with (train_lightning.py:74).  Opt-in; no CPU path
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
-from .rasterizer import _check, load_library
+from ._native import call, query, require_device
 
-_configured = False
 _F, _FA, _O = 80, 88, 48
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        lib.lara_coarse_decoder_padded_rows.restype = i64
-        lib.lara_coarse_decoder_padded_rows.argtypes = [i64]
-        lib.lara_coarse_decoder_forward.restype = ctypes.c_int
-        lib.lara_coarse_decoder_forward.argtypes = [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp] * 6
-        lib.lara_coarse_decoder_backward.restype = ctypes.c_int
-        lib.lara_coarse_decoder_backward.argtypes = [i32, i32, i32] + [vp] * 20
-        lib.lara_gemm_tn_workspace_bytes.restype = i64
-        lib.lara_gemm_tn_workspace_bytes.argtypes = []
-        lib.lara_gemm_tn_bf16.restype = ctypes.c_int
-        lib.lara_gemm_tn_bf16.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class _CoarseDecoder(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w3, b3, K, sh_dim, opacity_shift, scaling_shift):
-        if not x.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(x)
         f = lambda t: t.detach().float().contiguous()
         x, w1, b1, w2, b2, w3, b3 = map(f, (x, w1, b1, w2, b2, w3, b3))
         M, n_par = x.shape[0], K * (10 + sh_dim)
@@ -57,12 +30,8 @@ class _CoarseDecoder(torch.autograd.Function):
             raise RuntimeError("expected x [M,80], Linear(80,80), Linear(80,80), Linear(80, K*(10+sh_dim) <= 48)")
         new = lambda c: torch.empty(M, K * c, dtype=torch.float32, device=x.device)
         offset, sh, scaling, rotation, opacity = new(3), new(sh_dim), new(2), new(4), new(1)
-        with torch.cuda.device(x.device):
-            _check(_lib().lara_coarse_decoder_forward(M, K, sh_dim, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                                      b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), float(opacity_shift),
-                                                      float(scaling_shift), offset.data_ptr(), sh.data_ptr(), scaling.data_ptr(),
-                                                      rotation.data_ptr(), opacity.data_ptr(),
-                                                      torch.cuda.current_stream(x.device).cuda_stream), "lara_coarse_decoder_forward")
+        call("lara_coarse_decoder_forward", x.device, M, K, sh_dim, x, w1, b1, w2, b2, w3, b3, float(opacity_shift),
+             float(scaling_shift), offset, sh, scaling, rotation, opacity)
         ctx.save_for_backward(x, w1, b1, w2, b2, w3, offset)
         ctx.dims = (M, K, sh_dim, n_par)
         ctx.set_materialize_grads(False)
@@ -72,10 +41,9 @@ class _CoarseDecoder(torch.autograd.Function):
     def backward(ctx, g_offset, g_sh, g_scaling, g_rotation, g_opacity):
         x, w1, b1, w2, b2, w3, offset = ctx.saved_tensors
         M, K, sh_dim, n_par = ctx.dims
-        lib = _lib()
         gs = [None if g is None else g.float().contiguous() for g in (g_offset, g_sh, g_scaling, g_rotation, g_opacity)]
         dev = x.device
-        Mp = int(lib.lara_coarse_decoder_padded_rows(M))
+        Mp = query("lara_coarse_decoder_padded_rows", M)
         dx = torch.empty_like(x)
         # the factor matrices of the parameter gradients (bf16): one allocation, carved
         cols = (_FA, _FA, _FA, _F, _F, _O)
@@ -87,17 +55,11 @@ class _CoarseDecoder(torch.autograd.Function):
         xb, h1, h2, dz1, dz2, dz3 = mats
         grads = torch.zeros((2 * _F + _O) * _FA, dtype=torch.float32, device=dev)     # [dW | db | 0] of the three layers
         g1, g2, g3 = grads[:_F * _FA].view(_F, _FA), grads[_F * _FA:2 * _F * _FA].view(_F, _FA), grads[2 * _F * _FA:].view(_O, _FA)
-        ws = torch.empty(int(lib.lara_gemm_tn_workspace_bytes()), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.lara_coarse_decoder_backward(M, K, sh_dim, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                                    b2.data_ptr(), w3.data_ptr(), offset.data_ptr(), *[_ptr(g) for g in gs],
-                                                    dx.data_ptr(), xb.data_ptr(), h1.data_ptr(), h2.data_ptr(), dz1.data_ptr(),
-                                                    dz2.data_ptr(), dz3.data_ptr(), s), "lara_coarse_decoder_backward")
-            if M:
-                for dz, act, g in ((dz1, xb, g1), (dz2, h1, g2), (dz3, h2, g3)):      # G += dz^T [act | 1 | 0]
-                    _check(lib.lara_gemm_tn_bf16(Mp, dz.shape[1], _FA, dz.data_ptr(), act.data_ptr(), g.data_ptr(), ws.data_ptr(), s),
-                           "lara_gemm_tn_bf16")
+        ws = torch.empty(query("lara_gemm_tn_workspace_bytes"), dtype=torch.uint8, device=dev)
+        call("lara_coarse_decoder_backward", dev, M, K, sh_dim, x, w1, b1, w2, b2, w3, offset, *gs, dx, xb, h1, h2, dz1, dz2, dz3)
+        if M:
+            for dz, act, g in ((dz1, xb, g1), (dz2, h1, g2), (dz3, h2, g3)):      # G += dz^T [act | 1 | 0]
+                call("lara_gemm_tn_bf16", dev, Mp, dz.shape[1], _FA, dz, act, g, ws)
         return (dx, g1[:, :_F], g1[:, _F], g2[:, :_F], g2[:, _F], g3[:n_par, :_F], g3[:n_par, _F], None, None, None, None)
 
 

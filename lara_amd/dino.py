@@ -15,41 +15,16 @@ There is no CPU path and no torch fallback: tensors must live on the GPU and the
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .rasterizer import _alloc_bytes, _check, load_library
+from ._native import VitDims as _Dims, alloc_bytes, call, host_array, query, require_device
+from ._native import load_library as _lib  # noqa: F401  (the shared loader; this name was imported from here)
 
 PATCH, HEAD_DIM, MAX_C, MAX_F, MAX_T = 16, 64, 1024, 4096, 16384
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-
-_configured = False
-
-
-class _Dims(ctypes.Structure):   # lara_vit_dims
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "views", "H", "W", "C", "heads", "F", "depth")] + \
-               [("eps", ctypes.c_float), ("img_stride", ctypes.c_int64 * 5)]
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, pd = ctypes.c_void_p, ctypes.POINTER(_Dims)
-        lib.lara_vit_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_vit_workspace_bytes.argtypes = [pd, ctypes.c_int32]
-        lib.lara_vit_save_bytes.restype = ctypes.c_int64
-        lib.lara_vit_save_bytes.argtypes = [pd]
-        lib.lara_vit_forward.restype = ctypes.c_int
-        lib.lara_vit_forward.argtypes = [pd, vp, vp, vp, vp, vp, vp]
-        lib.lara_vit_backward.restype = ctypes.c_int
-        lib.lara_vit_backward.argtypes = [pd, vp, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
 
 
 def resample_pos_embed(pos_embed: torch.Tensor, new_size: tuple, old_size: tuple = None, num_prefix_tokens: int = 1) -> torch.Tensor:
@@ -143,43 +118,30 @@ def _dims(N, views, H, W, C, heads, F_, depth, eps, strides):
     return d
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 class _Run:
     """One call of the kernels: the dims, the flattened fp32 parameters (lara_vit.h order) and the saved state."""
 
     def __init__(self, d, images, params, dev):
         self.d, self.images, self.params, self.dev = d, images, params, dev
-        self.ptrs = _ptr_array(params)
+        self.ptrs = host_array("p", params)
         self.save = None
 
     def forward(self, training):
-        lib, d = _lib(), self.d
+        d = self.d
         hw = (d.H // PATCH) * (d.W // PATCH)
         out = torch.empty(d.N, hw, d.C, dtype=torch.float32, device=self.dev)
-        n = lib.lara_vit_workspace_bytes(ctypes.byref(d), 1 if training else 0)
-        if n < 0:
-            _check(int(n), "lara_vit_workspace_bytes")
-        ws = _alloc_bytes(int(n), self.dev)
-        self.save = _alloc_bytes(int(lib.lara_vit_save_bytes(ctypes.byref(d))), self.dev) if training else None
-        with torch.cuda.device(self.dev):
-            _check(lib.lara_vit_forward(ctypes.byref(d), self.images.data_ptr(), ctypes.addressof(self.ptrs), out.data_ptr(),
-                                        None if self.save is None else self.save.data_ptr(), ws.data_ptr(),
-                                        torch.cuda.current_stream(self.dev).cuda_stream), "lara_vit_forward")
+        ws = alloc_bytes(query("lara_vit_workspace_bytes", d, 1 if training else 0), self.dev)
+        self.save = alloc_bytes(query("lara_vit_save_bytes", d), self.dev) if training else None
+        call("lara_vit_forward", self.dev, d, self.images, self.ptrs, out, self.save, ws)
         return out
 
     def backward(self, grad):
-        lib, d = _lib(), self.d
+        d = self.d
         grad = grad.float().contiguous()
         grads = [torch.empty_like(p) for p in self.params]
-        ws = _alloc_bytes(int(lib.lara_vit_workspace_bytes(ctypes.byref(d), 1)), self.dev)
-        gptrs = _ptr_array(grads)
-        with torch.cuda.device(self.dev):
-            _check(lib.lara_vit_backward(ctypes.byref(d), ctypes.addressof(self.ptrs), self.save.data_ptr(), grad.data_ptr(),
-                                         ctypes.addressof(gptrs), ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream),
-                   "lara_vit_backward")
+        ws = alloc_bytes(query("lara_vit_workspace_bytes", d, 1), self.dev)
+        gptrs = host_array("p", grads)
+        call("lara_vit_backward", self.dev, d, self.ptrs, self.save, grad, gptrs, ws)
         return grads
 
 
@@ -263,8 +225,7 @@ class DinoViT(nn.Module):
 
     def _run(self, images, N, views, H, W, strides):
         self.check_size(H, W)
-        if not images.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(images)
         if images.dtype != torch.float32:
             raise ValueError(f"lara_amd.dino: images must be fp32; got {images.dtype}")
         params = self._params(H // PATCH, W // PATCH)

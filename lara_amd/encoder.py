@@ -17,43 +17,14 @@ through ``lara_amd.encoder_train`` (same kernels + the HIP backward, fp32 master
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-class _BlockWeights(ctypes.Structure):  # struct lara_groupblock_weights, include/lara_groupattn.h
-    _fields_ = [(n, ctypes.c_void_p) for n in
-                ("ln1_w", "ln1_b", "wq", "wkv", "wo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2",
-                 "ln3_w", "ln3_b", "wconv")] + [("eps", ctypes.c_float)]
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-        lib.lara_groupblock_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_groupblock_workspace_bytes.argtypes = [i32, i32]
-        lib.lara_groupblock_forward.restype = ctypes.c_int
-        lib.lara_groupblock_forward.argtypes = [i32, i32, i32, vp, vp, ctypes.POINTER(_BlockWeights), vp, vp]
-        lib.lara_voltrans_head_forward.restype = ctypes.c_int
-        lib.lara_voltrans_head_forward.argtypes = [i32, i32, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp]
-        for fn in (lib.lara_tokens_from_volume, lib.lara_volume_from_tokens):
-            fn.restype = ctypes.c_int
-            fn.argtypes = [i32, i32, i32, vp, vp, vp]
-        _configured = True
-    return lib
+from ._native import BlockWeights as _BlockWeights, call, query, require_device
 
 
 def _require_device(t: torch.Tensor):
-    if not t.is_cuda:
-        raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+    require_device(t)
     if t.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("lara_amd.encoder holds the inference classes; use lara_amd.encoder_train.VolTransformer to train")
 
@@ -64,9 +35,7 @@ def volume_to_tokens(volume: torch.Tensor) -> torch.Tensor:
     B, C, R = volume.shape[0], volume.shape[1], volume.shape[2]
     v = volume.float().contiguous()
     out = torch.empty(B * R ** 3, C, dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        _check(_lib().lara_tokens_from_volume(B, R, C, v.data_ptr(), out.data_ptr(),
-                                              torch.cuda.current_stream(v.device).cuda_stream), "lara_tokens_from_volume")
+    call("lara_tokens_from_volume", v.device, B, R, C, v, out)
     return out
 
 
@@ -75,9 +44,7 @@ def tokens_to_volume(tokens: torch.Tensor, B: int, R: int) -> torch.Tensor:
     C = tokens.shape[1]
     t = tokens.float().contiguous()
     out = torch.empty(B, C, R, R, R, dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _check(_lib().lara_volume_from_tokens(B, R, C, t.data_ptr(), out.data_ptr(),
-                                              torch.cuda.current_stream(t.device).cuda_stream), "lara_volume_from_tokens")
+    call("lara_volume_from_tokens", t.device, B, R, C, t, out)
     return out
 
 
@@ -149,16 +116,10 @@ class GroupAttBlock(nn.Module):
             raise RuntimeError("expected contiguous fp32 token rows [scenes * R^3, 256]")
         if cond_bf16.dtype != torch.bfloat16 or cond_bf16.shape != (scenes * (R // 2) ** 3, 4, self.cond_dim):
             raise RuntimeError("expected bf16 cond [scenes * (R/2)^3, 4, cond_dim]")
-        lib = _lib()
-        need = lib.lara_groupblock_workspace_bytes(scenes, R)
+        need = query("lara_groupblock_workspace_bytes", scenes, R)
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        w = self._weights()
-        with torch.cuda.device(x.device):
-            rc = lib.lara_groupblock_forward(scenes, R, self.cond_dim, x.data_ptr(), cond_bf16.contiguous().data_ptr(),
-                                             ctypes.byref(w), self._ws.data_ptr(),
-                                             torch.cuda.current_stream(x.device).cuda_stream)
-        _check(rc, "lara_groupblock_forward")
+        call("lara_groupblock_forward", x.device, scenes, R, self.cond_dim, x, cond_bf16.contiguous(), self._weights(), self._ws)
         return x
 
     def forward(self, x: torch.Tensor, cond: torch.Tensor, group_axis: int, block_size: int) -> torch.Tensor:
@@ -213,12 +174,8 @@ class VolTransformer(nn.Module):
         x.view(B, -1, self.embed_dim).copy_(self._pos_tokens)  # network.py:152: the same positional volume per scene
         for layer in self.layers:
             layer.forward_tokens(x, cond, B, R)
-        with torch.cuda.device(dev):
-            rc = _lib().lara_voltrans_head_forward(B, R, x.data_ptr(), self.norm_w.data_ptr(), self.norm_b.data_ptr(),
-                                                   float(self.eps), self.wdeconv.data_ptr(), self.deconv_b.data_ptr(),
-                                                   self.out_dim, out.data_ptr(), self._ws.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream)
-        _check(rc, "lara_voltrans_head_forward")
+        call("lara_voltrans_head_forward", dev, B, R, x, self.norm_w, self.norm_b, float(self.eps), self.wdeconv, self.deconv_b,
+             self.out_dim, out, self._ws)
 
     def forward(self, image_feats: torch.Tensor, use_graph: bool = False) -> torch.Tensor:
         """``use_graph``: replay the ~125 launches of a forward as ONE HIP graph (captured on first use per

@@ -15,64 +15,17 @@ There is no CPU path and no torch fallback: tensors must live on the GPU and the
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 from torch import nn
 
-from .encoder import _BlockWeights, _lib as _fwd_lib, tokens_to_volume, volume_to_tokens
-from .rasterizer import _check
-
-_configured = False
-
-
-class _BlockWeightsT(ctypes.Structure):  # struct lara_groupblock_weights_t
-    _fields_ = [(n, ctypes.c_void_p) for n in ("wq_t", "wkv_t", "wo_t", "w1_t", "w2_t", "wconv_t")]
-
+from ._native import (BlockGrads as _BlockGrads, BlockWeights as _BlockWeights, BlockWeightsT as _BlockWeightsT, call, query,
+                      require_device)
+from ._native import current_stream as _stream, load_library as _lib  # noqa: F401  (the shared ones; imported from here before)
+from .encoder import tokens_to_volume, volume_to_tokens
 
 _GRAD_FIELDS = ("ln1_w", "ln1_b", "wq", "wkv", "wo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2", "ln3_w", "ln3_b", "wconv")
-
-
-class _BlockGrads(ctypes.Structure):  # struct lara_groupblock_grads
-    _fields_ = [(n, ctypes.c_void_p) for n in _GRAD_FIELDS]
-
-
-def _lib():
-    global _configured
-    lib = _fwd_lib()
-    if not _configured:
-        vp, i32, f32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int64
-        lib.lara_groupblock_backward_workspace_bytes.restype = i64
-        lib.lara_groupblock_backward_workspace_bytes.argtypes = [i32, i32]
-        lib.lara_groupblock_backward.restype = ctypes.c_int
-        lib.lara_groupblock_backward.argtypes = [i32, i32, i32, vp, vp, ctypes.POINTER(_BlockWeights),
-                                                 ctypes.POINTER(_BlockWeightsT), vp, vp, vp, ctypes.POINTER(_BlockGrads), i32,
-                                                 vp, i32, vp, vp]
-        lib.lara_gemm_nt_bf16.restype = ctypes.c_int
-        lib.lara_gemm_nt_bf16.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp]
-        lib.lara_batched_transpose.restype = ctypes.c_int
-        lib.lara_batched_transpose.argtypes = [i32, i32, i32, vp, vp, i32, vp]
-        lib.lara_groupblock_save_bytes.restype = i64
-        lib.lara_groupblock_save_bytes.argtypes = [i32, i32]
-        lib.lara_groupblock_save_offsets.restype = ctypes.c_int
-        lib.lara_groupblock_save_offsets.argtypes = [i32, i32, ctypes.POINTER(i64), i32]
-        lib.lara_groupblock_forward_train.restype = ctypes.c_int
-        lib.lara_groupblock_forward_train.argtypes = [i32, i32, i32, vp, vp, vp, ctypes.POINTER(_BlockWeights), vp, vp]
-        lib.lara_voltrans_head_backward_workspace_bytes.restype = i64
-        lib.lara_voltrans_head_backward_workspace_bytes.argtypes = [i32, i32, i32]
-        lib.lara_voltrans_head_backward.restype = ctypes.c_int
-        lib.lara_voltrans_head_backward.argtypes = [i32, i32, vp, vp, vp, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.lara_gemm_tn_workspace_bytes.restype = i64
-        lib.lara_gemm_tn_workspace_bytes.argtypes = []
-        lib.lara_gemm_tn_bf16.restype = ctypes.c_int
-        lib.lara_gemm_tn_bf16.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
-        lib.lara_layernorm256_backward.restype = ctypes.c_int
-        lib.lara_layernorm256_backward.argtypes = [i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
-        lib.lara_groupattn_core_backward.restype = ctypes.c_int
-        lib.lara_groupattn_core_backward.argtypes = [i32, vp, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
 
 
 def _keep_activations() -> bool:
@@ -83,16 +36,10 @@ def _keep_activations() -> bool:
     return os.environ.get("LARA_ENCODER_RECOMPUTE", "0") != "1"
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 _scratch = {}   # (device index, tag) -> uint8 tensor, grown on demand
 
 
 def _workspace(dev, tag: str, nbytes: int) -> torch.Tensor:
-    if nbytes < 0:
-        _check(int(nbytes), f"workspace size query ({tag})")
     key = (dev.index, tag)
     t = _scratch.get(key)
     if t is None or t.numel() < nbytes:
@@ -168,9 +115,7 @@ def _forward_inference(image_feats, eps_block, eps_final, R, out_dim, pos_embed,
     (image_feats [B, V = 4, C, D, H, W], ..., 15 tensors per layer ...) -> [B, 2R, 2R, 2R, out_dim].  (Round 2's single autograd
     node for the whole transformer lived here; its backward is the per-block nodes below since round 3 and was removed in
     round 5.)"""
-    if not image_feats.is_cuda:
-        raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
-    lib = _lib()
+    require_device(image_feats)
     dev = image_feats.device
     B, V, cond_dim = image_feats.shape[:3]
     S = image_feats.shape[3] * image_feats.shape[4] * image_feats.shape[5]
@@ -178,9 +123,7 @@ def _forward_inference(image_feats, eps_block, eps_final, R, out_dim, pos_embed,
     # [v c, d h w] matrix transposed
     feats = image_feats.detach().float().contiguous()
     cond_bf = torch.empty(B * S, V, cond_dim, dtype=torch.bfloat16, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.lara_batched_transpose(B, V * cond_dim, S, feats.data_ptr(), cond_bf.data_ptr(), 1, _stream(dev)),
-               "lara_batched_transpose")
+    call("lara_batched_transpose", dev, B, V * cond_dim, S, feats, cond_bf, 1)
     return _inference_from_cond(cond_bf, B, cond_dim, eps_block, eps_final, R, out_dim, pos_embed, norm_w, norm_b, deconv_w, deconv_b,
                                 *layer_params)
 
@@ -188,26 +131,22 @@ def _forward_inference(image_feats, eps_block, eps_final, R, out_dim, pos_embed,
 def _inference_from_cond(cond_bf, B, cond_dim, eps_block, eps_final, R, out_dim, pos_embed, norm_w, norm_b, deconv_w, deconv_b,
                          *layer_params):
     """`_forward_inference` from the bf16 operand [B R^3, V, cond_dim] on."""
-    lib = _lib()
     dev = cond_bf.device
     n_layers = len(layer_params) // _NLP
     M = B * R ** 3
     x = volume_to_tokens(pos_embed.detach().float()).repeat(B, 1)       # network.py:152
-    ws = _workspace(dev, "fwd", lib.lara_groupblock_workspace_bytes(B, R))
+    ws = _workspace(dev, "fwd", query("lara_groupblock_workspace_bytes", B, R))
     with torch.cuda.device(dev):
         for l in range(n_layers):
             f = _layer_bf16([t.detach() for t in layer_params[l * _NLP:(l + 1) * _NLP]])
             w = _fill(_BlockWeights(), f, _GRAD_FIELDS)
             w.eps = eps_block
-            _check(lib.lara_groupblock_forward(B, R, cond_dim, x.data_ptr(), cond_bf.data_ptr(), ctypes.byref(w),
-                                               ws.data_ptr(), _stream(dev)), "lara_groupblock_forward")
+            call("lara_groupblock_forward", dev, B, R, cond_dim, x, cond_bf, w, ws)
         wd = deconv_w.detach().permute(2, 3, 4, 1, 0).reshape(8 * out_dim, 256).to(torch.bfloat16).contiguous()
         nw, nb, db = norm_w.detach().float().contiguous(), norm_b.detach().float().contiguous(), deconv_b.detach().float().contiguous()
         out = torch.empty(B, 2 * R, 2 * R, 2 * R, out_dim, dtype=torch.float32, device=dev)
         hws = _workspace(dev, "head", M * 512)
-        _check(lib.lara_voltrans_head_forward(B, R, x.data_ptr(), nw.data_ptr(), nb.data_ptr(), float(eps_final),
-                                              wd.data_ptr(), db.data_ptr(), out_dim, out.data_ptr(), hws.data_ptr(),
-                                              _stream(dev)), "lara_voltrans_head_forward")
+        call("lara_voltrans_head_forward", dev, B, R, x, nw, nb, float(eps_final), wd, db, out_dim, out, hws)
     return out
 
 
@@ -256,22 +195,19 @@ class _Sweep:
 class _CondFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image_feats, sweep):
-        lib = _lib()
         dev = image_feats.device
         B, V, C = image_feats.shape[:3]
         S = image_feats.shape[3] * image_feats.shape[4] * image_feats.shape[5]
         feats = image_feats.detach().float().contiguous()
         cond_bf = torch.empty(B * S, V, C, dtype=torch.bfloat16, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.lara_batched_transpose(B, V * C, S, feats.data_ptr(), cond_bf.data_ptr(), 1, _stream(dev)),
-                   "lara_batched_transpose")
+        call("lara_batched_transpose", dev, B, V * C, S, feats, cond_bf, 1)
         sweep.cond_bf = cond_bf
         ctx.sweep, ctx.feat_shape, ctx.feat_dtype = sweep, tuple(image_feats.shape), image_feats.dtype
         return torch.zeros(1, dtype=torch.float32, device=dev)
 
     @staticmethod
     def backward(ctx, g_token):
-        lib, sw = _lib(), ctx.sweep
+        sw = ctx.sweep
         if not ctx.needs_input_grad[0]:
             return None, None
         dev = sw.dev
@@ -280,13 +216,11 @@ class _CondFn(torch.autograd.Function):
         lddkv = sw.n_layers * 512
         with torch.cuda.device(dev):
             wkv_all_t = torch.cat([f["wkv"] for f in sw.fs], 0).t().contiguous()
-            _check(lib.lara_gemm_nt_bf16(sw.dkv_all.shape[0], sw.cond_dim, lddkv, sw.dkv_all.data_ptr(), wkv_all_t.data_ptr(),
-                                         dcond.data_ptr(), 1, _stream(dev)), "lara_gemm_nt_bf16")
+            call("lara_gemm_nt_bf16", dev, sw.dkv_all.shape[0], sw.cond_dim, lddkv, sw.dkv_all, wkv_all_t, dcond, 1)
             Bf, V, C = ctx.feat_shape[:3]
             S = dcond.shape[0] // Bf
             d_feats = torch.empty(ctx.feat_shape, dtype=torch.float32, device=dev)
-            _check(lib.lara_batched_transpose(Bf, S, V * C, dcond.data_ptr(), d_feats.data_ptr(), 0, _stream(dev)),
-                   "lara_batched_transpose")
+            call("lara_batched_transpose", dev, Bf, S, V * C, dcond, d_feats, 0)
         sw.dkv_all = sw.flat = None
         return (d_feats if ctx.feat_dtype == torch.float32 else d_feats.to(ctx.feat_dtype)), None
 
@@ -307,7 +241,7 @@ class _FeatCondFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_token):
         from .featvol import TOKENS
-        lib, sw = _lib(), ctx.sweep
+        sw = ctx.sweep
         if not any(ctx.needs_input_grad[:6]):
             return (None,) * 8
         dev = sw.dev
@@ -315,8 +249,7 @@ class _FeatCondFn(torch.autograd.Function):
         lddkv = sw.n_layers * 512
         with torch.cuda.device(dev):
             wkv_all_t = torch.cat([f["wkv"] for f in sw.fs], 0).t().contiguous()
-            _check(lib.lara_gemm_nt_bf16(sw.dkv_all.shape[0], sw.cond_dim, lddkv, sw.dkv_all.data_ptr(), wkv_all_t.data_ptr(),
-                                         dcond.data_ptr(), 1, _stream(dev)), "lara_gemm_nt_bf16")
+            call("lara_gemm_nt_bf16", dev, sw.dkv_all.shape[0], sw.cond_dim, lddkv, sw.dkv_all, wkv_all_t, dcond, 1)
         sw.dkv_all = sw.flat = None
         dx, d_lnw, d_lnb, d_w, d_b, d_e = ctx.prep.backward(dcond, TOKENS, ctx.needs_input_grad[5])
         return dx, d_lnw, d_lnb, d_w, d_b, d_e, None, None
@@ -337,7 +270,7 @@ class _StartFn(torch.autograd.Function):
 class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sweep, l, *p):
-        lib, sw = _lib(), sweep
+        sw = sweep
         dev = x.device
         f = sw.fs[l] = _layer_bf16([t.detach() for t in p])
         w = _fill(_BlockWeights(), f, _GRAD_FIELDS)
@@ -345,27 +278,21 @@ class _BlockFn(torch.autograd.Function):
         keep = _keep_activations()
         with torch.cuda.device(dev):
             if keep:
-                nsave = lib.lara_groupblock_save_bytes(sw.B, sw.R)
-                if nsave < 0:
-                    _check(int(nsave), "lara_groupblock_save_bytes")
-                act = torch.empty(nsave, dtype=torch.uint8, device=dev)
+                act = torch.empty(query("lara_groupblock_save_bytes", sw.B, sw.R), dtype=torch.uint8, device=dev)
                 x_out = torch.empty_like(x)
-                _check(lib.lara_groupblock_forward_train(sw.B, sw.R, sw.cond_dim, x.data_ptr(), x_out.data_ptr(), sw.cond_bf.data_ptr(),
-                                                         ctypes.byref(w), act.data_ptr(), _stream(dev)),
-                       "lara_groupblock_forward_train")
+                call("lara_groupblock_forward_train", dev, sw.B, sw.R, sw.cond_dim, x, x_out, sw.cond_bf, w, act)
             else:
                 act = None
                 x_out = x.clone()
-                ws = _workspace(dev, "fwd", lib.lara_groupblock_workspace_bytes(sw.B, sw.R))
-                _check(lib.lara_groupblock_forward(sw.B, sw.R, sw.cond_dim, x_out.data_ptr(), sw.cond_bf.data_ptr(), ctypes.byref(w),
-                                                   ws.data_ptr(), _stream(dev)), "lara_groupblock_forward")
+                ws = _workspace(dev, "fwd", query("lara_groupblock_workspace_bytes", sw.B, sw.R))
+                call("lara_groupblock_forward", dev, sw.B, sw.R, sw.cond_dim, x_out, sw.cond_bf, w, ws)
         ctx.save_for_backward(x)
         ctx.sweep, ctx.l, ctx.act = sw, l, act
         return x_out
 
     @staticmethod
     def backward(ctx, g):
-        lib, sw, l = _lib(), ctx.sweep, ctx.l
+        sw, l = ctx.sweep, ctx.l
         (x_in,) = ctx.saved_tensors
         dev = sw.dev
         f = sw.fs[l]
@@ -388,13 +315,11 @@ class _BlockFn(torch.autograd.Function):
         # `chained`: the workspace still holds what block l + 1 of THIS sweep left (the bf16 copy of g, the neighbour table)
         chained = int(_ws_owner.get(dev.index) == (id(sw), l + 1))
         with torch.cuda.device(dev):
-            ws = _workspace(dev, "block_bwd", lib.lara_groupblock_backward_workspace_bytes(sw.B, sw.R))
+            ws = _workspace(dev, "block_bwd", query("lara_groupblock_backward_workspace_bytes", sw.B, sw.R))
             if _block_bwd_log is not None:
                 _block_bwd_log.append(("block_backward_launch", l))
-            _check(lib.lara_groupblock_backward(sw.B, sw.R, sw.cond_dim, x_in.data_ptr(), sw.cond_bf.data_ptr(), ctypes.byref(w),
-                                                ctypes.byref(wt), None if ctx.act is None else ctx.act.data_ptr(), g.data_ptr(), None,
-                                                ctypes.byref(dw), chained, sw.dkv_all.data_ptr() + l * 1024, lddkv, ws.data_ptr(),
-                                                _stream(dev)), "lara_groupblock_backward")
+            call("lara_groupblock_backward", dev, sw.B, sw.R, sw.cond_dim, x_in, sw.cond_bf, w, wt, ctx.act, g, None, dw, chained,
+                 sw.dkv_all.data_ptr() + l * 1024, lddkv, ws)
         _ws_owner[dev.index] = (id(sw), l)
         ctx.act = None      # released now, not with the graph; a second backward over a retained graph recomputes them (act = NULL)
         return (g, None, None, gd["ln1_w"], gd["ln1_b"], gd["wq"], gd["wkv"][:256], gd["wkv"][256:], gd["wo"], gd["ln2_w"], gd["ln2_b"],
@@ -405,7 +330,7 @@ class _BlockFn(torch.autograd.Function):
 class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, deconv_w, deconv_b, sweep, eps_final, out_dim):
-        lib, sw = _lib(), sweep
+        sw = sweep
         dev = x.device
         M = sw.B * sw.R ** 3
         with torch.cuda.device(dev):
@@ -413,16 +338,14 @@ class _HeadFn(torch.autograd.Function):
             nw, nb, db = norm_w.detach().float().contiguous(), norm_b.detach().float().contiguous(), deconv_b.detach().float().contiguous()
             out = torch.empty(sw.B, 2 * sw.R, 2 * sw.R, 2 * sw.R, out_dim, dtype=torch.float32, device=dev)
             hws = _workspace(dev, "head", M * 512)
-            _check(lib.lara_voltrans_head_forward(sw.B, sw.R, x.data_ptr(), nw.data_ptr(), nb.data_ptr(), float(eps_final),
-                                                  wd.data_ptr(), db.data_ptr(), out_dim, out.data_ptr(), hws.data_ptr(),
-                                                  _stream(dev)), "lara_voltrans_head_forward")
+            call("lara_voltrans_head_forward", dev, sw.B, sw.R, x, nw, nb, float(eps_final), wd, db, out_dim, out, hws)
         ctx.save_for_backward(x, norm_w, norm_b, deconv_w)
         ctx.sweep, ctx.eps_final, ctx.out_dim = sw, float(eps_final), out_dim
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib, sw = _lib(), ctx.sweep
+        sw = ctx.sweep
         x_last, norm_w, norm_b, deconv_w = ctx.saved_tensors
         dev, out_dim = sw.dev, ctx.out_dim
         M = sw.B * sw.R ** 3
@@ -434,11 +357,9 @@ class _HeadFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             wd_t = deconv_w.detach().permute(2, 3, 4, 1, 0).reshape(8 * out_dim, 256).to(torch.bfloat16).t().contiguous()
             nw, nb = norm_w.detach().float().contiguous(), norm_b.detach().float().contiguous()
-            hws = _workspace(dev, "head_bwd", lib.lara_voltrans_head_backward_workspace_bytes(sw.B, sw.R, out_dim))
-            _check(lib.lara_voltrans_head_backward(sw.B, sw.R, x_last.data_ptr(), nw.data_ptr(), nb.data_ptr(), ctx.eps_final,
-                                                   wd_t.data_ptr(), out_dim, dout.data_ptr(), g.data_ptr(), d_nw.data_ptr(),
-                                                   d_nb.data_ptr(), d_wd.data_ptr(), d_b8.data_ptr(), hws.data_ptr(),
-                                                   _stream(dev)), "lara_voltrans_head_backward")
+            hws = _workspace(dev, "head_bwd", query("lara_voltrans_head_backward_workspace_bytes", sw.B, sw.R, out_dim))
+            call("lara_voltrans_head_backward", dev, sw.B, sw.R, x_last, nw, nb, ctx.eps_final, wd_t, out_dim, dout, g, d_nw, d_nb,
+                 d_wd, d_b8, hws)
         _ws_owner.pop(dev.index, None)      # a new sweep starts: block L - 1 is not chained to anything
         # ... and with fresh gradient accumulators: `_CondFn.backward` releases them at the END of a sweep only when the image
         # features want a gradient; a second backward over a retained graph must not add into the first one's sums
@@ -508,8 +429,7 @@ class VolTransformer(nn.Module):
         self.deconv = nn.ConvTranspose3d(embed_dim, out_dim, kernel_size=2, stride=2, padding=0)
 
     def forward(self, image_feats: torch.Tensor) -> torch.Tensor:
-        if not image_feats.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(image_feats)
         B, V, C, D = image_feats.shape[:4]
         if D != self.n_groups[0] or V != 4:
             raise RuntimeError("kernels are specialised for one image-feature voxel per group and 4 input views")

@@ -23,7 +23,6 @@ CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import math
 import os
@@ -31,29 +30,12 @@ import os
 import torch
 
 from . import cameras as _cameras
-from .loss import _ImgView, _window_host
-from .rasterizer import _check, load_library
+from ._native import ImageView as _ImgView, call, host_array, query, require_device
+from ._native import load_library as _lib  # noqa: F401  (the shared loader; this name was imported from here)
+from .loss import _window_host
 
 ROW = 16                   # include/lara_eval.h: LARA_EVAL_ROW
 MAX_THRESHOLDS = 8         # LARA_EVAL_MAX_THRESHOLDS
-_NO_CPU = "lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path"
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.lara_eval_workspace_doubles.restype = i64
-        lib.lara_eval_workspace_doubles.argtypes = [i32] * 6
-        lib.lara_eval_scores.restype = ctypes.c_int
-        lib.lara_eval_scores.argtypes = [i32, i32, i32, ctypes.POINTER(_ImgView), ctypes.POINTER(_ImgView), vp, i32, i32, i32, vp, vp, vp,
-                                         i32, i32, ctypes.POINTER(ctypes.c_double), vp, vp, vp]
-        lib.lara_eval_quantize_frames.restype = ctypes.c_int
-        lib.lara_eval_quantize_frames.argtypes = [i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
 
 
 # ---------------------------------------------------------------------------------------------------------- scores
@@ -91,10 +73,9 @@ def scores_device(image, tar_rgb, skip_views=0, depth_pred=None, tar_dep=None, t
         raise ValueError("lara_amd.evaluate: nothing to score")
     first = image if image is not None else depth_pred
     for t in (image, tar_rgb if image is not None else None, depth_pred, tar_dep, tar_msk):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
+        if t is not None:
+            require_device(t)
     dev = first.device
-    lib = _lib()
     xv = yv = None
     if image is not None:
         image, tar_rgb = image.detach().float().contiguous(), tar_rgb.detach().float().contiguous()
@@ -109,18 +90,13 @@ def scores_device(image, tar_rgb, skip_views=0, depth_pred=None, tar_dep=None, t
         elif tar_msk.dtype not in (torch.uint8, torch.bool):
             tar_msk = (tar_msk != 0).to(torch.uint8)          # `.bool()` of any other type
         tar_msk = tar_msk.contiguous()
-    nws = int(lib.lara_eval_workspace_doubles(B, H, Wc, Vd, Hd, Wd))
-    if nws < 0:
-        raise ValueError("lara_amd.evaluate: sizes out of range for lara_eval_scores")
+    nws = query("lara_eval_workspace_doubles", B, H, Wc, Vd, Hd, Wd,
+                error=ValueError("lara_amd.evaluate: sizes out of range for lara_eval_scores"))
     ws = torch.empty(nws, dtype=torch.float64, device=dev)
     scores = torch.empty(B, ROW, dtype=torch.float64, device=dev)
-    thr = (ctypes.c_double * max(len(thresholds), 1))(*thresholds)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.lara_eval_scores(B, H, Wc, None if xv is None else ctypes.byref(xv), None if yv is None else ctypes.byref(yv),
-                                    ctypes.cast(_window_host(), ctypes.c_void_p), Vd, Hd, Wd, ptr(depth_pred), ptr(tar_dep), ptr(tar_msk),
-                                    msk_bytes, len(thresholds), thr, scores.data_ptr(), ws.data_ptr(),
-                                    torch.cuda.current_stream(dev).cuda_stream), "lara_eval_scores")
+    thr = host_array("d", thresholds or [0.0])
+    call("lara_eval_scores", dev, B, H, Wc, xv, yv, _window_host(), Vd, Hd, Wd, depth_pred, tar_dep, tar_msk, msk_bytes,
+         len(thresholds), thr, scores, ws)
     return scores
 
 
@@ -156,8 +132,7 @@ def scene_scores(batch, output, n_views, novel_view_only=True, eval_depth=(), pr
     depth = len(eval_depth) > 0
     if not with_image and not depth:
         for t in (image, tar):
-            if not t.is_cuda:
-                raise RuntimeError(_NO_CPU)
+            require_device(t)
         return [{"psnr": None, "ssim": None, "depth_acc": None} for _ in range(tar.shape[0])]
     dev_rows = scores_device(image if with_image else None, tar, skip,
                              output[f"depth{prex}"] if depth else None, batch["tar_dep"] if depth else None,
@@ -261,8 +236,7 @@ def quantize_frames(image, rend_normal, acc_map, n=None):
     [H, n*W(, 1)] side by side (pass ``n``), or per view [n, H, W, 3] / [n, H, W(, 1)].  Returns (frames, normal_frames), both
     [n, H, W, 3] uint8: rint(image * 255) and rint((((normal * alpha + 1 - alpha) + 1) / 2) * 255), ties to even, clamped."""
     for t in (image, rend_normal, acc_map):
-        if not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
+        require_device(t)
     image, rend_normal, acc_map = (t.detach().float().contiguous() for t in (image, rend_normal, acc_map))
     if image.dim() == 3:
         if n is None:
@@ -279,10 +253,7 @@ def quantize_frames(image, rend_normal, acc_map, n=None):
         raise ValueError("lara_amd.evaluate: image, rend_normal and acc_map disagree in size")
     frames = torch.empty(n, H, W, 3, dtype=torch.uint8, device=image.device)
     normals = torch.empty_like(frames)
-    with torch.cuda.device(image.device):
-        _check(_lib().lara_eval_quantize_frames(n, H, W, sV, sY, image.data_ptr(), rend_normal.data_ptr(), acc_map.data_ptr(),
-                                                frames.data_ptr(), normals.data_ptr(),
-                                                torch.cuda.current_stream(image.device).cuda_stream), "lara_eval_quantize_frames")
+    call("lara_eval_quantize_frames", image.device, n, H, W, sV, sY, image, rend_normal, acc_map, frames, normals)
     return frames, normals
 
 
@@ -308,8 +279,7 @@ def render_turntable(renderer, gs_params, cams, chunk=8, bg=None):
         opacity, scaling, rotation = opacity[mask], scaling[mask], rotation[mask]
     else:
         centers, shs, opacity, scaling, rotation = gs_params
-    if not centers.is_cuda:
-        raise RuntimeError(_NO_CPU)
+    require_device(centers)
     dev = centers.device
     N = len(cams)
     H, W = int(cams[0].image_height), int(cams[0].image_width)
@@ -324,8 +294,6 @@ def render_turntable(renderer, gs_params, cams, chunk=8, bg=None):
             cam.to_device(dev)
     c2w = torch.stack([_cam_c2w(cam) for cam in cams]).to(dev)
     ixt = torch.stack([fov_to_ixt(torch.tensor((cam.FoVx, cam.FoVy)), (W, H)) for cam in cams]).to(dev)
-    lib = _lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     for o in range(0, N, max(int(chunk), 1)):
         part = cams[o:o + max(int(chunk), 1)]
         n = len(part)
@@ -333,10 +301,7 @@ def render_turntable(renderer, gs_params, cams, chunk=8, bg=None):
         bgs = None if bg is None else torch.as_tensor(bg, dtype=torch.float32, device=dev).reshape(1, 3).expand(n, 3)
         out = renderer.render_views(part, rays, centers, shs, opacity, scaling, rotation, dev, bg_colors=bgs, concat=True)
         img, nrm, acc = (out[k].contiguous() for k in ("image", "rend_normal", "acc_map"))
-        with torch.cuda.device(dev):
-            _check(lib.lara_eval_quantize_frames(n, H, W, W, n * W, img.data_ptr(), nrm.data_ptr(), acc.data_ptr(),
-                                                 frames[o:o + n].data_ptr(), normals[o:o + n].data_ptr(), stream),
-                   "lara_eval_quantize_frames")
+        call("lara_eval_quantize_frames", dev, n, H, W, W, n * W, img, nrm, acc, frames[o:o + n], normals[o:o + n])
     return frames, normals
 
 

@@ -13,38 +13,14 @@ There is no CPU path and no torch fallback: tensors must live on the GPU and the
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import nn
 
-from .rasterizer import _alloc_bytes, _check, load_library
+from ._native import FeatvolDims as _Dims, alloc_bytes, call, query, require_device
+from ._native import load_library as _lib  # noqa: F401  (the shared loader; this name was imported from here)
 
 VOLUME, TOKENS = 0, 1          # LARA_FEATVOL_VOLUME / LARA_FEATVOL_TOKENS
 MAX_C, MAX_HW = 1024, 8192
-
-_configured = False
-
-
-class _Dims(ctypes.Structure):   # lara_featvol_dims
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "V", "C", "E", "h", "w", "R", "img_w", "img_h")] + \
-               [("eps", ctypes.c_float), ("x_stride", ctypes.c_int64 * 4)]
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        pd = ctypes.POINTER(_Dims)
-        lib.lara_featvol_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_featvol_workspace_bytes.argtypes = [pd]
-        lib.lara_featvol_forward.restype = ctypes.c_int
-        lib.lara_featvol_forward.argtypes = [pd] + [vp] * 10 + [i32, vp, vp, vp]
-        lib.lara_featvol_backward.restype = ctypes.c_int
-        lib.lara_featvol_backward.argtypes = [pd] + [vp] * 10 + [i32] + [vp] * 8
-        _configured = True
-    return lib
 
 
 class _ModLN(nn.Module):
@@ -67,8 +43,7 @@ class _Prep:
     """Everything one call of the kernels reads, checked and laid out."""
 
     def __init__(self, fv, batch, img_feats, n_views_sel):
-        if not img_feats.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(img_feats)
         if img_feats.dim() != 4 or img_feats.dtype != torch.float32:
             raise ValueError(f"img_feats must be fp32 [B*V, C, h, w]; got {img_feats.dtype} {tuple(img_feats.shape)}")
         V = int(n_views_sel)
@@ -103,25 +78,16 @@ class _Prep:
         self.p = (f(ln_w), f(ln_b), f(mlp_w), f(mlp_b), f(embed))
 
     def _ws(self):
-        n = _lib().lara_featvol_workspace_bytes(ctypes.byref(self.d))
-        if n < 0:
-            _check(int(n), "lara_featvol_workspace_bytes")
-        return _alloc_bytes(int(n), self.dev)
+        return alloc_bytes(query("lara_featvol_workspace_bytes", self.d), self.dev)
 
-    def _ptrs(self):
-        ln_w, ln_b, mlp_w, mlp_b, _ = self.p
-        return [t.data_ptr() for t in (self.x, self.rays, self.w2c, self.ixt, self.grid, ln_w, ln_b, mlp_w, mlp_b)]
+    def _inputs(self):
+        return (self.x, self.rays, self.w2c, self.ixt, self.grid) + self.p[:4]
 
     def forward(self, layout):
         CE, R = self.C + self.E, self.d.R
         out = (torch.empty(self.B, self.V, CE, R, R, R, dtype=torch.float32, device=self.dev) if layout == VOLUME else
                torch.empty(self.B * self.S, self.V, CE, dtype=torch.bfloat16, device=self.dev))
-        embed = self.p[4]
-        ws = self._ws()
-        with torch.cuda.device(self.dev):
-            _check(_lib().lara_featvol_forward(ctypes.byref(self.d), *self._ptrs(), None if embed is None else embed.data_ptr(),
-                                               layout, out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream),
-                   "lara_featvol_forward")
+        call("lara_featvol_forward", self.dev, self.d, *self._inputs(), self.p[4], layout, out, self._ws())
         return out
 
     def backward(self, grad, layout, want_embed=True):
@@ -133,12 +99,7 @@ class _Prep:
         d_lnw, d_lnb = torch.empty(C, **f32), torch.empty(C, **f32)
         d_w, d_b = torch.empty(2 * C, 32, **f32), torch.empty(2 * C, **f32)
         d_e = torch.empty(self.V, self.E, **f32) if (want_embed and self.E > 0) else None
-        ws = self._ws()
-        with torch.cuda.device(self.dev):
-            _check(_lib().lara_featvol_backward(ctypes.byref(self.d), *self._ptrs(), grad.data_ptr(), layout, dx.data_ptr(),
-                                                d_lnw.data_ptr(), d_lnb.data_ptr(), d_w.data_ptr(), d_b.data_ptr(),
-                                                None if d_e is None else d_e.data_ptr(), ws.data_ptr(),
-                                                torch.cuda.current_stream(self.dev).cuda_stream), "lara_featvol_backward")
+        call("lara_featvol_backward", self.dev, self.d, *self._inputs(), grad, layout, dx, d_lnw, d_lnb, d_w, d_b, d_e, self._ws())
         return dx, d_lnw, d_lnb, d_w, d_b, d_e
 
 

@@ -17,67 +17,22 @@ arguments; bind it with ``Decoder.forward_fine = lara_amd.fine.forward_fine``.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 
 import torch
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        lib.lara_point_feats_forward.restype = ctypes.c_int
-        lib.lara_point_feats_forward.argtypes = [i32, i32, i32, i32] + [vp] * 10
-        lib.lara_point_feats_backward.restype = ctypes.c_int
-        lib.lara_point_feats_backward.argtypes = [i32, i32, i32, i32] + [vp] * 14
-        lib.lara_point_feats_forward_concat.restype = ctypes.c_int
-        lib.lara_point_feats_forward_concat.argtypes = [i32, i32, i32, i32, i32] + [vp] * 10
-        lib.lara_point_feats_backward_concat.restype = ctypes.c_int
-        lib.lara_point_feats_backward_concat.argtypes = [i32, i32, i32, i32, i32] + [vp] * 14
-        lib.lara_point_feats_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_point_feats_workspace_bytes.argtypes = [i32, i32, i32]
-        lib.lara_fine_decoder_forward.restype = ctypes.c_int
-        lib.lara_fine_decoder_forward.argtypes = [i32] + [vp] * 9
-        lib.lara_fine_decoder_backward.restype = ctypes.c_int
-        lib.lara_fine_decoder_backward.argtypes = [i32] + [vp] * 15
-        lib.lara_fine_wgrad_floats.restype = i32
-        lib.lara_fine_wgrad_workspace_bytes.restype = ctypes.c_int64
-        lib.lara_fine_wgrad_workspace_bytes.argtypes = [i32]
-        lib.lara_fine_decoder_wgrad.restype = ctypes.c_int
-        lib.lara_fine_decoder_wgrad.argtypes = [i32] + [vp] * 9
-        lib.lara_fine_ln_blocks.restype = i32
-        lib.lara_fine_ln_blocks.argtypes = [i32]
-        lib.lara_fine_ln_forward.restype = ctypes.c_int
-        lib.lara_fine_ln_forward.argtypes = [i32, vp, vp, vp, ctypes.c_float, vp, vp, vp]
-        lib.lara_fine_ln_backward.restype = ctypes.c_int
-        lib.lara_fine_ln_backward.argtypes = [i32] + [vp] * 7
-        lib.lara_take_rows.restype = ctypes.c_int
-        lib.lara_take_rows.argtypes = [i32, vp, i32, ctypes.POINTER(_RowsItem), i32, vp]
-        lib.lara_voxel_rows.restype = ctypes.c_int
-        lib.lara_voxel_rows.argtypes = [i32, i32, vp, vp, vp, i32, vp]
-        _configured = True
-    return lib
+from ._native import RowsItem, alloc_bytes, call, query, require_device
 
 
 def _workspace(device, V, h, w):
-    n = _lib().lara_point_feats_workspace_bytes(V, h, w)
-    if n < 0:
-        _check(int(n), "lara_point_feats_workspace_bytes")
-    return torch.empty(int(n), dtype=torch.uint8, device=device)
+    return alloc_bytes(query("lara_point_feats_workspace_bytes", V, h, w), device)
 
 
 class _PointFeats(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, w2cs, ixts, img_ref, image, acc_map, depth, row_views):
-        if not points.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(points)
         f = lambda t: t.detach().float().contiguous()
         points, w2cs, ixts, img_ref, image, acc_map, depth = map(f, (points, w2cs, ixts, img_ref, image, acc_map, depth))
         n, V, h, w = points.shape[0], img_ref.shape[0], img_ref.shape[2], img_ref.shape[3]
@@ -91,12 +46,8 @@ class _PointFeats(torch.autograd.Function):
             raise RuntimeError("expected points [n,3], w2cs [V,4,4], ixts [V,3,3], img_ref [V,3,h,w], image [V,h,w,3], acc_map [V,h,w], depth [V,h,w,1]")
         out = torch.empty(V, 8, n, dtype=torch.float32, device=points.device)
         ws = _workspace(points.device, V, h, w)
-        with torch.cuda.device(points.device):
-            _check(_lib().lara_point_feats_forward_concat(n, V, int(row_views or 0), h, w, points.data_ptr(), w2cs.data_ptr(),
-                                                          ixts.data_ptr(), img_ref.data_ptr(), image.data_ptr(), acc_map.data_ptr(),
-                                                          depth.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                                          torch.cuda.current_stream(points.device).cuda_stream),
-                   "lara_point_feats_forward")
+        call("lara_point_feats_forward_concat", points.device, n, V, int(row_views or 0), h, w, points, w2cs, ixts, img_ref, image,
+             acc_map, depth, out, ws)
         ctx.save_for_backward(points, w2cs, ixts, img_ref, image, acc_map, depth)
         ctx.row_views = int(row_views or 0)
         return out
@@ -117,15 +68,9 @@ class _PointFeats(torch.autograd.Function):
             secs.append(flat[o:o + t.numel()].view(t.shape) if nd else None)
             o += sz
         d_image, d_acc, d_depth = secs
-        ptr = lambda t: None if t is None else t.data_ptr()
         ws = _workspace(points.device, V, h, w)
-        with torch.cuda.device(points.device):
-            _check(_lib().lara_point_feats_backward_concat(n, V, ctx.row_views, h, w, points.data_ptr(), w2cs.data_ptr(),
-                                                           ixts.data_ptr(), img_ref.data_ptr(), image.data_ptr(), acc_map.data_ptr(),
-                                                           depth.data_ptr(), g_out.data_ptr(), d_points.data_ptr(), ptr(d_image),
-                                                           ptr(d_acc), ptr(d_depth), ws.data_ptr(),
-                                                           torch.cuda.current_stream(points.device).cuda_stream),
-                   "lara_point_feats_backward")
+        call("lara_point_feats_backward_concat", points.device, n, V, ctx.row_views, h, w, points, w2cs, ixts, img_ref, image,
+             acc_map, depth, g_out, d_points, d_image, d_acc, d_depth, ws)
         return d_points if need[0] else None, None, None, None, d_image, d_acc, d_depth, None
 
 
@@ -144,18 +89,11 @@ class _TakeRows(torch.autograd.Function):
         return out, None
 
 
-class _RowsItem(ctypes.Structure):        # include/lara_pointfeat.h: lara_rows_item
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("width", ctypes.c_int32)]
-
-
 def _rows_call(idx, srcs, dsts, scatter):
-    items = (_RowsItem * len(srcs))()
+    items = (RowsItem * len(srcs))()
     for k, (a, b) in enumerate(zip(srcs, dsts)):
         items[k].src, items[k].dst, items[k].width = a.data_ptr(), b.data_ptr(), a[0].numel()
-    dev = srcs[0].device
-    with torch.cuda.device(dev):
-        _check(_lib().lara_take_rows(idx.numel(), idx.data_ptr(), len(srcs), items, int(scatter), torch.cuda.current_stream(dev).cuda_stream),
-               "lara_take_rows")
+    call("lara_take_rows", srcs[0].device, idx.numel(), idx, len(srcs), items, int(scatter))
 
 
 class _TakeRowsMulti(torch.autograd.Function):
@@ -164,8 +102,7 @@ class _TakeRowsMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, idx, *xs):
-        if not xs[0].is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(xs[0])
         if idx.dtype != torch.int64 or idx.device != xs[0].device or idx.dim() != 1:
             raise RuntimeError(f"lara_amd: take_rows needs a 1-D int64 index tensor on {xs[0].device}, got {idx.dtype} on {idx.device}")
         idx = idx.contiguous()
@@ -210,22 +147,19 @@ class _VoxelRowsScenes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vol, *vox):
-        if not vol.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(vol)
         if vol.dim() != 3 or len(vox) != vol.shape[0] or vol.shape[2] % 4:
             raise RuntimeError("lara_amd: voxel rows need vol [B, V, C] (C % 4 == 0) and one index tensor per scene")
         x = vol.detach().float().contiguous()
         dev, C = x.device, x.shape[2]
         outs = []
-        with torch.cuda.device(dev):
-            for i, v in enumerate(vox):
-                if v.dtype != torch.int64 or v.device != dev or v.dim() != 1:
-                    raise RuntimeError(f"lara_amd: voxel indices must be 1-D int64 tensors on {dev}")
-                v = v.contiguous()
-                out = torch.empty((v.numel(), C), dtype=torch.float32, device=dev)
-                _check(_lib().lara_voxel_rows(v.numel(), C, v.data_ptr(), x[i].data_ptr(), out.data_ptr(), 0,
-                                              torch.cuda.current_stream(dev).cuda_stream), "lara_voxel_rows")
-                outs.append(out)
+        for i, v in enumerate(vox):
+            if v.dtype != torch.int64 or v.device != dev or v.dim() != 1:
+                raise RuntimeError(f"lara_amd: voxel indices must be 1-D int64 tensors on {dev}")
+            v = v.contiguous()
+            out = torch.empty((v.numel(), C), dtype=torch.float32, device=dev)
+            call("lara_voxel_rows", dev, v.numel(), C, v, x[i], out, 0)
+            outs.append(out)
         ctx.save_for_backward(*[v.contiguous() for v in vox])
         ctx.shape = tuple(x.shape)
         ctx.set_materialize_grads(False)
@@ -237,13 +171,11 @@ class _VoxelRowsScenes(torch.autograd.Function):
         B, V, C = ctx.shape
         dev = vox[0].device
         d = torch.zeros(ctx.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            for i, (v, g) in enumerate(zip(vox, gs)):
-                if g is None or v.numel() == 0:
-                    continue
-                g = g.float().contiguous()
-                _check(_lib().lara_voxel_rows(v.numel(), C, v.data_ptr(), g.data_ptr(), d[i].data_ptr(), 1,
-                                              torch.cuda.current_stream(dev).cuda_stream), "lara_voxel_rows")
+        for i, (v, g) in enumerate(zip(vox, gs)):
+            if g is None or v.numel() == 0:
+                continue
+            g = g.float().contiguous()
+            call("lara_voxel_rows", dev, v.numel(), C, v, g, d[i], 1)
         return (d,) + (None,) * len(vox)
 
 
@@ -296,8 +228,7 @@ class _FineDecoder(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xn, pf, Wqk, W1ov, b1, W2, b2):
-        if not xn.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(xn)
         f = lambda t: t.detach().float().contiguous()
         xn, pf, Wqk, W1ov, b1, W2, b2 = map(f, (xn, pf, Wqk, W1ov, b1, W2, b2))
         n = xn.shape[0]
@@ -306,11 +237,7 @@ class _FineDecoder(torch.autograd.Function):
             raise RuntimeError("lara_fine_decoder_forward: the kernel is built for xn [n,80], pf [4,8,n], Wqk [64,80], "
                                "W1ov [64,64], b1 [64], W2 [12,64], b2 [12]")
         sh = torch.empty(n, _SH, dtype=torch.float32, device=xn.device)
-        with torch.cuda.device(xn.device):
-            _check(_lib().lara_fine_decoder_forward(n, xn.data_ptr(), pf.data_ptr(), Wqk.data_ptr(), W1ov.data_ptr(),
-                                                    b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), sh.data_ptr(),
-                                                    torch.cuda.current_stream(xn.device).cuda_stream),
-                   "lara_fine_decoder_forward")
+        call("lara_fine_decoder_forward", xn.device, n, xn, pf, Wqk, W1ov, b1, W2, b2, sh)
         ctx.save_for_backward(xn, pf, Wqk, W1ov, b1, W2, b2)
         return sh
 
@@ -322,21 +249,12 @@ class _FineDecoder(torch.autograd.Function):
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=xn.device)
         d_xn, d_pf = new(n, _FD), new(_NV, _CD, n)
         U, H, DH, DT = new(n, 64), new(n, _HID), new(n, _HID), new(n, 64)
-        with torch.cuda.device(xn.device):
-            _check(_lib().lara_fine_decoder_backward(n, xn.data_ptr(), pf.data_ptr(), Wqk.data_ptr(), W1ov.data_ptr(),
-                                                     b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), d_sh.data_ptr(),
-                                                     d_xn.data_ptr(), d_pf.data_ptr(), U.data_ptr(), H.data_ptr(),
-                                                     DH.data_ptr(), DT.data_ptr(),
-                                                     torch.cuda.current_stream(xn.device).cuda_stream),
-                   "lara_fine_decoder_backward")
-            # the five parameter gradients: reductions of the factor arrays over the points, one launch + an ordered sum
-            # (include/lara_finedec.h: lara_fine_decoder_wgrad; rounds 2-4: batched BLAS GEMMs + torch reductions, 79 launches)
-            lib = _lib()
-            dw = new(lib.lara_fine_wgrad_floats())
-            ws = torch.empty(max(lib.lara_fine_wgrad_workspace_bytes(n), 16), dtype=torch.uint8, device=xn.device)
-            _check(lib.lara_fine_decoder_wgrad(n, xn.data_ptr(), U.data_ptr(), H.data_ptr(), DH.data_ptr(), DT.data_ptr(),
-                                               d_sh.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                                               torch.cuda.current_stream(xn.device).cuda_stream), "lara_fine_decoder_wgrad")
+        call("lara_fine_decoder_backward", xn.device, n, xn, pf, Wqk, W1ov, b1, W2, b2, d_sh, d_xn, d_pf, U, H, DH, DT)
+        # the five parameter gradients: reductions of the factor arrays over the points, one launch + an ordered sum
+        # (include/lara_finedec.h: lara_fine_decoder_wgrad; rounds 2-4: batched BLAS GEMMs + torch reductions, 79 launches)
+        dw = new(query("lara_fine_wgrad_floats"))
+        ws = torch.empty(max(query("lara_fine_wgrad_workspace_bytes", n), 16), dtype=torch.uint8, device=xn.device)
+        call("lara_fine_decoder_wgrad", xn.device, n, xn, U, H, DH, DT, d_sh, dw, ws)
         o = 0
         out = []
         for shape in ((_NH * _CD, _FD), (_HID, _NH * _CD), (_HID,), (_SH, _HID), (_SH,)):
@@ -369,16 +287,12 @@ class _FineLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        if not x.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(x)
         x, gamma, beta = x.detach().float().contiguous(), gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         n = x.shape[0]
         xn = torch.empty_like(x)
         stats = torch.empty(n, 2, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _check(_lib().lara_fine_ln_forward(n, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), xn.data_ptr(),
-                                               stats.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
-                   "lara_fine_ln_forward")
+        call("lara_fine_ln_forward", x.device, n, x, gamma, beta, float(eps), xn, stats)
         ctx.save_for_backward(x, gamma, stats)
         return xn
 
@@ -388,14 +302,10 @@ class _FineLayerNorm(torch.autograd.Function):
         n = x.shape[0]
         d_xn = d_xn.float().contiguous()
         d_x = torch.empty_like(x)
-        lib = _lib()
-        parts = torch.empty(max(lib.lara_fine_ln_blocks(n), 1), 2 * _FD, dtype=torch.float32, device=x.device)
+        parts = torch.empty(max(query("lara_fine_ln_blocks", n), 1), 2 * _FD, dtype=torch.float32, device=x.device)
         if n == 0:
             parts.zero_()
-        with torch.cuda.device(x.device):
-            _check(lib.lara_fine_ln_backward(n, x.data_ptr(), gamma.data_ptr(), stats.data_ptr(), d_xn.data_ptr(), d_x.data_ptr(),
-                                             parts.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
-                   "lara_fine_ln_backward")
+        call("lara_fine_ln_backward", x.device, n, x, gamma, stats, d_xn, d_x, parts)
         tot = parts.sum(0)
         return d_x, tot[:_FD], tot[_FD:], None
 

@@ -14,44 +14,11 @@ are held to.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from .rasterizer import _check, load_library
+from ._native import ImageView as _ImgView, call, host_array, require_device, query
 
-_configured = False
 _weights = {}
-
-
-class _ImgView(ctypes.Structure):      # include/lara_loss.h: lara_image_view (element strides)
-    _fields_ = [("p", ctypes.c_void_p)] + [(n, ctypes.c_int64) for n in ("sN", "sC", "sY", "sV", "sX")] + [("Wv", ctypes.c_int32)]
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.lara_loss_partial_floats.restype = i64
-        lib.lara_loss_partial_floats.argtypes = [i64]
-        lib.lara_loss_terms_forward.restype = ctypes.c_int
-        lib.lara_loss_terms_forward.argtypes = [i32, i32, i32, i32] + [vp] * 10
-        lib.lara_loss_terms_backward.restype = ctypes.c_int
-        lib.lara_loss_terms_backward.argtypes = [i32, i32, i32, i32] + [vp] * 13
-        lib.lara_ms_ssim_workspace_floats.restype = i64
-        lib.lara_ms_ssim_workspace_floats.argtypes = [i32, i32, i32, i32]
-        lib.lara_ms_ssim_forward.restype = ctypes.c_int
-        lib.lara_ms_ssim_forward.argtypes = [i32, i32, i32, i32, ctypes.POINTER(_ImgView), ctypes.POINTER(_ImgView), vp, vp, vp, vp]
-        lib.lara_ms_ssim_backward.restype = ctypes.c_int
-        lib.lara_ms_ssim_backward.argtypes = [i32, i32, i32, i32, ctypes.POINTER(_ImgView), ctypes.POINTER(_ImgView), vp, vp,
-                                              ctypes.POINTER(_ImgView), vp, vp]
-        _configured = True
-    return lib
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class _LossTerms(torch.autograd.Function):
@@ -60,8 +27,7 @@ class _LossTerms(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tar, image, image_fine, rend_dist, rend_normal, depth_normal, acc_map):
-        if not image.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(image)
         f = lambda t: None if t is None else t.detach().float().contiguous()
         tar, image, image_fine, rend_dist, rend_normal, depth_normal, acc_map = map(
             f, (tar, image, image_fine, rend_dist, rend_normal, depth_normal, acc_map))
@@ -74,14 +40,10 @@ class _LossTerms(torch.autograd.Function):
         for t, c in ((rend_dist, 1), (rend_normal, 3), (depth_normal, 3), (acc_map, 1)):
             if t is not None and t.numel() != n * c:
                 raise RuntimeError("map sizes do not match tar_rgb")
-        lib = _lib()
         terms = torch.empty(4, dtype=torch.float32, device=image.device)
-        partials = torch.empty(int(lib.lara_loss_partial_floats(n)), dtype=torch.float32, device=image.device)
-        with torch.cuda.device(image.device):
-            _check(lib.lara_loss_terms_forward(B, V, H, W, tar.data_ptr(), image.data_ptr(), _ptr(image_fine), _ptr(rend_dist),
-                                               _ptr(rend_normal), _ptr(depth_normal), _ptr(acc_map), terms.data_ptr(),
-                                               partials.data_ptr(), torch.cuda.current_stream(image.device).cuda_stream),
-                   "lara_loss_terms_forward")
+        partials = torch.empty(query("lara_loss_partial_floats", n), dtype=torch.float32, device=image.device)
+        call("lara_loss_terms_forward", image.device, B, V, H, W, tar, image, image_fine, rend_dist, rend_normal, depth_normal,
+             acc_map, terms, partials)
         ctx.dims = (B, V, H, W)
         ctx.have = (image_fine is not None, rend_dist is not None, rend_normal is not None)
         ctx.save_for_backward(*[t for t in (tar, image, image_fine, rend_normal, depth_normal, acc_map) if t is not None])
@@ -104,11 +66,8 @@ class _LossTerms(torch.autograd.Function):
         d_rn = torch.empty_like(rend_normal) if have_normal and need[4] else None
         d_dn = torch.empty_like(depth_normal) if have_normal and need[5] else None
         g = g.float().contiguous()
-        with torch.cuda.device(dev):
-            _check(_lib().lara_loss_terms_backward(B, V, H, W, tar.data_ptr(), image.data_ptr(), _ptr(image_fine), _ptr(rend_normal),
-                                                   _ptr(depth_normal), _ptr(acc_map), g.data_ptr(), _ptr(d_image), _ptr(d_fine),
-                                                   _ptr(d_dist), _ptr(d_rn), _ptr(d_dn), torch.cuda.current_stream(dev).cuda_stream),
-                   "lara_loss_terms_backward")
+        call("lara_loss_terms_backward", dev, B, V, H, W, tar, image, image_fine, rend_normal, depth_normal, acc_map, g, d_image,
+             d_fine, d_dist, d_rn, d_dn)
         return None, d_image, d_fine, d_dist, d_rn, d_dn, None
 
 
@@ -207,11 +166,11 @@ _win_host = {}
 
 
 def _window_host(size=11, sigma=1.5):
-    """The filter taps as a ctypes array (the same fp32 numbers `_gauss_window` puts on the device)."""
+    """The filter taps as a host array (the same fp32 numbers `_gauss_window` puts on the device)."""
     key = (size, sigma)
     if key not in _win_host:
         w = _gauss_window("cpu", size, sigma)
-        _win_host[key] = (ctypes.c_float * size)(*[float(v) for v in w])
+        _win_host[key] = host_array("f", [float(v) for v in w])
     return _win_host[key]
 
 
@@ -222,23 +181,18 @@ class _MsSsimMeans(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, tar):
-        if not image.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(image)
         image, tar = image.detach().float().contiguous(), tar.detach().float().contiguous()
         B, V, H, W = tar.shape[:4]
         if tar.shape != (B, V, H, W, 3) or image.shape != (B, H, V * W, 3):
             raise RuntimeError("expected tar_rgb [B,V,H,W,3] and image [B,H,V*W,3]")
-        lib = _lib()
-        nws = int(lib.lara_ms_ssim_workspace_floats(B, 3, H, V * W))
-        if nws < 0:
-            raise ValueError(f"ms_ssim: the smaller image side must exceed {(11 - 1) * 2 ** 4} (four 2x downsamplings)")
+        nws = query("lara_ms_ssim_workspace_floats", B, 3, H, V * W, error=ValueError(
+            f"ms_ssim: the smaller image side must exceed {(11 - 1) * 2 ** 4} (four 2x downsamplings)"))
         ws = torch.empty(nws, dtype=torch.float32, device=image.device)
         means = torch.empty(5, B * 3, 2, dtype=torch.float32, device=image.device)
         xv = _ImgView(image.data_ptr(), H * V * W * 3, 1, V * W * 3, W * 3, 3, W)
         yv = _ImgView(tar.data_ptr(), V * H * W * 3, 1, W * 3, H * W * 3, 3, W)
-        with torch.cuda.device(image.device):
-            _check(lib.lara_ms_ssim_forward(B, 3, H, V * W, ctypes.byref(xv), ctypes.byref(yv), _window_host(), means.data_ptr(),
-                                            ws.data_ptr(), torch.cuda.current_stream(image.device).cuda_stream), "lara_ms_ssim_forward")
+        call("lara_ms_ssim_forward", image.device, B, 3, H, V * W, xv, yv, _window_host(), means, ws)
         ctx.dims = (B, V, H, W)
         ctx.save_for_backward(image, tar, ws)
         return means
@@ -252,10 +206,7 @@ class _MsSsimMeans(torch.autograd.Function):
         xv = _ImgView(image.data_ptr(), H * V * W * 3, 1, V * W * 3, W * 3, 3, W)
         yv = _ImgView(tar.data_ptr(), V * H * W * 3, 1, W * 3, H * W * 3, 3, W)
         dv = _ImgView(d_image.data_ptr(), H * V * W * 3, 1, V * W * 3, W * 3, 3, W)
-        with torch.cuda.device(image.device):
-            _check(_lib().lara_ms_ssim_backward(B, 3, H, V * W, ctypes.byref(xv), ctypes.byref(yv), _window_host(), d_means.data_ptr(),
-                                                ctypes.byref(dv), ws.data_ptr(), torch.cuda.current_stream(image.device).cuda_stream),
-                   "lara_ms_ssim_backward")
+        call("lara_ms_ssim_backward", image.device, B, 3, H, V * W, xv, yv, _window_host(), d_means, dv, ws)
         return d_image, None
 
 

@@ -17,16 +17,12 @@ state-dict key names are recalled -- PARITY with the `lpips` package is UNPINNED
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from .loss import _ImgView
-from .rasterizer import _check, load_library
+from ._native import (LPIPS_MAX_LAYERS as MAX_LAYERS, LPIPS_TAPS as TAPS, ImageView as _ImgView, LpipsLayer as _Layer,
+                      LpipsNet as _Net, call, query)
 
 ROW = 8                    # include/lara_lpips.h: LARA_LPIPS_ROW: five tap terms, their sum, 0, 0
-TAPS = 5
-MAX_LAYERS = 16
 SHIFT = (-0.030, -0.088, -0.188)
 SCALE = (0.458, 0.448, 0.450)
 
@@ -40,36 +36,6 @@ LAYERS = {
     "alex": [(3, 64, 11, 4, 2, 0, 0, True, (1, 0)), (64, 192, 5, 1, 2, 3, 2, True, (2, 3)), (192, 384, 3, 1, 1, 3, 2, True, (3, 6)),
              (384, 256, 3, 1, 1, 0, 0, True, (4, 8)), (256, 256, 3, 1, 1, 0, 0, True, (5, 10))],
 }
-_configured = False
-
-
-class _Layer(ctypes.Structure):      # include/lara_lpips.h: lara_lpips_layer
-    _fields_ = [("w", ctypes.c_void_p), ("bias", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("cin", "cout", "k", "stride", "pad", "pool_k", "pool_s", "tap")]
-
-
-class _Net(ctypes.Structure):        # lara_lpips_net
-    _fields_ = [("n_layers", ctypes.c_int32), ("layers", _Layer * MAX_LAYERS), ("lin", ctypes.c_void_p * TAPS),
-                ("shift", ctypes.c_float * 3), ("scale", ctypes.c_float * 3)]
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        lib.lara_lpips_workspace_bytes.restype = i64
-        lib.lara_lpips_workspace_bytes.argtypes = [ctypes.POINTER(_Net), i32, i32, i32]
-        lib.lara_lpips_forward.restype = ctypes.c_int
-        lib.lara_lpips_forward.argtypes = [ctypes.POINTER(_Net), i32, i32, i32, ctypes.POINTER(_ImgView), ctypes.POINTER(_ImgView),
-                                           f32, f32, vp, vp, vp]
-        lib.lara_lpips_conv2d.restype = ctypes.c_int
-        lib.lara_lpips_conv2d.argtypes = [i32] * 9 + [vp] * 5
-        lib.lara_lpips_maxpool.restype = ctypes.c_int
-        lib.lara_lpips_maxpool.argtypes = [i32] * 6 + [vp] * 3
-        _configured = True
-    return lib
-
 
 def _out(side, k, s, pad):
     return (side + 2 * pad - k) // s + 1 if side + 2 * pad >= k else 0
@@ -169,10 +135,8 @@ class LPIPS:
         return self
 
     def workspace_bytes(self, B, H, W):
-        n = int(_lib().lara_lpips_workspace_bytes(ctypes.byref(self._c_net()), B, H, W))
-        if n < 0:
-            raise ValueError(f"lara_amd.lpips: sizes out of range for lara_lpips_forward (B={B}, {H} x {W})")
-        return n
+        return query("lara_lpips_workspace_bytes", self._c_net(), B, H, W,
+                     error=ValueError(f"lara_amd.lpips: sizes out of range for lara_lpips_forward (B={B}, {H} x {W})"))
 
     def _c_net(self):
         if not self.weights:
@@ -193,10 +157,7 @@ class LPIPS:
         tap_shapes(self.net, H, W)                             # ValueError on an image too small
         self.to(dev)
         ws = torch.empty(self.workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _check(_lib().lara_lpips_forward(ctypes.byref(self._c_net()), B, H, W, ctypes.byref(xv), ctypes.byref(yv), mul, add,
-                                             scores.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                   "lara_lpips_forward")
+        call("lara_lpips_forward", dev, self._c_net(), B, H, W, xv, yv, mul, add, scores, ws)
 
     @torch.no_grad()
     def rows(self, in0, in1):
@@ -281,10 +242,7 @@ def conv2d_nhwc(x, packed, bias, stride=1, pad=0, relu=True):
     if not ((Cin == 3 and Cout % 16 == 0) or (Cin % 32 == 0 and Cout % 64 == 0)):
         raise ValueError(f"lara_amd.lpips: conv2d_nhwc: no kernel for Cin={Cin}, Cout={Cout} (Cin 3 or a multiple of 32, Cout of 64)")
     y = torch.empty(N, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib().lara_lpips_conv2d(N, H, W, Cin, Cout, k, stride, pad, int(relu), x.data_ptr(), packed.data_ptr(), bias.data_ptr(),
-                                      y.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
-    _check(rc, "lara_lpips_conv2d")
+    call("lara_lpips_conv2d", x.device, N, H, W, Cin, Cout, k, stride, pad, int(relu), x, packed, bias, y)
     return y
 
 
@@ -296,7 +254,5 @@ def maxpool_nhwc(x, k, s):
     if H < k or W < k or C % 4:
         raise ValueError("lara_amd.lpips: maxpool_nhwc: the window does not fit, or channels are no multiple of 4")
     y = torch.empty(N, (H - k) // s + 1, (W - k) // s + 1, C, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(_lib().lara_lpips_maxpool(N, H, W, C, k, s, x.data_ptr(), y.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
-               "lara_lpips_maxpool")
+    call("lara_lpips_maxpool", x.device, N, H, W, C, k, s, x, y)
     return y

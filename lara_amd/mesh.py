@@ -12,37 +12,13 @@ One deliberate difference: the reference raises (``argmax`` of an empty array) w
 empty mesh is returned and written.  No CPU path."""
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 
 import numpy as np
 import torch
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.lara_mesh_crop.restype = ctypes.c_int
-        lib.lara_mesh_crop.argtypes = [i64, i64, vp, vp, ctypes.POINTER(ctypes.c_double * 6), vp, vp, vp]
-        lib.lara_mesh_compact_rows.restype = ctypes.c_int
-        lib.lara_mesh_compact_rows.argtypes = [i64, i32, vp, vp, vp, vp, vp]
-        lib.lara_mesh_cluster_labels.restype = ctypes.c_int
-        lib.lara_mesh_cluster_labels.argtypes = [i64, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i32), vp]
-        lib.lara_mesh_cluster_stats.restype = ctypes.c_int
-        lib.lara_mesh_cluster_stats.argtypes = [i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
-        lib.lara_mesh_keep_clusters.restype = ctypes.c_int
-        lib.lara_mesh_keep_clusters.argtypes = [i64, i64] + [vp] * 8
-        lib.lara_mesh_remap.restype = ctypes.c_int
-        lib.lara_mesh_remap.argtypes = [i64, i64] + [vp] * 5
-        _configured = True
-    return lib
+from ._native import call, host_array, require_device
 
 
 def _compact(rows, keep, ends, n_out):
@@ -51,8 +27,7 @@ def _compact(rows, keep, ends, n_out):
     if n_out == 0:
         return out
     width = rows[0].numel() * rows.element_size() // 4 if rows.shape[0] else 1
-    _check(_lib().lara_mesh_compact_rows(rows.shape[0], width, rows.data_ptr(), keep.data_ptr(), ends.data_ptr(), out.data_ptr(),
-                                         torch.cuda.current_stream(rows.device).cuda_stream), "lara_mesh_compact_rows")
+    call("lara_mesh_compact_rows", rows.device, rows.shape[0], width, rows, keep, ends, out)
     return out
 
 
@@ -75,8 +50,7 @@ def clean_mesh(vertices, triangles, colors=None, aabb=None, keep=10):
     computes them.  Everything stays on the device; the host reads sizes only (and the kernels' error word with them),
     plus one word per union round inside ``lara_mesh_cluster_labels``."""
     dev = vertices.device
-    if dev.type != "cuda":
-        raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+    require_device(dev)
     V = vertices.detach().to(torch.float32).contiguous()
     Nv = V.shape[0]
     if V.dim() != 2 or V.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
@@ -85,16 +59,13 @@ def clean_mesh(vertices, triangles, colors=None, aabb=None, keep=10):
         raise RuntimeError("lara_amd.mesh.clean_mesh: meshes need Nv < 2^31 and 3 T < 2^31 (int32 indices)")
     F = triangles.to(device=dev, dtype=torch.int32).contiguous()
     C_in = None if colors is None else colors.detach().to(dev).contiguous()
-    lib = _lib()
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if aabb is not None and F.shape[0]:
             box = np.asarray(aabb, np.float64).reshape(2, 3) * 1.1          # meshExtractor.py:37, in double as numpy does
-            cbox = (ctypes.c_double * 6)(*box.reshape(-1).tolist())
+            cbox = host_array("d", box.reshape(-1).tolist())
             inside = torch.empty(F.shape[0], dtype=torch.int32, device=dev)
-            _check(lib.lara_mesh_crop(Nv, F.shape[0], V.data_ptr(), F.data_ptr(), ctypes.byref(cbox), inside.data_ptr(),
-                                      err.data_ptr(), stream), "lara_mesh_crop")
+            call("lara_mesh_crop", dev, Nv, F.shape[0], V, F, cbox, inside, err)
             ends = torch.cumsum(inside, 0, dtype=torch.int64)
             n_in, e = torch.stack([ends[-1], err[0].long()]).tolist()       # host read: the cropped size
             _raise_on(e, "clean_mesh")
@@ -112,9 +83,8 @@ def clean_mesh(vertices, triangles, colors=None, aabb=None, keep=10):
         adj = torch.empty(3 * T, **i32)
         label = torch.empty(T, **i32)
         work = torch.empty(2, **i32)
-        rounds = ctypes.c_int32(0)
-        _check(lib.lara_mesh_cluster_labels(T, F.data_ptr(), cap, keys.data_ptr(), owner.data_ptr(), adj.data_ptr(), label.data_ptr(),
-                                            work.data_ptr(), ctypes.byref(rounds), stream), "lara_mesh_cluster_labels")
+        rounds = host_array("i", 1)                                            # (host word the call writes)
+        call("lara_mesh_cluster_labels", dev, T, F, cap, keys, owner, adj, label, work, rounds)
         del keys, owner, adj
         root_ends = torch.cumsum(label == torch.arange(T, **i32), 0, dtype=torch.int64)
         C = int(root_ends[-1])                                                 # host read: the number of clusters
@@ -122,26 +92,23 @@ def clean_mesh(vertices, triangles, colors=None, aabb=None, keep=10):
         counts = torch.zeros(C, dtype=torch.int64, device=dev)
         acc = torch.zeros(2 * C, dtype=torch.int64, device=dev)
         area = torch.empty(C, dtype=torch.float64, device=dev)
-        _check(lib.lara_mesh_cluster_stats(Nv, T, V.data_ptr(), F.data_ptr(), label.data_ptr(), root_ends.data_ptr(), C,
-                                           clusters.data_ptr(), counts.data_ptr(), acc.data_ptr(), area.data_ptr(), err.data_ptr(),
-                                           stream), "lara_mesh_cluster_stats")
+        call("lara_mesh_cluster_stats", dev, Nv, T, V, F, label, root_ends, C, clusters, counts, acc, area, err)
         # meshExtractor.py:130: n = sort(counts)[-min(C, keep)] -- C is small, one sort; the threshold stays on the device
         i = (C - min(C, int(keep))) % C
         threshold = torch.sort(counts).values[i:i + 1]
         kept = torch.empty(T, **i32)
         referenced = torch.zeros(Nv, **i32)
-        _check(lib.lara_mesh_keep_clusters(Nv, T, F.data_ptr(), clusters.data_ptr(), counts.data_ptr(), threshold.data_ptr(),
-                                           kept.data_ptr(), referenced.data_ptr(), err.data_ptr(), stream), "lara_mesh_keep_clusters")
+        call("lara_mesh_keep_clusters", dev, Nv, T, F, clusters, counts, threshold, kept, referenced, err)
         tends = torch.cumsum(kept, 0, dtype=torch.int64)
         vends = torch.cumsum(referenced, 0, dtype=torch.int64)
         T2, Nv2, e = torch.stack([tends[-1], vends[-1], err[0].long()]).tolist()   # host read: the output sizes
         _raise_on(e, "clean_mesh")
         F2 = _compact(F, kept, tends, T2)
         out_t = torch.empty_like(F2)
-        _check(lib.lara_mesh_remap(Nv, T2, F2.data_ptr(), vends.data_ptr(), out_t.data_ptr(), err.data_ptr(), stream), "lara_mesh_remap")
+        call("lara_mesh_remap", dev, Nv, T2, F2, vends, out_t, err)
         V2 = _compact(V, referenced, vends, Nv2)
         C2 = None if C_in is None else _compact(C_in, referenced, vends, Nv2)
-    info = {"triangle_clusters": clusters, "cluster_n_triangles": counts, "cluster_area": area, "union_rounds": rounds.value}
+    info = {"triangle_clusters": clusters, "cluster_n_triangles": counts, "cluster_area": area, "union_rounds": rounds[0]}
     return V2, out_t.long(), C2, info
 
 

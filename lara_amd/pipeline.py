@@ -37,7 +37,7 @@ import os
 import torch
 from torch import nn
 
-from . import cameras, coarse
+from . import _native, cameras, coarse
 from .fine import _tn_over_points, fold_fine_weights, forward_fine, sample_point_feats, take_rows, take_rows_multi, voxel_rows_scenes
 from .renderer import Renderer, _AssembleScenes, batch_map_buffers
 
@@ -298,8 +298,7 @@ class LaRaPipeline(nn.Module):
                           volume_feat_up.shape[0], with_fine, return_buffer)
 
     def _step(self, batch, make_gaussians, dev, B, with_fine, return_buffer=False):
-        if dev.type != "cuda":
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        _native.require_device(dev)
         n_sel = self.n_views
         scalars = self.host_scalars(batch)
         cur = torch.cuda.current_stream(dev)

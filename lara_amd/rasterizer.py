@@ -14,14 +14,13 @@ Same names, argument meaning, return arity and error behaviour; differentiable w
 means3D / shs (or colors_precomp) / opacities / scales / rotations (or cov3D_precomp, which in the
 2DGS rasteriser is the precomputed 3x3 splat-to-pixel matrix), and hands a gradient to ``means2D``.
 
-The host side is a thin ctypes binding of the C ABI in ``include/lara2dgs.h``: PyTorch only owns
+The host side calls the C ABI of ``include/lara2dgs.h`` through the binding in ``lara_amd/_native.py``: PyTorch only owns
 memory and the stream.  There is no CPU path and no fallback: without ``liblara2dgs.so`` or with
 non-GPU tensors the operator raises.
 """
 from __future__ import annotations
 
 import collections
-import ctypes
 import os
 import threading
 import time
@@ -31,97 +30,15 @@ from typing import NamedTuple, Optional
 import torch
 from torch import nn
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# (LARA2DGS_LIB: another build of the same library -- kernel A/B experiments, tools/build_variant.sh; never a CPU path)
-LIB_PATH = os.environ.get("LARA2DGS_LIB") or os.path.join(_HERE, "liblara2dgs.so")
-ABI_VERSION = 10
-
-
-class _View(ctypes.Structure):
-    _fields_ = [
-        ("P", ctypes.c_int32), ("sh_degree", ctypes.c_int32), ("sh_coeffs", ctypes.c_int32),
-        ("image_height", ctypes.c_int32), ("image_width", ctypes.c_int32),
-        ("tanfovx", ctypes.c_float), ("tanfovy", ctypes.c_float), ("scale_modifier", ctypes.c_float),
-        ("prefiltered", ctypes.c_int32), ("debug", ctypes.c_int32), ("forward_only", ctypes.c_int32),
-        ("capacity", ctypes.c_int64),
-        ("bg", ctypes.c_void_p), ("viewmatrix", ctypes.c_void_p),
-        ("projmatrix", ctypes.c_void_p), ("campos", ctypes.c_void_p),
-        ("counts_out", ctypes.c_void_p),
-    ]
-
-
-class _Subset(ctypes.Structure):        # struct lara2dgs_subset
-    _fields_ = [("coarse_state", ctypes.c_void_p), ("coarse_state_stride", ctypes.c_int64), ("coarse_capacity", ctypes.c_int64),
-                ("coarse_P", ctypes.c_int32), ("coarse_forward_only", ctypes.c_int32), ("inv", ctypes.c_void_p)]
-
-
-class GradLayout(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int64) for n in
-                ("means3D", "means2D", "shs", "colors", "opacities", "scales", "rotations", "transmat", "total")]
-
-
-class StateLayout(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int64) for n in
-                ("header", "geom", "cullbox", "point_list", "ranges", "tile_order", "pair_base", "pair_pos", "final_T", "n_contrib",
-                 "seg_base", "seg_cnt", "bwd_order", "bwd_items", "ckpt", "pair_mask", "tile_maxc", "seg_cost", "total")]
-
-
-_lib = None
+from . import _native
+# (the binding lives in lara_amd/_native.py; these names stay importable from here)
+from ._native import (ABI_VERSION, LIB_PATH, GradLayout, StateLayout, Subset as _Subset, View as _View,  # noqa: F401
+                      alloc_bytes as _alloc_bytes, check as _check, check_poison_guards, _poison_mode)
 
 
 def load_library():
-    """Load liblara2dgs.so (built by ``__graft_entry__.build()`` / ``make -C lara_amd/csrc``)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"lara_amd: HIP library not found at {LIB_PATH}. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lara_amd/csrc`. "
-            "There is no CPU fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.lara2dgs_abi_version.restype = ctypes.c_int
-    lib.lara2dgs_error_string.restype = ctypes.c_char_p
-    lib.lara2dgs_error_string.argtypes = [ctypes.c_int]
-    lib.lara2dgs_last_hip_error.restype = ctypes.c_int
-    lib.lara2dgs_state_bytes.restype = i64
-    lib.lara2dgs_state_bytes.argtypes = [i32, i32, i32, i64, i32]
-    lib.lara2dgs_scratch_bytes.restype = i64
-    lib.lara2dgs_scratch_bytes.argtypes = [i32, i32, i32, i64, i32]
-    lib.lara2dgs_get_state_layout.restype = ctypes.c_int
-    lib.lara2dgs_get_state_layout.argtypes = [i32, i32, i32, i64, i32, ctypes.POINTER(StateLayout)]
-    lib.lara2dgs_forward.restype = ctypes.c_int
-    lib.lara2dgs_forward.argtypes = [ctypes.POINTER(_View)] + [vp] * 13
-    lib.lara2dgs_backward.restype = ctypes.c_int
-    lib.lara2dgs_backward.argtypes = [ctypes.POINTER(_View)] + [vp] * 20
-    lib.lara2dgs_forward_views.restype = ctypes.c_int
-    lib.lara2dgs_forward_views.argtypes = [i32, ctypes.POINTER(_View)] + [vp] * 11 + [i64, vp, i64, vp]
-    lib.lara2dgs_forward_views_subset.restype = ctypes.c_int
-    lib.lara2dgs_forward_views_subset.argtypes = [i32, ctypes.POINTER(_View)] + [vp] * 11 + [i64, vp, i64, ctypes.POINTER(_Subset), vp]
-    lib.lara2dgs_backward_views.restype = ctypes.c_int
-    lib.lara2dgs_backward_views.argtypes = [i32, ctypes.POINTER(_View)] + [vp] * 10 + [i64, vp, i64, vp, vp]
-    lib.lara2dgs_get_grad_layout.restype = ctypes.c_int
-    lib.lara2dgs_get_grad_layout.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(GradLayout)]
-    lib.lara2dgs_mark_visible.restype = ctypes.c_int
-    lib.lara2dgs_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
-    lib.lara2dgs_profile_enable.restype = ctypes.c_int
-    lib.lara2dgs_profile_enable.argtypes = [ctypes.c_int]
-    lib.lara2dgs_profile_collect.restype = ctypes.c_int
-    lib.lara2dgs_profile_collect.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-    lib.lara2dgs_selftest.restype = ctypes.c_int
-    lib.lara2dgs_selftest.argtypes = [ctypes.c_int, vp, vp, vp]
-    if lib.lara2dgs_abi_version() != ABI_VERSION:
-        raise RuntimeError("lara_amd: liblara2dgs.so ABI version mismatch; rebuild the library")
-    _lib = lib
-    return lib
-
-
-def _check(rc: int, what: str):
-    if rc != 0:
-        lib = load_library()
-        raise RuntimeError(f"lara_amd: {what} failed: {lib.lara2dgs_error_string(rc).decode()} "
-                           f"(hipError {lib.lara2dgs_last_hip_error()})")
+    """The shared loader.  `LIB_PATH` of this module is still the path it loads from: pointing it elsewhere works as before."""
+    return _native.load_library(LIB_PATH)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -318,41 +235,10 @@ def _run_forward(bucket, n, enqueue, debug=False):
 _scratch = {}   # (device index, stream id) -> uint8 tensor
 
 
-_GUARD = 1 << 16   # poison mode: guard bytes on either side of a state / scratch buffer
-_guards = []       # poison mode: [(whole allocation, payload bytes)] handed out since the last check_poison_guards()
-
-
-def _poison_mode() -> bool:
-    return os.environ.get("LARA2DGS_POISON_BUFFERS") == "1"
-
-
-def _alloc_bytes(n: int, device: torch.device) -> torch.Tensor:
-    """A state / scratch buffer.  LARA2DGS_POISON_BUFFERS=1 (tests / debugging): the buffer sits between two 64 KB guard
-    zones and everything is filled with 0xFF bytes (NaN as floats, 4 G as counts) before the library sees it -- a kernel that
-    reads a field before it is written, or beyond either end, then fails loudly instead of living off whatever the caching
-    allocator left around, and `check_poison_guards()` finds a write beyond either end."""
-    if not _poison_mode():
-        return torch.empty(n, dtype=torch.uint8, device=device)
-    whole = torch.empty(n + 2 * _GUARD, dtype=torch.uint8, device=device)
-    whole.fill_(255)
-    _guards.append((whole, n))
-    return whole[_GUARD:_GUARD + n]
-
-
-def check_poison_guards() -> list:
-    """Poison mode: the payload sizes of the buffers handed out since the last call whose guard zones no longer read 0xFF
-    (i.e. some kernel wrote outside the buffer); synchronises the device."""
-    torch.cuda.synchronize()
-    bad = [n for whole, n in _guards
-           if not bool((whole[:_GUARD] == 255).all()) or not bool((whole[_GUARD + n:] == 255).all())]
-    _guards.clear()
-    return bad
-
-
 def _get_scratch(device: torch.device, nbytes: int) -> torch.Tensor:
     if _poison_mode():      # a fresh, guarded, 0xFF-filled buffer per call (the backward must not live off the forward's either)
         return _alloc_bytes(nbytes, device)
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    key = (device.index, _native.current_stream(device))
     buf = _scratch.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
@@ -377,10 +263,6 @@ def _prep(t: Optional[torch.Tensor], name: str, device) -> Optional[torch.Tensor
     if t.data_ptr() % 16:
         t = t.clone()
     return t
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -419,8 +301,7 @@ def _validate(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_
     """Shape / device checks of the operator; returns the kernel-ready tensors."""
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if not means3D.is_cuda:
-        raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+    _native.require_device(means3D)
     device = means3D.device
     P = means3D.shape[0]
     means3D_c = _prep(means3D, "means3D", device)
@@ -506,17 +387,19 @@ def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotation
                 views[i].capacity = cap
                 views[i].forward_only = fo
                 views[i].counts_out = counts_ptr + 16 * i
+            # Direct calls of the typed handle, here and in the backward, not `_native.call`: the rasteriser's per-call rates are
+            # host-bound, the device is already entered, and the helper's pass over 17 arguments is work per call they can see.
             sb = (lib.lara2dgs_state_bytes(_sizing_P(P), H, W, cap, fo) + 255) // 256 * 256
             qb = (lib.lara2dgs_scratch_bytes(_sizing_P(P), H, W, cap, fo) + 255) // 256 * 256
             state = _alloc_bytes(n * sb, device)
             scratch = _get_scratch(device, n * qb)      # a scratch buffer per view: every kernel is one launch over the cameras
-            args = (n, views, _ptr(means3D_c), _ptr(sh_c), _ptr(col_c), _ptr(opa_c), _ptr(sc_c), _ptr(rot_c), _ptr(tm_c),
-                    color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), state.data_ptr(), sb, scratch.data_ptr(), qb)
+            args = (n, views, *_native.pointers(means3D_c, sh_c, col_c, opa_c, sc_c, rot_c, tm_c, color, allmap, radii, state),
+                    sb, scratch.data_ptr(), qb)
             if sub is None:
-                rc = lib.lara2dgs_forward_views(*args, torch.cuda.current_stream(device).cuda_stream)
+                _check(lib.lara2dgs_forward_views(*args, _native.current_stream(device)), "lara2dgs_forward_views")
             else:
-                rc = lib.lara2dgs_forward_views_subset(*args, ctypes.byref(sub), torch.cuda.current_stream(device).cuda_stream)
-            _check(rc, "lara2dgs_forward_views")
+                _check(lib.lara2dgs_forward_views_subset(*args, sub, _native.current_stream(device)),
+                       "lara2dgs_forward_views_subset")
             return state, (lambda: state.view(n, sb)[:, :64].contiguous().view(torch.int32)), (sb, qb)
 
         state, cap, (sb, qb), D = _run_forward(_bucket(device, P, H, W), n, enqueue, any(rs.debug for rs in settings))
@@ -567,7 +450,8 @@ class _RasterizeViews(torch.autograd.Function):
         H, W = int(rs0.image_height), int(rs0.image_width)
         state, cap, (sb, qb) = ctx.state, ctx.cap, ctx.strides
         G = GradLayout()
-        _check(lib.lara2dgs_get_grad_layout(P, ctx.M, int(has_sh), int(has_col), int(has_sr), int(has_tm), ctypes.byref(G)),
+        # (direct calls on the per-call path: see `_forward_views_impl`)
+        _check(lib.lara2dgs_get_grad_layout(P, ctx.M, int(has_sh), int(has_col), int(has_sr), int(has_tm), G),
                "lara2dgs_get_grad_layout")
         with torch.cuda.device(device):
             if grad_color is None:
@@ -585,13 +469,10 @@ class _RasterizeViews(torch.autograd.Function):
             # each view's gradient rows stay in its own scratch buffer until ONE preprocess_bwd launch folds the n views into
             # the summed gradient (no per-view gradient tensors)
             scratch = _get_scratch(device, n * qb)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = lib.lara2dgs_backward_views(
-                n, views, _ptr(means3D), _ptr(sh if has_sh else None), _ptr(col if has_col else None),
-                _ptr(sc if has_sr else None), _ptr(rot if has_sr else None), _ptr(tm if has_tm else None),
-                radii.data_ptr(), grad_color.data_ptr(), _ptr(grad_allmap), state.data_ptr(), sb,
-                scratch.data_ptr(), qb, out.data_ptr(), stream)
-            _check(rc, "lara2dgs_backward_views")
+            ptrs = _native.pointers(means3D, sh if has_sh else None, col if has_col else None, sc if has_sr else None,
+                                    rot if has_sr else None, tm if has_tm else None, radii, grad_color, grad_allmap, state)
+            _check(lib.lara2dgs_backward_views(n, views, *ptrs, sb, scratch.data_ptr(), qb, out.data_ptr(),
+                                               _native.current_stream(device)), "lara2dgs_backward_views")
 
         def sec(off, k, shape):
             return None if off < 0 else out[off:off + P * k].view(shape)
@@ -674,7 +555,6 @@ class GaussianRasterizer(nn.Module):
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Boolean mask of points in front of the near plane (view-space z > 0.2)."""
-        lib = load_library()
         rs = self.raster_settings
         with torch.no_grad():
             if not positions.is_cuda:
@@ -685,11 +565,7 @@ class GaussianRasterizer(nn.Module):
             present = torch.zeros((P,), dtype=torch.uint8, device=device)
             vm = _prep(rs.viewmatrix, "viewmatrix", device)
             pm = _prep(rs.projmatrix, "projmatrix", device)
-            with torch.cuda.device(device):
-                rc = lib.lara2dgs_mark_visible(P, _ptr(pos), vm.data_ptr(), pm.data_ptr(),
-                                               present.data_ptr(),
-                                               torch.cuda.current_stream(device).cuda_stream)
-            _check(rc, "lara2dgs_mark_visible")
+            _native.call("lara2dgs_mark_visible", device, P, pos, vm, pm, present)
         return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
@@ -710,9 +586,8 @@ class GaussianRasterizer(nn.Module):
 def state_views(state: torch.Tensor, P: int, H: int, W: int, cap: int, forward_only: bool = False) -> dict:
     """Typed views into a forward's ``state`` buffer (the integer parity surface).  A forward-only state holds the sections
     up to `tile_order`."""
-    lib = load_library()
     L = StateLayout()
-    _check(lib.lara2dgs_get_state_layout(P, H, W, cap, int(forward_only), ctypes.byref(L)), "lara2dgs_get_state_layout")
+    _native.call("lara2dgs_get_state_layout", None, P, H, W, cap, int(forward_only), L)
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
 
     def sec(off, nbytes, dtype, shape):
@@ -764,9 +639,8 @@ def profile_enable(on: bool = True):
 
 def profile_collect(max_entries: int = 65536) -> list:
     """[(kernel name, milliseconds)] since the last collect; synchronises the recorded events."""
-    lib = load_library()
-    names = ctypes.create_string_buffer(max_entries * 24)
-    ms = (ctypes.c_float * max_entries)()
-    n = lib.lara2dgs_profile_collect(names, len(names), ms, max_entries)
+    names = _native.char_buffer(max_entries * 24)
+    ms = _native.host_array("f", max_entries)
+    n = load_library().lara2dgs_profile_collect(names, len(names), ms, max_entries)
     parts = names.raw.split(b"\0")
     return [(parts[i].decode(), float(ms[i])) for i in range(n)]

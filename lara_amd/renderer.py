@@ -17,37 +17,13 @@ working.  No CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 from torch import nn
 
-from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _check, load_library,
-                         rasterize_gaussians_views)
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-        lib.lara_surface_maps_forward.restype = ctypes.c_int
-        lib.lara_surface_maps_forward.argtypes = [i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
-        lib.lara_surface_maps_backward.restype = ctypes.c_int
-        lib.lara_surface_maps_backward.argtypes = [i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.lara_activate_gaussians_forward.restype = ctypes.c_int
-        lib.lara_activate_gaussians_forward.argtypes = [ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp]
-        lib.lara_activate_gaussians_backward.restype = ctypes.c_int
-        lib.lara_activate_gaussians_backward.argtypes = [ctypes.c_int64] + [vp] * 10
-        lib.lara_surface_maps_forward_views.restype = ctypes.c_int
-        lib.lara_surface_maps_forward_views.argtypes = [i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
-        lib.lara_surface_maps_backward_views.restype = ctypes.c_int
-        lib.lara_surface_maps_backward_views.argtypes = [i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        _configured = True
-    return lib
+from ._native import call, require_device
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_views
 
 
 class _SurfaceMaps(torch.autograd.Function):
@@ -56,8 +32,7 @@ class _SurfaceMaps(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, color, allmap, rays, rot, depth_ratio):
-        if not color.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(color)
         color, allmap = color.float().contiguous(), allmap.float().contiguous()
         rays, rot = rays.detach().float().contiguous(), rot.detach().float().contiguous()
         H, W = color.shape[1], color.shape[2]
@@ -66,12 +41,8 @@ class _SurfaceMaps(torch.autograd.Function):
         o = dict(dtype=torch.float32, device=color.device)
         image, depth, acc = torch.empty(H, W, 3, **o), torch.empty(H, W, 1, **o), torch.empty(H, W, **o)
         rnorm, dnorm, rdist = torch.empty(H, W, 3, **o), torch.empty(H, W, 3, **o), torch.empty(H, W, **o)
-        with torch.cuda.device(color.device):
-            _check(_lib().lara_surface_maps_forward(H, W, color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), rot.data_ptr(),
-                                                    float(depth_ratio), image.data_ptr(), depth.data_ptr(), acc.data_ptr(),
-                                                    rnorm.data_ptr(), dnorm.data_ptr(), rdist.data_ptr(),
-                                                    torch.cuda.current_stream(color.device).cuda_stream),
-                   "lara_surface_maps_forward")
+        call("lara_surface_maps_forward", color.device, H, W, color, allmap, rays, rot, float(depth_ratio), image, depth, acc, rnorm,
+             dnorm, rdist)
         ctx.save_for_backward(color, allmap, rays, rot)
         ctx.depth_ratio = float(depth_ratio)
         ctx.set_materialize_grads(False)     # an output the loss does not read keeps a None gradient (kernel: NULL = zero)
@@ -84,12 +55,7 @@ class _SurfaceMaps(torch.autograd.Function):
         gs = [None if g is None else g.float().contiguous() for g in (g_image, g_depth, g_acc, g_rnorm, g_dnorm, g_rdist)]
         d_color = torch.empty_like(color)
         d_allmap = None if all(g is None for g in gs[1:]) else torch.empty_like(allmap)     # (see _SurfaceMapsViews.backward)
-        with torch.cuda.device(color.device):
-            _check(_lib().lara_surface_maps_backward(H, W, color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), rot.data_ptr(),
-                                                     ctx.depth_ratio, *[None if g is None else g.data_ptr() for g in gs],
-                                                     d_color.data_ptr(), None if d_allmap is None else d_allmap.data_ptr(),
-                                                     torch.cuda.current_stream(color.device).cuda_stream),
-                   "lara_surface_maps_backward")
+        call("lara_surface_maps_backward", color.device, H, W, color, allmap, rays, rot, ctx.depth_ratio, *gs, d_color, d_allmap)
         return d_color, d_allmap, None, None, None
 
 
@@ -99,17 +65,13 @@ class _Activate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, opacity, scales, rotations):
-        if not opacity.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(opacity)
         P = opacity.shape[0]
         if opacity.shape != (P, 1) or scales.shape != (P, 2) or rotations.shape != (P, 4):
             raise RuntimeError("expected opacity [P,1], scales [P,2], rotations [P,4]")
         o, s, r = (t.detach().float().contiguous() for t in (opacity, scales, rotations))
         oa, sa, ra = torch.empty_like(o), torch.empty_like(s), torch.empty_like(r)
-        with torch.cuda.device(o.device):
-            _check(_lib().lara_activate_gaussians_forward(P, o.data_ptr(), s.data_ptr(), r.data_ptr(), oa.data_ptr(), sa.data_ptr(),
-                                                          ra.data_ptr(), torch.cuda.current_stream(o.device).cuda_stream),
-                   "lara_activate_gaussians_forward")
+        call("lara_activate_gaussians_forward", o.device, P, o, s, r, oa, sa, ra)
         ctx.save_for_backward(oa, sa, r)
         ctx.set_materialize_grads(False)
         return oa, sa, ra
@@ -121,12 +83,7 @@ class _Activate(torch.autograd.Function):
         gs = [None if g is None else g.float().contiguous() for g in (g_o, g_s, g_r)]
         need = ctx.needs_input_grad
         d = [torch.empty_like(t) if n else None for t, n in zip((oa, sa, r), need)]
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(oa.device):
-            _check(_lib().lara_activate_gaussians_backward(P, oa.data_ptr(), sa.data_ptr(), r.data_ptr(), ptr(gs[0]), ptr(gs[1]),
-                                                           ptr(gs[2]), ptr(d[0]), ptr(d[1]), ptr(d[2]),
-                                                           torch.cuda.current_stream(oa.device).cuda_stream),
-                   "lara_activate_gaussians_backward")
+        call("lara_activate_gaussians_backward", oa.device, P, oa, sa, r, *gs, *d)
         return tuple(d)
 
 
@@ -141,8 +98,7 @@ class _SurfaceMapsViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, color, allmap, rays, rots, depth_ratio, into=None):
-        if not color.is_cuda:
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(color)
         color, allmap = color.float().contiguous(), allmap.float().contiguous()
         rays, rots = rays.detach().float().contiguous(), rots.detach().float().contiguous()
         n, H, W = color.shape[0], color.shape[2], color.shape[3]
@@ -160,12 +116,8 @@ class _SurfaceMapsViews(torch.autograd.Function):
                 if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous() or t.device != color.device or t.requires_grad:
                     raise RuntimeError("lara_amd: `into` buffers must be contiguous fp32 tensors of the maps' shapes that need no gradient")
             image, depth, acc, rnorm, dnorm, rdist = (t.detach() for t in into)
-        with torch.cuda.device(color.device):
-            _check(_lib().lara_surface_maps_forward_views(n, H, W, color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), rots.data_ptr(),
-                                                          float(depth_ratio), image.data_ptr(), depth.data_ptr(), acc.data_ptr(),
-                                                          rnorm.data_ptr(), dnorm.data_ptr(), rdist.data_ptr(),
-                                                          torch.cuda.current_stream(color.device).cuda_stream),
-                   "lara_surface_maps_forward_views")
+        call("lara_surface_maps_forward_views", color.device, n, H, W, color, allmap, rays, rots, float(depth_ratio), image, depth,
+             acc, rnorm, dnorm, rdist)
         ctx.save_for_backward(color, allmap, rays, rots)
         ctx.depth_ratio = float(depth_ratio)
         ctx.set_materialize_grads(False)     # an output the loss does not read keeps a None gradient (kernel: NULL = zero)
@@ -180,12 +132,8 @@ class _SurfaceMapsViews(torch.autograd.Function):
         # seven planes of d_allmap would be zeros -- None instead, which the rasteriser's backward takes as "colour only"
         d_color = torch.empty_like(color)
         d_allmap = None if all(g is None for g in gs[1:]) else torch.empty_like(allmap)
-        with torch.cuda.device(color.device):
-            _check(_lib().lara_surface_maps_backward_views(n, H, W, color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), rots.data_ptr(),
-                                                           ctx.depth_ratio, *[None if g is None else g.data_ptr() for g in gs],
-                                                           d_color.data_ptr(), None if d_allmap is None else d_allmap.data_ptr(),
-                                                           torch.cuda.current_stream(color.device).cuda_stream),
-                   "lara_surface_maps_backward_views")
+        call("lara_surface_maps_backward_views", color.device, n, H, W, color, allmap, rays, rots, ctx.depth_ratio, *gs, d_color,
+             d_allmap)
         return d_color, d_allmap, None, None, None, None
 
 

@@ -10,31 +10,11 @@ triangles and vertex colours; the post-processing (crop, cluster filter, meshExt
 installed.  No CPU path."""
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from .rasterizer import _check, load_library
-
-_configured = False
-
-
-def _lib():
-    global _configured
-    lib = load_library()
-    if not _configured:
-        vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-        lib.lara_tsdf_integrate.restype = ctypes.c_int
-        lib.lara_tsdf_integrate.argtypes = [i32, ctypes.POINTER(f32 * 3), f32, f32, i32, i32, i32] + [vp] * 9
-        lib.lara_tsdf_integrate_blocks.restype = ctypes.c_int
-        lib.lara_tsdf_integrate_blocks.argtypes = [i32, ctypes.POINTER(f32 * 3), f32, f32, i32, i32, i32, i32] + [vp] * 12
-        lib.lara_tsdf_mesh_count.restype = ctypes.c_int
-        lib.lara_tsdf_mesh_count.argtypes = [i32, ctypes.POINTER(f32 * 3), f32] + [vp] * 6
-        lib.lara_tsdf_mesh_emit.restype = ctypes.c_int
-        lib.lara_tsdf_mesh_emit.argtypes = [i32, ctypes.POINTER(f32 * 3), f32] + [vp] * 10
-        _configured = True
-    return lib
+from ._native import call, host_array, require_device
 
 
 class TSDFVolume:
@@ -52,8 +32,7 @@ class TSDFVolume:
         if self.block_sparse and self.res % self.BLOCK:
             raise RuntimeError("block-sparse volumes need a resolution that is a multiple of 16")
         dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
+        require_device(dev)
         n = self.res ** 3
         self.tsdf = torch.zeros(n, dtype=torch.float32, device=dev)
         self.weight = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -72,7 +51,7 @@ class TSDFVolume:
         if color.shape != (V, H, W, 3) or intrinsics.shape != (V, 4) or extrinsics.shape != (V, 4, 4):
             raise RuntimeError("expected depth [V,H,W], color [V,H,W,3], intrinsics [V,4], extrinsics [V,4,4]")
         depth_trunc = f(depth_trunc).expand(V).contiguous() if torch.as_tensor(depth_trunc).dim() == 0 else f(depth_trunc)
-        origin = (ctypes.c_float * 3)(*self.origin)
+        origin = host_array("f", self.origin)
         if V > 64:          # (the kernels keep a view mask in 64 bits)
             for o in range(0, V, 64):
                 self.integrate(depth[o:o + 64], color[o:o + 64], intrinsics[o:o + 64], extrinsics[o:o + 64], depth_trunc[o:o + 64])
@@ -80,20 +59,12 @@ class TSDFVolume:
         if self.block_sparse:
             c2w = torch.linalg.inv_ex(extrinsics.double())[0].float().contiguous()
             touched = torch.empty(V * self.allocated.numel(), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _check(_lib().lara_tsdf_integrate_blocks(self.res, ctypes.byref(origin), self.voxel_length, self.sdf_trunc, V, H, W, self.stride,
-                                                         depth.data_ptr(), color.data_ptr(), intrinsics.data_ptr(), extrinsics.data_ptr(),
-                                                         c2w.data_ptr(), depth_trunc.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                                         self.rgb.data_ptr(), touched.data_ptr(), self.allocated.data_ptr(),
-                                                         torch.cuda.current_stream(dev).cuda_stream), "lara_tsdf_integrate_blocks")
+            call("lara_tsdf_integrate_blocks", dev, self.res, origin, self.voxel_length, self.sdf_trunc, V, H, W, self.stride, depth,
+                 color, intrinsics, extrinsics, c2w, depth_trunc, self.tsdf, self.weight, self.rgb, touched, self.allocated)
             self.last_touched = touched.view(V, -1)
             return
-        with torch.cuda.device(dev):
-            _check(_lib().lara_tsdf_integrate(self.res, ctypes.byref(origin), self.voxel_length, self.sdf_trunc, V, H, W,
-                                              depth.data_ptr(), color.data_ptr(), intrinsics.data_ptr(), extrinsics.data_ptr(),
-                                              depth_trunc.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                              self.rgb.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                   "lara_tsdf_integrate")
+        call("lara_tsdf_integrate", dev, self.res, origin, self.voxel_length, self.sdf_trunc, V, H, W, depth, color, intrinsics,
+             extrinsics, depth_trunc, self.tsdf, self.weight, self.rgb)
 
     def integrate_render(self, cam, render_pkg, alpha_thres=0.08, depth_trunc=10.0):
         """One rendered view as `MeshExtractor.extract` prepares it (meshExtractor.py:76-108): pinhole intrinsics from
@@ -117,22 +88,19 @@ class TSDFVolume:
         dev, r = self.tsdf.device, self.res
         if r % self.BLOCK:
             raise RuntimeError("mesh extraction needs a resolution that is a multiple of 16")
-        origin = (ctypes.c_float * 3)(*self.origin)
-        alloc = self.allocated.data_ptr() if self.block_sparse else None
+        origin = host_array("f", self.origin)
+        alloc = self.allocated if self.block_sparse else None
         counts = torch.zeros(r ** 3, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(_lib().lara_tsdf_mesh_count(r, ctypes.byref(origin), self.voxel_length, self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                               self.rgb.data_ptr(), alloc, counts.data_ptr(), stream), "lara_tsdf_mesh_count")
+            call("lara_tsdf_mesh_count", dev, r, origin, self.voxel_length, self.tsdf, self.weight, self.rgb, alloc, counts)
             ends = torch.cumsum(counts, 0, dtype=torch.int64)
             T = int(ends[-1])                    # the one host read: the output's size
             verts = torch.empty(T, 3, 3, dtype=torch.float32, device=dev)
             cols = torch.empty(T, 3, 3, dtype=torch.float32, device=dev)
             keys = torch.empty(T, 3, dtype=torch.int64, device=dev)
             if T:
-                _check(_lib().lara_tsdf_mesh_emit(r, ctypes.byref(origin), self.voxel_length, self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                                  self.rgb.data_ptr(), alloc, counts.data_ptr(), ends.data_ptr(), verts.data_ptr(),
-                                                  cols.data_ptr(), keys.data_ptr(), stream), "lara_tsdf_mesh_emit")
+                call("lara_tsdf_mesh_emit", dev, r, origin, self.voxel_length, self.tsdf, self.weight, self.rgb, alloc, counts, ends,
+                     verts, cols, keys)
         if not weld:
             return verts.view(-1, 3), torch.arange(3 * T, device=dev).view(T, 3), cols.view(-1, 3)
         uniq, inverse = torch.unique(keys.view(-1), return_inverse=True)

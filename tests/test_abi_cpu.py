@@ -1,25 +1,237 @@
 """The C-ABI library builds for gfx950 without a GPU, loads, and exports every symbol that
-include/lara2dgs.h declares.  No compute calls here (no GPU)."""
+include/lara2dgs.h declares; the Python copy of the ABI (lara_amd/_native.py) agrees with the headers, function by
+function and struct by struct.  No compute calls here (no GPU)."""
 import ctypes
 import os
 import re
 
 import pytest
 
-from lara_amd import rasterizer
+from lara_amd import _native, rasterizer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# ---- the headers, read as what they are: plain C with one prototype style ----------------------------------------------------
+_C_KINDS = {"int": "i", "int32_t": "i", "uint32_t": "i", "int64_t": "l", "float": "f", "double": "d"}
+_STRUCT_RE = r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;"
+
+
+def _c_kind(decl):
+    """Kind of a C type without its declarator's name: 'p' any pointer or array parameter, 'i' int / int32_t, 'l' int64_t,
+    'f' float, 'd' double; anything else (a struct by value) is returned as written."""
+    decl = " ".join(decl.replace("const", " ").split())
+    return "p" if "*" in decl or "[" in decl else _C_KINDS.get(decl, decl)
+
+
+def header_texts(include_dir=None):
+    include_dir = include_dir or os.path.join(ROOT, "include")
+    texts = {}
+    for hdr in sorted(os.listdir(include_dir)):
+        if hdr.endswith(".h"):
+            text = re.sub(r"/\*.*?\*/", "", open(os.path.join(include_dir, hdr)).read(), flags=re.S)
+            texts[hdr] = re.sub(r"//[^\n]*", "", text)
+    return texts
+
+
+def header_functions(include_dir=None):
+    """{name: (return kind, [parameter kinds])} of every prototype: return 'i' / 'l' / 'z' (const char *)."""
+    out = {}
+    for text in header_texts(include_dir).values():
+        text = re.sub(_STRUCT_RE, "", text, flags=re.S)
+        text = re.sub(r"^\s*#.*$", "", text, flags=re.M).replace('extern "C" {', "")
+        for stmt in text.split(";"):
+            m = re.match(r"[\s}]*((?:const\s+)?\w+[\s*]+)(lara2dgs_\w+|lara_\w+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+            if m is None:
+                assert not re.search(r"\blara\w*\s*\(", stmt), f"a prototype this parser does not read: {stmt!r}"
+                continue
+            ret, name, params = m.group(1), m.group(2), " ".join(m.group(3).split())
+            kinds = []
+            if params not in ("", "void"):
+                for p in params.split(","):
+                    d = re.match(r"(.*?)(\w+)\s*(\[[^\]]*\])?$", p.strip())
+                    kinds.append(_c_kind(d.group(1) + (d.group(3) or "")))
+            assert name not in out, f"{name} is declared twice"
+            out[name] = ("z" if "char" in ret else _c_kind(ret), kinds)
+    return out
+
+
+def header_structs(include_dir=None):
+    """{typedef name: [(field, kind)]}; an array field's kind carries its length, e.g. 'l[4]' (macros resolved)."""
+    out = {}
+    for text in header_texts(include_dir).values():
+        macros = dict(re.findall(r"#define\s+(\w+)\s+\(?(-?\d+)\)?\s", text))
+        for m in re.finditer(_STRUCT_RE, text, flags=re.S):
+            fields = []
+            for stmt in m.group(1).split(";"):
+                names = [d.strip() for d in " ".join(stmt.split()).split(",")]
+                if names == [""]:
+                    continue
+                first = re.match(r"(.*?)(\w+)\s*(?:\[(\w+)\])?$", names[0])
+                base = first.group(1).replace("*", " ")
+                decls = [(first.group(1), first.group(2), first.group(3))]
+                for more in names[1:]:                       # `int64_t a, b, c;`
+                    d = re.match(r"(\**)\s*(\w+)\s*(?:\[(\w+)\])?$", more)
+                    decls.append((base + d.group(1), d.group(2), d.group(3)))
+                for ctype, field, length in decls:
+                    fields.append((field, _c_kind(ctype) + (f"[{int(macros.get(length, length))}]" if length else "")))
+            out[m.group(2)] = fields
+    return out
+
+
+def _ctypes_kind(t):
+    """The same kinds for a ctypes type of the binding."""
+    if isinstance(t, type) and issubclass(t, ctypes.Array):
+        return f"{_ctypes_kind(t._type_)}[{t._length_}]"
+    if isinstance(t, type) and issubclass(t, ctypes.Structure):
+        return {cls: name for name, cls in _native.STRUCTS.items()}[t]
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "contents"):
+        return "p"
+    return {ctypes.c_int: "i", ctypes.c_int32: "i", ctypes.c_int64: "l", ctypes.c_float: "f", ctypes.c_double: "d"}[t]
+
+
 def declared_functions():
-    names = set()
-    for hdr in sorted(os.listdir(os.path.join(ROOT, "include"))):        # every header of the C ABI
-        if not hdr.endswith(".h"):
-            continue
-        text = open(os.path.join(ROOT, "include", hdr)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        names |= set(re.findall(r"\b(lara2dgs_[a-z0-9_]+|lara_[a-z0-9_]+)\s*\(", text))
-    return sorted(names)
+    return sorted(header_functions())
+
+
+def table_mismatches(include_dir=None):
+    """Every disagreement between the signature table and the headers, as text."""
+    declared, bad = header_functions(include_dir), []
+    bad += [f"{n}: declared in a header, no row in the table" for n in sorted(set(declared) - set(_native._SIGS))]
+    bad += [f"{n}: a row in the table, declared in no header" for n in sorted(set(_native._SIGS) - set(declared))]
+    for name in sorted(set(declared) & set(_native._SIGS)):
+        restype, argtypes, _ = _native._SIGS[name]
+        ret = "z" if restype is ctypes.c_char_p else _ctypes_kind(restype)
+        kinds = [_ctypes_kind(t) for t in argtypes]
+        if (ret, kinds) != declared[name]:
+            bad.append(f"{name}: header {declared[name]}, table {(ret, kinds)}")
+    return bad
+
+
+def test_signature_table_equals_the_headers():
+    """Every function the headers declare has a row, every row a declaration, and they agree in the return type and, position by
+    position, in the kind of every parameter (pointer / int32 / int64 / float)."""
+    assert len(header_functions()) == len(_native._SIGS) == 91
+    assert table_mismatches() == []
+
+
+def test_stream_flag_follows_the_prototype():
+    """The helper appends the stream exactly where the prototype ends in `void *stream`."""
+    seen = 0
+    for text in header_texts().values():
+        for name, params in re.findall(r"\b(lara2dgs_\w+|lara_\w+)\s*\(([^()]*)\)\s*;", text):
+            assert _native._SIGS[name][2] == bool(re.search(r"void\s*\*\s*stream\s*$", params)), name
+            seen += 1
+    assert seen == 91
+
+
+def test_a_changed_prototype_fails_the_table_check(tmp_path):
+    """The check has teeth: a header that gains, loses or reorders a parameter disagrees with the table."""
+    import shutil
+    src = open(os.path.join(ROOT, "include", "lara_rays.h")).read()
+    proto = re.search(r"int lara_build_rays_out\((.*?)\);", src, flags=re.S)
+    params = [p.strip() for p in " ".join(proto.group(1).split()).split(",")]
+    variants = {"gains": params[:1] + ["int32_t extra"] + params[1:], "loses": params[:2] + params[3:],
+                "reorders": params[:3] + [params[4], params[3]] + params[5:]}
+    for what, ps in variants.items():
+        inc = tmp_path / what
+        shutil.copytree(os.path.join(ROOT, "include"), inc)
+        (inc / "lara_rays.h").write_text(src.replace(proto.group(0), f"int lara_build_rays_out({', '.join(ps)});"))
+        assert [m for m in table_mismatches(str(inc)) if m.startswith("lara_build_rays_out:")], what
+
+
+def test_struct_mirrors_equal_the_header_structs():
+    """Every struct a header defines is mirrored once, with the header's field names in the header's order and the same kind
+    (and array length) field by field."""
+    structs = header_structs()
+    assert sorted(structs) == sorted(_native.STRUCTS) and len(structs) == 13
+    for name, cls in _native.STRUCTS.items():
+        assert [(f, _ctypes_kind(t)) for f, t in cls._fields_] == structs[name], name
+    assert structs["lara_lpips_net"][1] == ("layers", f"lara_lpips_layer[{_native.LPIPS_MAX_LAYERS}]")
+
+
+def test_a_mistyped_table_row_fails_when_it_is_parsed():
+    for row in ("i lara_x(q)", "i lara_x(s p)", "x lara_x(i)", "i lara_x(i*)", "i lara_x(i) extra", "i lara_x(i)\ni lara_x(i)"):
+        with pytest.raises(ValueError):
+            _native._parse_signatures(row)
+    assert _native._parse_signatures("l lara_x(i*2 View s)")["lara_x"][1:] == (
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_native.View), ctypes.c_void_p], True)
+
+
+# ---- the call helper, against a stand-in library object ---------------------------------------------------------------------
+class _FakeLibrary:
+    """Stands in for the loaded library: records what each function is called with and answers `rc`."""
+
+    def __init__(self, rc=0):
+        self.rc, self.calls = rc, []
+
+    def __getattr__(self, name):
+        if name == "lara2dgs_error_string":
+            return lambda rc: b"invalid argument"
+        if name == "lara2dgs_last_hip_error":
+            return lambda: 7
+        return lambda *a: (self.calls.append((name, a)), self.rc)[1]
+
+
+@pytest.fixture
+def fake_library(monkeypatch):
+    import contextlib
+    import torch
+
+    class FakeStream:
+        cuda_stream = 0x5EED
+
+    lib = _FakeLibrary()
+    lib.entered = []
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: (lib.entered.append(dev), contextlib.nullcontext())[1])
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: FakeStream())
+    monkeypatch.setattr(_native, "_handle", lib)
+    return lib
+
+
+def test_call_passes_tensors_none_and_the_stream(fake_library):
+    import torch
+    t, u = torch.zeros(4), torch.zeros(3, dtype=torch.uint8)
+    view = _native.ImageView()
+    # a prototype that ends in `void *stream`: the stream is appended, the device entered; a tensor arrives as its data_ptr(),
+    # None as NULL, a raw address as it is
+    _native.call("lara2dgs_mark_visible", "dev0", 5, t, None, t.data_ptr() + 8, u)
+    assert fake_library.calls.pop() == ("lara2dgs_mark_visible", (5, t.data_ptr(), None, t.data_ptr() + 8, u.data_ptr(), 0x5EED))
+    assert fake_library.entered == ["dev0"]
+    # one that does not: nothing is appended; ints, floats and struct instances pass through as they are
+    layout = _native.GradLayout()
+    _native.call("lara2dgs_get_grad_layout", None, 1, 2, 3, 4, 5, 6, layout)
+    assert fake_library.calls.pop() == ("lara2dgs_get_grad_layout", (1, 2, 3, 4, 5, 6, layout))
+    _native.call("lara_lpips_forward", "dev0", None, 1, 2, 3, view, view, 2.0, -1.0, t, u)
+    name, args = fake_library.calls.pop()
+    assert args[4] is view and args[6:8] == (2.0, -1.0) and args[-1] == 0x5EED and len(args) == 11
+    # a miscounted argument list never reaches the library
+    with pytest.raises(TypeError, match="lara2dgs_mark_visible takes 6 arguments, got 5"):
+        _native.call("lara2dgs_mark_visible", "dev0", 5, t, None, t)
+    with pytest.raises(TypeError, match="lara2dgs_state_bytes takes 5 arguments, got 6"):
+        _native.query("lara2dgs_state_bytes", 8, 16, 16, 1024, 0, 0)
+    assert fake_library.calls == []
+
+
+def test_call_and_query_raise_with_the_called_functions_own_name(fake_library):
+    import torch
+    fake_library.rc = -1
+    with pytest.raises(RuntimeError, match=r"lara_amd: lara_voxel_rows failed: invalid argument \(hipError 7\)"):
+        _native.call("lara_voxel_rows", "dev0", 1, 4, torch.zeros(1), None, None, 0)
+    with pytest.raises(RuntimeError, match=r"lara_amd: lara_point_feats_workspace_bytes failed: invalid argument \(hipError 7\)"):
+        _native.query("lara_point_feats_workspace_bytes", 4, 8, 8)
+    with pytest.raises(ValueError, match="too small"):
+        _native.query("lara_ms_ssim_workspace_floats", 1, 3, 8, 8, error=ValueError("too small"))
+    fake_library.rc = 4096
+    assert _native.query("lara_point_feats_workspace_bytes", 4, 8, 8) == 4096
+
+
+def test_no_cpu_path_check():
+    import torch
+    for t in (torch.zeros(1), torch.device("cpu")):
+        with pytest.raises(RuntimeError, match=r"tensors must live on an MI355X \(HIP\) device; there is no CPU path"):
+            _native.require_device(t)
+    _native.require_device(torch.device("cuda", 0))
 
 
 def test_header_declares_the_three_reference_entry_points():
@@ -38,10 +250,6 @@ def test_block_save_offsets_follow_the_save_area(hip_lib):
     """lara_groupblock_save_offsets (host code only): eleven increasing, 256-byte aligned offsets inside
     lara_groupblock_save_bytes; a wrong count or an unsupported shape is refused."""
     fn = hip_lib.lara_groupblock_save_offsets
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
-    hip_lib.lara_groupblock_save_bytes.restype = ctypes.c_int64
-    hip_lib.lara_groupblock_save_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
     for scenes, R in ((1, 4), (3, 6), (4, 32)):
         M = scenes * R ** 3
         offs = (ctypes.c_int64 * 11)()

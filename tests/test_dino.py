@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from lara_amd._native import load_library
 from tests.dino_restate import RestatedViT, fixture_grads, load_fixture
 
 
@@ -122,7 +123,7 @@ def test_argument_errors_raise_before_any_launch():
 
 def test_library_refuses_bad_dims(hip_lib):
     from lara_amd import dino
-    lib = dino._lib()
+    lib = load_library()
     ok = dict(N=2, views=1, H=64, W=48, C=128, heads=2, F_=256, depth=2, eps=1e-6, strides=(9216, 0, 3072, 48, 1))
     assert lib.lara_vit_workspace_bytes(ctypes.byref(dino._dims(**ok)), 1) > 0
     assert lib.lara_vit_save_bytes(ctypes.byref(dino._dims(**ok))) > 0

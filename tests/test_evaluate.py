@@ -190,7 +190,8 @@ def test_library_refuses_bad_sizes_before_any_launch(hip_lib):
     """include/lara_eval.h: a side below 11, more than 8 thresholds, a bad mask element size -> LARA2DGS_E_INVALID (the
     argument checks come before any pointer is used)."""
     import ctypes
-    lib = evaluate._lib()
+    from lara_amd._native import load_library
+    lib = load_library()
     v = evaluate._ImgView(4096, 1000, 1, 100, 30, 3, 10)
     d = ctypes.c_void_p(4096)
     thr = (ctypes.c_double * 9)(*[0.1] * 9)

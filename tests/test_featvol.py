@@ -75,8 +75,9 @@ def test_bad_shapes_are_refused():
 
 def test_invalid_arguments_return_error_codes(hip_lib):
     import ctypes
-    from lara_amd.featvol import _Dims, _lib
-    lib = _lib()
+    from lara_amd._native import load_library
+    from lara_amd.featvol import _Dims
+    lib = load_library()
     d = _Dims()
     d.B, d.V, d.C, d.E, d.h, d.w, d.R, d.img_w, d.img_h, d.eps = 1, 4, 768, 32, 32, 32, 16, 512, 512, 1e-6
     assert lib.lara_featvol_workspace_bytes(ctypes.byref(d)) > 0

@@ -58,7 +58,7 @@ def test_forward_and_gradients_against_the_reference():
 @pytest.mark.parametrize("V", [1, 3, 4])
 def test_views_layouts_strides_and_runs_are_bitwise(V):
     from lara_amd.featvol import TOKENS, VOLUME
-    from lara_amd.encoder_train import _lib as enc_lib, _stream
+    from lara_amd._native import current_stream as _stream, load_library as enc_lib
     f, t, batch, fv = _fixture()
     B, Vf, h, w = batch["tar_rays_down"].shape[:4]
     C = t["ln_w"].shape[0]

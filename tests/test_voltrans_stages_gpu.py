@@ -67,6 +67,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from lara_amd._native import load_library
 from oracle import voltrans_bf16 as vb
 from oracle.voltrans_ref import build_modules, restated_block, restated_cond, restated_voltrans
 
@@ -303,11 +304,6 @@ def _s():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _lib():
-    from lara_amd.encoder_train import _lib as lib_
-    return lib_()
-
-
 def _dev_weights(w):
     """the reference's (bf16-valued) fp64 operands -> the device's structs; returns (tensors, weights struct, transposed struct)"""
     from lara_amd.encoder import _BlockWeights
@@ -349,7 +345,7 @@ def device_forward(scenes, R, cond_dim):
     key = (scenes, R, cond_dim)
     if key in _DEVICE:
         return _DEVICE[key]
-    lib = _lib()
+    lib = load_library()
     c = case_inputs(scenes, R, cond_dim)
     w = vb.block_weights(c["m"]["layers"][0], cond_dim, True)
     keep, ws, wt = _dev_weights(w)
@@ -421,7 +417,7 @@ def test_forward_stages_teacher_forced(hip_lib, scenes, R, cond_dim):
     A_conv = 27 * 256 * U * vb.st_conv(xn3.abs(), w["wconv"].abs(), scenes, R)
     check_fp32("x_out", d["x_out"].cpu(), pn + vb.st_conv(xn3, w["wconv"], scenes, R), A_conv + A)
     # the in-place inference entry gives the same bits
-    lib = _lib()
+    lib = load_library()
     xi = d["x"].clone()
     ws = torch.full((int(lib.lara_groupblock_workspace_bytes(scenes, R)),), 0xFF, dtype=torch.uint8, device=DEV)
     assert lib.lara_groupblock_forward(scenes, R, cond_dim, xi.data_ptr(), d["cond"].data_ptr(), ctypes.byref(d["ws"]), ws.data_ptr(), _s()) == 0
@@ -465,7 +461,7 @@ def _run_backward(lib, d, scenes, R, cond_dim, g_in, *, saved=True, dkv=None, ld
 @pytest.mark.gpu
 @pytest.mark.parametrize("scenes,R,cond_dim", CASES)
 def test_block_backward(hip_lib, scenes, R, cond_dim):
-    lib = _lib()
+    lib = load_library()
     d = device_forward(scenes, R, cond_dim)
     c, S = d["c"], d["stages"]
     M = c["M"]
@@ -538,7 +534,7 @@ def test_block_backward(hip_lib, scenes, R, cond_dim):
 @pytest.mark.parametrize("Cout", COUTS)
 @pytest.mark.parametrize("scenes,R,cond_dim", CASES)
 def test_head_forward_and_backward(hip_lib, scenes, R, cond_dim, Cout):
-    lib = _lib()
+    lib = load_library()
     c = case_inputs(scenes, R, cond_dim)
     M = c["M"]
     hw = vb.head_weights(c["m"], Cout, True)

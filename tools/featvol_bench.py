@@ -39,7 +39,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("featvol_bench: needs an MI355X")
     from lara_amd.batch import synthetic_batch
-    from lara_amd.encoder_train import _lib as enc_lib, _stream
+    from lara_amd._native import current_stream as _stream, load_library as enc_lib
     from lara_amd.featvol import TOKENS, FeatureVolume
     from tests.featvol_restate import restated
     dev = torch.device("cuda:0")
