@@ -235,10 +235,11 @@ __global__ void __launch_bounds__(256) zero_strided_kernel(char *__restrict__ ba
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-inline void zero_strided(void *base, int64_t stride, int64_t bytes, int n_views, hipStream_t s) {
+inline int zero_strided(void *base, int64_t stride, int64_t bytes, int n_views, hipStream_t s) {
     const int64_t n = (bytes + 15) / 16;
     const unsigned gx = (unsigned)(n < 256 * 64 ? (n + 255) / 256 : 64);
-    hipLaunchKernelGGL(zero_strided_kernel, dim3(gx ? gx : 1, (unsigned)n_views), dim3(256), 0, s, (char *)base, stride, (bytes + 15) / 16 * 16);
+    L2D_LAUNCH_IN_SCOPE(s, zero_strided_kernel, dim3(gx ? gx : 1, (unsigned)n_views), dim3(256), 0, (char *)base, stride, (bytes + 15) / 16 * 16);
+    return LARA2DGS_OK;
 }
 
 bool strides_ok(const lara2dgs_view &v0, int64_t state_stride, int64_t scratch_stride) {
@@ -306,7 +307,7 @@ static int forward_views_impl(int32_t n_views, const lara2dgs_view *views, const
         sc[i] = carve_scratch(vd[i], (char *)scratch + i * scratch_stride, SL);
         rad[i] = out_radii + (int64_t)i * v0.P;
         if (i == 0)   // the views agree in (P, H, W, capacity): one layout, one strided fill for all of them
-            zero_strided(sc[0].tile_count, scratch_stride, SL.sub_start - SL.tile_count, n_views, caller);
+            L2D_TRY(zero_strided(sc[0].tile_count, scratch_stride, SL.sub_start - SL.tile_count, n_views, caller));
     }
     int rc = LARA2DGS_OK;
     for (int i0 = 0; i0 < n_views && rc == LARA2DGS_OK; i0 += L2D_MAX_VIEWS) {

@@ -46,20 +46,18 @@ int lara_groupattn_forward(int32_t G, int32_t cond_dim, const float *x, const ui
         GemmP p{};
         p.A = cond_bf16; p.W = wkv; p.C = kvf; p.M = G * 4; p.N = 512; p.K = cond_dim;
         // K = cond_dim = 800: deep enough for the LDS-DMA ring (102 -> 77 us)
-        if (launch_gemm_ring<0, 0>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_gemm_ring<0, 0>(p, s));
     }
-    L2D_CHECK_LAUNCH();
     {
         L2D_PROF("ga_fused", s);
         const int units = (G + 3) / 4;
         // the two 256 x 256 weights in fragment order (2 x 128 KB at the start of the workspace): one launch of 64
         // workgroups in front of the step
         unsigned short *wqp = (unsigned short *)workspace, *wop = wqp + 65536;
-        hipLaunchKernelGGL(pack_weight_frag_kernel, dim3(64), dim3(256), 0, s, wq, wqp, wo, wop);
-        hipLaunchKernelGGL(group_attn_fused2_kernel<false>, dim3(units), dim3(64), 0, s, x, ln_weight, ln_bias, eps, wqp, kvf, wop, y, G,
-                           (unsigned short *)nullptr, (unsigned short *)nullptr, (unsigned short *)nullptr);
+        L2D_LAUNCH_IN_SCOPE(s, pack_weight_frag_kernel, dim3(64), dim3(256), 0, wq, wqp, wo, wop);
+        L2D_LAUNCH_IN_SCOPE(s, group_attn_fused2_kernel<false>, dim3(units), dim3(64), 0, x, ln_weight, ln_bias, eps, wqp, kvf, wop, y, G,
+                            (unsigned short *)nullptr, (unsigned short *)nullptr, (unsigned short *)nullptr);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 

@@ -774,24 +774,16 @@ int launch_binning_subset(const ViewDev &v, StateView st, ScratchView sc, hipStr
                           long long coarse_stride, const int32_t *inv) {
     const unsigned nz = (unsigned)vb.n;
     const long long sst = vb.state_stride, qst = vb.scratch_stride;
-    {
-        L2D_PROF("tile_scan", s);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, s, v, sc.tile_count, sc.sub_start,
-                           st.ranges, st.header, st.tile_order, sc.block_tot, st.seg_base, st.seg_cnt, st.bwd_order,
-                           st.bwd_items, sc.sort_parts, sc.sort_items, sst, qst);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tile_scan", s, tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, v, sc.tile_count, sc.sub_start,
+               st.ranges, st.header, st.tile_order, sc.block_tot, st.seg_base, st.seg_cnt, st.bwd_order,
+               st.bwd_items, sc.sort_parts, sc.sort_items, sst, qst);
     if (v.P == 0) return LARA2DGS_OK;
     if (!v.fwd_only) {
         L2D_PROF("subset_pair_base", s);
-        hipLaunchKernelGGL(pair_base_kernel, dim3((v.P + 255) / 256, 1, nz), dim3(256), 0, s, v, sc.rect, sc.block_tot, st.pair_base, sst, qst);
+        L2D_LAUNCH_IN_SCOPE(s, pair_base_kernel, dim3((v.P + 255) / 256, 1, nz), dim3(256), 0, v, sc.rect, sc.block_tot, st.pair_base, sst, qst);
     }
-    {
-        L2D_PROF("subset_compact", s);
-        hipLaunchKernelGGL(subset_compact_kernel, dim3(v.tiles, 1, nz), dim3(256), 0, s, v, st.header, st.ranges, st.point_list,
-                           st.pair_base, st.pair_pos, sst, cst.ranges, cst.point_list, cst.pair_base, cst.pair_pos, coarse_stride, inv);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("subset_compact", s, subset_compact_kernel, dim3(v.tiles, 1, nz), dim3(256), 0, v, st.header, st.ranges, st.point_list,
+               st.pair_base, st.pair_pos, sst, cst.ranges, cst.point_list, cst.pair_base, cst.pair_pos, coarse_stride, inv);
     return LARA2DGS_OK;
 }
 
@@ -799,27 +791,17 @@ int launch_binning(const ViewDev &v, StateView st, ScratchView sc, hipStream_t s
     // the binning of ALL views of the batch in three launches (blockIdx.z = view; st / sc are view 0's)
     const unsigned nz = (unsigned)vb.n;
     const long long sst = vb.state_stride, qst = vb.scratch_stride;
-    {
-        L2D_PROF("tile_scan", s);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, s, v, sc.tile_count, sc.sub_start,
-                           st.ranges, st.header, st.tile_order, sc.block_tot, st.seg_base, st.seg_cnt, st.bwd_order,
-                           st.bwd_items, sc.sort_parts, sc.sort_items, sst, qst);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tile_scan", s, tile_scan_kernel, dim3(v.P > 0 ? 2 : 1, 1, nz), dim3(1024), 0, v, sc.tile_count, sc.sub_start,
+               st.ranges, st.header, st.tile_order, sc.block_tot, st.seg_base, st.seg_cnt, st.bwd_order,
+               st.bwd_items, sc.sort_parts, sc.sort_items, sst, qst);
     if (v.P == 0) return LARA2DGS_OK;
     {
         L2D_PROF("scatter", s);
         const int use_lds = v.tiles <= L2D_LDS_HIST_TILES;
-        hipLaunchKernelGGL(scatter_kernel, dim3((v.P + 255) / 256, 1, nz), dim3(256),
-                           use_lds ? (size_t)v.tiles * 4 : 0, s, v, sc.rect, sc.sub_start, sc.block_tot,
-                           st.pair_base, sc.tile_fill, sc.keys, use_lds, sst, qst);
+        L2D_LAUNCH_IN_SCOPE(s, scatter_kernel, dim3((v.P + 255) / 256, 1, nz), dim3(256), use_lds ? (size_t)v.tiles * 4 : 0, v, sc.rect, sc.sub_start, sc.block_tot,
+                            st.pair_base, sc.tile_fill, sc.keys, use_lds, sst, qst);
     }
-    L2D_CHECK_LAUNCH();
-    {
-        L2D_PROF("tile_sort", s);
-        hipLaunchKernelGGL(tile_sort_kernel, dim3(v.tiles * 2, 1, nz), dim3(512), 0, s, v, st.ranges, st.header, st.tile_order,
-                           sc.keys, st.point_list, sc.rect, st.pair_base, st.pair_pos, sc.sort_parts, sc.sort_items, sst, qst);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tile_sort", s, tile_sort_kernel, dim3(v.tiles * 2, 1, nz), dim3(512), 0, v, st.ranges, st.header, st.tile_order,
+               sc.keys, st.point_list, sc.rect, st.pair_base, st.pair_pos, sc.sort_parts, sc.sort_items, sst, qst);
     return LARA2DGS_OK;
 }

@@ -425,11 +425,8 @@ int lara_coarse_decoder_forward(int32_t M, int32_t K, int32_t sh_dim, const floa
     p.out[0] = offset; p.out[1] = sh; p.out[2] = scaling; p.out[3] = rotation; p.out[4] = opacity;
     p.opacity_shift = opacity_shift; p.scaling_shift = scaling_shift;
     const int trips = (M + CD_PTS - 1) / CD_PTS;
-    {
-        L2D_PROF("coarse_decoder_fwd", (hipStream_t)stream);
-        hipLaunchKernelGGL(coarse_fwd_kernel, dim3(trips < CD_WG_FWD ? trips : CD_WG_FWD), dim3(256), 0, (hipStream_t)stream, p);
-    }
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    L2D_LAUNCH("coarse_decoder_fwd", (hipStream_t)stream, coarse_fwd_kernel, dim3(trips < CD_WG_FWD ? trips : CD_WG_FWD), dim3(256), 0, p);
+    return LARA2DGS_OK;
 }
 
 int lara_coarse_decoder_backward(int32_t M, int32_t K, int32_t sh_dim, const float *x, const float *w1, const float *b1,
@@ -449,11 +446,8 @@ int lara_coarse_decoder_backward(int32_t M, int32_t K, int32_t sh_dim, const flo
     p.xb = xb; p.h1 = h1; p.h2 = h2; p.dz1 = dz1; p.dz2 = dz2; p.dz3 = dz3;
     const int trips = (M + CD_PTS - 1) / CD_PTS;
     const int grid = trips < CD_WG_BWD ? trips : CD_WG_BWD;
-    {
-        L2D_PROF("coarse_decoder_bwd", s);
-        hipLaunchKernelGGL(coarse_bwd_kernel, dim3(grid), dim3(256), 0, s, p);
-    }
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    L2D_LAUNCH("coarse_decoder_bwd", s, coarse_bwd_kernel, dim3(grid), dim3(256), 0, p);
+    return LARA2DGS_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/lara2dgs.h"
+#include "launch.h"
 
 #define TILE 16            // tile edge in pixels: the binning contract (tile ids / ranges are bit-exact)
 #define NEAR_N 0.2f
@@ -88,6 +89,7 @@ struct ScratchView {
 };
 
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }    // align_up(v, 256) on sizes
 
 // Checkpoint rows: the worst case.  A tile of `len` entries has (len - 1) / L2D_SEG interior boundaries, so a frame of
 // D <= cap pairs never needs more than cap / L2D_SEG rows (round 5: the slab used to be half of that, and a frame beyond half
@@ -170,22 +172,3 @@ int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, b
 int launch_selftest_butterfly(const float *in, float *out, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present,
                         hipStream_t s);
-
-void l2d_set_hip_error(hipError_t e);
-
-// optional event bracketing of a launch (see lara2dgs_profile_enable)
-struct L2dProfScope {
-    int slot;
-    hipStream_t s;
-    L2dProfScope(const char *name, hipStream_t stream);
-    ~L2dProfScope();
-};
-#define L2D_PROF(name, stream) L2dProfScope prof_scope__(name, stream)
-#define L2D_CHECK_LAUNCH()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) {                            \
-            l2d_set_hip_error(e__);                         \
-            return LARA2DGS_E_LAUNCH;                       \
-        }                                                   \
-    } while (0)

@@ -32,6 +32,7 @@
 // preprocess_bwd gathers a surfel's rows.  The reference issues one atomic per (pixel, surfel,
 // component).
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -513,10 +514,6 @@ __device__ __forceinline__ float mul_legacy(const float a, const float b) {
     return r;
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_full(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
 // The quad's 2x2 pixels are lanes 0..3 = (x, y) in {(0,0), (1,0), (0,1), (1,1)} of the block.  22 sums over the four lanes
 // land 5-6 per lane (slot float 4 i + lane&3 = r[i]; r[5] in lanes 0, 1 only):
 //
@@ -553,11 +550,11 @@ __device__ __forceinline__ void quad_reduce_scatter(const float dp[3], const flo
     for (int c = 0; c < 3; c++) {
         float d = dp[c];
         asm volatile("" : "+v"(d));      // (left alone, the compiler re-associates dp + dpp(dp) into v_mov 0 + v_mov_dpp + v_fmac)
-        const float t = d + dpp_full<0xB1>(d);           // quad_perm [1,0,3,2]
-        const float tq = q[c] + dpp_full<0xB1>(q[c]);
+        const float t = d + dpp_move<0xB1, 0xf>(d);           // quad_perm [1,0,3,2]
+        const float tq = q[c] + dpp_move<0xB1, 0xf>(q[c]);
         const float mine = k.a1 * t + (k.a2 * d + k.a3 * tq);
         const float send = k.b1 * t + (k.b2 * d + k.b3 * tq);
-        r[c] = mine + dpp_full<0x4E>(send);              // quad_perm [2,3,0,1]
+        r[c] = mine + dpp_move<0x4E, 0xf>(send);              // quad_perm [2,3,0,1]
     }
     // (A DPP instruction's bank_mask cannot replace the selects: a "bank" is four CONSECUTIVE lanes of a row -- a whole quad --, not a
     // lane position inside the quad.  Tried in round 6 with the masks read as lane positions: 374 -> 366 us and wrong sums.  With the
@@ -568,15 +565,15 @@ __device__ __forceinline__ void quad_reduce_scatter(const float dp[3], const flo
     for (int i = 0; i < 5; i++) {
         const float mine = b0 ? h[2 * i + 1] : h[2 * i];
         const float send = b0 ? h[2 * i] : h[2 * i + 1];
-        v1[i] = mine + dpp_full<0xB1>(send);
+        v1[i] = mine + dpp_move<0xB1, 0xf>(send);
     }
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const float mine = b1 ? v1[2 * i + 1] : v1[2 * i];
         const float send = b1 ? v1[2 * i] : v1[2 * i + 1];
-        r[3 + i] = mine + dpp_full<0x4E>(send);
+        r[3 + i] = mine + dpp_move<0x4E, 0xf>(send);
     }
-    r[5] = v1[4] + dpp_full<0x4E>(v1[4]);
+    r[5] = v1[4] + dpp_move<0x4E, 0xf>(v1[4]);
 }
 // the 16-sum form of the colour-only backward: rows 0-2 as above, r[3] = sum h[lane & 3]
 __device__ __forceinline__ void quad_reduce_scatter16(const float dp[3], const float q[3], const float h[4], const QuadCoef &k,
@@ -587,22 +584,22 @@ __device__ __forceinline__ void quad_reduce_scatter16(const float dp[3], const f
         float d = dp[c], qq = q[c];
         asm volatile("" : "+v"(d));
         asm volatile("" : "+v"(qq));     // (q is a product here: left alone it is fused into the sum -- v_mov_dpp + v_fmac, another rounding)
-        const float t = d + dpp_full<0xB1>(d);
-        const float tq = qq + dpp_full<0xB1>(qq);
+        const float t = d + dpp_move<0xB1, 0xf>(d);
+        const float tq = qq + dpp_move<0xB1, 0xf>(qq);
         const float mine = k.a1 * t + (k.a2 * d + k.a3 * tq);
         const float send = k.b1 * t + (k.b2 * d + k.b3 * tq);
-        r[c] = mine + dpp_full<0x4E>(send);
+        r[c] = mine + dpp_move<0x4E, 0xf>(send);
     }
     float v1[2];
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const float mine = b0 ? h[2 * i + 1] : h[2 * i];
         const float send = b0 ? h[2 * i] : h[2 * i + 1];
-        v1[i] = mine + dpp_full<0xB1>(send);
+        v1[i] = mine + dpp_move<0xB1, 0xf>(send);
     }
     const float mine = b1 ? v1[1] : v1[0];
     const float send = b1 ? v1[0] : v1[1];
-    r[3] = mine + dpp_full<0x4E>(send);
+    r[3] = mine + dpp_move<0x4E, 0xf>(send);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1129,7 +1126,7 @@ composite_bwd_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint2
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < NG; k++) g[k] += dpp_full<0xB1>(g[k]);  // the entry's two lanes
+                for (int k = 0; k < NG; k++) g[k] += dpp_move<0xB1, 0xf>(g[k]);  // the entry's two lanes
                 // (colour-only slots: float 4 l + i = lane l's r[i] -- rows 0-2 transposed, (G da, qG2 ddx, qG2 ddy) where the full
                 //  kernel has the dL/dz sums, the colour products and the weight in every lane's last float)
                 const bool touched = (MAPS ? g[21] : g[15]) > 0.f;
@@ -1316,11 +1313,10 @@ int launch_composite_fwd(const ViewDev &v, StateView st, ScratchView sc, float *
     {
         L2D_PROF(v.fwd_only ? "composite_fwd_only" : "composite_fwd", s);
         auto kern = v.fwd_only ? composite_fwd_kernel<false> : composite_fwd_kernel<true>;
-        hipLaunchKernelGGL(kern, dim3(v.tiles, 1, nz), dim3(256), 0, s, v, st.header, st.ranges, st.point_list,
-                           (const float4 *)st.geom, st.tile_order, (const float4 *)st.cullbox, st.final_T, st.n_contrib, st.seg_base,
-                           st.seg_cnt, st.ckpt, st.pair_mask, st.tile_maxc, st.seg_cost, out_color, out_allmap, vb);
+        L2D_LAUNCH_IN_SCOPE(s, kern, dim3(v.tiles, 1, nz), dim3(256), 0, v, st.header, st.ranges, st.point_list,
+                            (const float4 *)st.geom, st.tile_order, (const float4 *)st.cullbox, st.final_T, st.n_contrib, st.seg_base,
+                            st.seg_cnt, st.ckpt, st.pair_mask, st.tile_maxc, st.seg_cost, out_color, out_allmap, vb);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -1329,9 +1325,8 @@ int launch_bwd_order(const ViewDev &v, StateView st, ScratchView sc, hipStream_t
     L2D_PROF("bwd_order", s);
     const int64_t zb = (zero_bytes + 15) / 16 * 16;      // (the region is 256-byte aligned and padded: rounding up stays inside it)
     const unsigned zw = zb > 0 ? (unsigned)((zb / 16 + 8191) / 8192 < 128 ? (zb / 16 + 8191) / 8192 : 128) : 0u;
-    hipLaunchKernelGGL(bwd_order_kernel, dim3(1 + zw, 1, (unsigned)vb.n), dim3(1024), 0, s, v, st.header, st.bwd_items, st.seg_cnt,
-                       st.seg_cost, vb.state_stride, (char *)zero_base, (long long)zb, vb.scratch_stride);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, bwd_order_kernel, dim3(1 + zw, 1, (unsigned)vb.n), dim3(1024), 0, v, st.header, st.bwd_items, st.seg_cnt,
+                        st.seg_cost, vb.state_stride, (char *)zero_base, (long long)zb, vb.scratch_stride);
     return LARA2DGS_OK;
 }
 
@@ -1344,18 +1339,16 @@ int launch_composite_bwd(const ViewDev &v, StateView st, ScratchView sc, const f
         const unsigned grid = (unsigned)v.tiles + v.cap / L2D_SEG;
         // dL_dallmap == NULL: the gradient on the seven maps is zero -> the colour-only kernel
         auto kern = dL_dallmap ? composite_bwd_kernel<true> : composite_bwd_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3(grid, 1, (unsigned)vb.n), dim3(256), 0, s, v, st.header, st.ranges,
-                           st.point_list, (const float4 *)st.geom, st.tile_order,
-                           (const float4 *)st.cullbox, st.final_T, st.n_contrib, st.seg_base, st.seg_cnt, st.bwd_order,
-                           st.bwd_items, st.ckpt, st.pair_mask, st.tile_maxc, dL_dcolor, dL_dallmap, st.pair_pos, sc.pair_grad,
-                           (uint8_t *)sc.pair_valid, vb);
+        L2D_LAUNCH_IN_SCOPE(s, kern, dim3(grid, 1, (unsigned)vb.n), dim3(256), 0, v, st.header, st.ranges,
+                            st.point_list, (const float4 *)st.geom, st.tile_order,
+                            (const float4 *)st.cullbox, st.final_T, st.n_contrib, st.seg_base, st.seg_cnt, st.bwd_order,
+                            st.bwd_items, st.ckpt, st.pair_mask, st.tile_maxc, dL_dcolor, dL_dallmap, st.pair_pos, sc.pair_grad,
+                            (uint8_t *)sc.pair_valid, vb);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
 int launch_selftest_butterfly(const float *in, float *out, hipStream_t s) {
-    hipLaunchKernelGGL(selftest_butterfly_kernel, dim3(1), dim3(64), 0, s, in, out);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, selftest_butterfly_kernel, dim3(1), dim3(64), 0, in, out);
     return LARA2DGS_OK;
 }

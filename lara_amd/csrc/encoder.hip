@@ -67,9 +67,8 @@ int lara_batched_transpose(int32_t batch, int32_t rows, int32_t cols, const floa
     if (batch == 0 || rows == 0 || cols == 0) return LARA2DGS_OK;
     if (!src || !dst) return LARA2DGS_E_INVALID;
     const dim3 grid((cols + 63) / 64, (rows + 63) / 64, batch);
-    if (dst_bf16) hipLaunchKernelGGL(batched_transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, rows, cols);
-    else hipLaunchKernelGGL(batched_transpose_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, rows, cols);
-    L2D_CHECK_LAUNCH();
+    if (dst_bf16) L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, batched_transpose_kernel<true>, grid, dim3(256), 0, src, dst, rows, cols);
+    else L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, batched_transpose_kernel<false>, grid, dim3(256), 0, src, dst, rows, cols);
     return LARA2DGS_OK;
 }
 
@@ -114,39 +113,29 @@ int lara_groupblock_forward(int32_t scenes, int32_t R, int32_t cond_dim, float *
         MlpP p{};
         p.x1 = x; p.x2 = x; p.ln2_w = w->ln2_w; p.ln2_b = w->ln2_b; p.b1 = w->b1; p.b2 = w->b2; p.ln3_w = w->ln3_w; p.ln3_b = w->ln3_b;
         p.w1 = w->w1; p.w2 = w->w2; p.xn3 = xn; p.stats = stats; p.eps = w->eps; p.M = M;
-        if (launch_mlp_fused<0>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_mlp_fused<0>(p, s));
     }
 #else       // (rounds 2-5: four launches; tools/build_variant.sh -DLARA_MLP_UNFUSED for A/B runs)
-    {
-        L2D_PROF("gb_ln2", s);
-        hipLaunchKernelGGL(ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, w->ln2_w, w->ln2_b, w->eps, xn,
-                           (float2 *)nullptr, M);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("gb_ln2", s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, w->ln2_w, w->ln2_b, w->eps, xn,
+               (float2 *)nullptr, M);
     {
         L2D_PROF("gb_mlp1", s);
         GemmP p{};
         p.A = xn; p.W = w->w1; p.C = hid; p.bias = w->b1; p.M = M; p.N = 512; p.K = 256;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 2>), dim3((M + 127) / 128, 4), dim3(256), 0, s, p);
+        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 2>), dim3((M + 127) / 128, 4), dim3(256), 0, p);
     }
-    L2D_CHECK_LAUNCH();
     {
         L2D_PROF("gb_mlp2", s);
         GemmP p{};
         p.A = hid; p.W = w->w2; p.C = x; p.resid = x; p.bias = w->b2; p.M = M; p.N = 256; p.K = 512;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, s, p);
+        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, p);
     }
-    L2D_CHECK_LAUNCH();
     // 3. norm3 + convolution + residual on the normalised activations
-    {
-        L2D_PROF("gb_ln3", s);
-        hipLaunchKernelGGL(ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, w->ln3_w, w->ln3_b, w->eps, xn,
-                           stats, M);
-    }
+    L2D_LAUNCH("gb_ln3", s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, w->ln3_w, w->ln3_b, w->eps, xn,
+               stats, M);
 #endif
-    L2D_CHECK_LAUNCH();
 #ifdef LARA_MLP_UNFUSED
-    if (hipMemsetAsync(zero_row, 0, 512, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+    L2D_HIP(hipMemsetAsync(zero_row, 0, 512, s));
 #endif      // (the fused kernel zero-fills the row behind xn's last: mlp_fused.h)
     {
         L2D_PROF("gb_conv3d", s);
@@ -154,9 +143,8 @@ int lara_groupblock_forward(int32_t scenes, int32_t R, int32_t cond_dim, float *
         p.A = xn; p.W = w->wconv; p.C = x; p.resid = x; p.M = M; p.N = 256; p.K = 27 * 256;
         p.R = R; p.Cin = 256; p.stats = stats; p.gamma = w->ln3_w; p.beta = w->ln3_b;
         p.zero_off = (uint32_t)(zero_row - (char *)xn);
-        if (launch_gemm_ring<1, 4>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_gemm_ring<1, 4>(p, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -170,21 +158,15 @@ int lara_voltrans_head_forward(int32_t scenes, int32_t R, const float *x, const 
     const int M = scenes * R * R * R;
     hipStream_t s = (hipStream_t)stream;
     unsigned short *xn = (unsigned short *)workspace;
-    {
-        L2D_PROF("vt_ln", s);
-        hipLaunchKernelGGL(ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, ln_w, ln_b, eps, xn,
-                           (float2 *)nullptr, M);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("vt_ln", s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, ln_w, ln_b, eps, xn,
+               (float2 *)nullptr, M);
     {
         L2D_PROF("vt_deconv", s);
         GemmP p{};
         p.A = xn; p.W = wdeconv; p.C = out; p.bias = bias; p.M = M; p.N = 8 * Cout; p.K = 256;
         p.R = R; p.Cout = Cout;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 5>), dim3((M + 127) / 128, (8 * Cout + 127) / 128), dim3(256), 0,
-                           s, p);
+        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 5>), dim3((M + 127) / 128, (8 * Cout + 127) / 128), dim3(256), 0, p);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -195,9 +177,8 @@ static int tokens_volume(int32_t scenes, int32_t R, int32_t C, const float *src,
     if (!src || !dst) return LARA2DGS_E_INVALID;
     const int M = scenes * R * R * R;
     const size_t n = (size_t)M * C;
-    hipLaunchKernelGGL(tokens_volume_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, C,
-                       src, dst, M, to_tokens);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, tokens_volume_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, R, C,
+                        src, dst, M, to_tokens);
     return LARA2DGS_OK;
 }
 

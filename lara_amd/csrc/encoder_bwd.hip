@@ -287,7 +287,6 @@ gemm_bf16_tn_lds_kernel(const TnGroup grp) {
 #pragma unroll
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     if (GATHER && nst > 0) table(0);
     if (nst > 0) { issue(0); if (GATHER) table(1); }
     for (int st = 0; st < nst; st++) {
@@ -369,7 +368,6 @@ template <bool GATHER>
 __global__ void __launch_bounds__(512)
 gemm_tn_ring_kernel(const TnRingGroup grp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ring[];  // TR_RING * TR_STAGE bytes
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -807,17 +805,20 @@ ln_bwd_kernel(const void *dy_, const float *__restrict__ x, const float *__restr
             if (skip) kn = ((const float4 *)(skip + (size_t)(tok + 1) * 256))[lane];
         }
         float s = v.x + v.y + v.z + v.w;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         const float mean = s * (1.0f / 256.0f);
         const float c0 = v.x - mean, c1 = v.y - mean, c2 = v.z - mean, c3 = v.w - mean;
         float q = c0 * c0 + c1 * c1 + c2 * c2 + c3 * c3;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
         const float rstd = 1.0f / sqrtf(q * (1.0f / 256.0f) + eps);
         const float h0 = c0 * rstd, h1 = c1 * rstd, h2 = c2 * rstd, h3 = c3 * rstd;
         const float a0 = d.x * g.x, a1 = d.y * g.y, a2 = d.z * g.z, a3 = d.w * g.w;
         float sa = a0 + a1 + a2 + a3, sh = a0 * h0 + a1 * h1 + a2 * h2 + a3 * h3;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sh += __shfl_xor(sh, o, 64); }
         sa *= (1.0f / 256.0f); sh *= (1.0f / 256.0f);
@@ -990,8 +991,6 @@ group_attn_bwd_kernel(const unsigned short *__restrict__ Q, const unsigned short
 // ---- host helpers -------------------------------------------------------------------------------------
 constexpr size_t TN_PART_BYTES = 128ull << 20;  // partial-tile buffer of the weight-gradient GEMMs
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int cu_count() {   // the ring kernels run one workgroup per CU: launches are sized to one round
     static const int cus = [] {
         int dev = 0, v = 0;
@@ -1033,7 +1032,7 @@ int gemm_tn(const unsigned short *A, int lda, int N, const unsigned short *B, in
         const int cus = cu_count();
         static const hipError_t attr = hipFuncSetAttribute((const void *)gemm_tn_ring_kernel<true>,
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, TR_RING * TR_STAGE);
-        if (attr != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(attr);
         const int g128 = M / 128;
         int splits = max(1, min(min(cus / T, g128), (int)(TN_PART_BYTES / out_bytes)));
         const int chunk = ((g128 + splits - 1) / splits) * 128;
@@ -1043,9 +1042,9 @@ int gemm_tn(const unsigned short *A, int lda, int N, const unsigned short *B, in
         q.A = A; q.B = B; q.part = part; q.nbr = nbr; q.M = M; q.lda = lda; q.ldb = ldb; q.T = T; q.ntile = q.ktile = 1; q.Kc = 256;
         q.chunk = chunk; q.splits = splits;
         g.count = 1; g.first_wg[0] = 0; g.first_wg[1] = T * splits;
-        hipLaunchKernelGGL(gemm_tn_ring_kernel<true>, dim3(T * splits), dim3(512), TR_RING * TR_STAGE, s, g);
-        hipLaunchKernelGGL(accum_partials4_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, s, dst, part, n, splits, (size_t)n);
-        return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+        L2D_LAUNCH_IN_SCOPE(s, gemm_tn_ring_kernel<true>, dim3(T * splits), dim3(512), TR_RING * TR_STAGE, g);
+        L2D_LAUNCH_IN_SCOPE(s, accum_partials4_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, dst, part, n, splits, (size_t)n);
+        return LARA2DGS_OK;
     }
     const int tiles = ((N + 127) / 128) * ((Kc + 127) / 128) * T;
     // about 1024 workgroups per launch (4 per CU: one round), in multiples of 8 splits (one per XCD, see the
@@ -1063,19 +1062,19 @@ int gemm_tn(const unsigned short *A, int lda, int N, const unsigned short *B, in
     if (staged) {
         TnGroup g{};
         g.p[0] = p; g.count = 1; g.first_slot[0] = 0; g.first_slot[1] = tiles * splits / 8;
-        if (nbr) hipLaunchKernelGGL((gemm_bf16_tn_lds_kernel<true>), dim3(tiles * splits), dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((gemm_bf16_tn_lds_kernel<false>), dim3(tiles * splits), dim3(256), 0, s, g);
+        if (nbr) L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_tn_lds_kernel<true>), dim3(tiles * splits), dim3(256), 0, g);
+        else L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_tn_lds_kernel<false>), dim3(tiles * splits), dim3(256), 0, g);
     } else {
-        if (nbr) hipLaunchKernelGGL((gemm_bf16_tn_kernel<true>), dim3(tiles * splits), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((gemm_bf16_tn_kernel<false>), dim3(tiles * splits), dim3(256), 0, s, p);
+        if (nbr) L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_tn_kernel<true>), dim3(tiles * splits), dim3(256), 0, p);
+        else L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_tn_kernel<false>), dim3(tiles * splits), dim3(256), 0, p);
     }
     if ((n & 3) == 0 && (((uintptr_t)dst | (uintptr_t)part) & 15) == 0 && (n / 4 + 63) / 64 < 128 && splits >= 64)
-        hipLaunchKernelGGL(accum_partials4_wide_kernel, dim3((n / 4 + 63) / 64), dim3(1024), 0, s, dst, part, n, splits, (size_t)n);
+        L2D_LAUNCH_IN_SCOPE(s, accum_partials4_wide_kernel, dim3((n / 4 + 63) / 64), dim3(1024), 0, dst, part, n, splits, (size_t)n);
     else if ((n & 3) == 0 && (((uintptr_t)dst | (uintptr_t)part) & 15) == 0)
-        hipLaunchKernelGGL(accum_partials4_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, s, dst, part, n, splits, (size_t)n);
+        L2D_LAUNCH_IN_SCOPE(s, accum_partials4_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, dst, part, n, splits, (size_t)n);
     else
-        hipLaunchKernelGGL(accum_partials_kernel, dim3((n + 63) / 64), dim3(256), 0, s, dst, part, n, splits, (size_t)n);
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+        L2D_LAUNCH_IN_SCOPE(s, accum_partials_kernel, dim3((n + 63) / 64), dim3(256), 0, dst, part, n, splits, (size_t)n);
+    return LARA2DGS_OK;
 }
 
 // dst_k[N_k, Kc_k] += A_k^T . B_k for several products that are ready at the same time, as one launch + one reduction launch
@@ -1093,9 +1092,8 @@ int gemm_tn_group(const TnJob *jobs, int count, float *part, hipStream_t s) {
     }
     if (!ok) {
         for (int k = 0; k < count; k++) {
-            const int rc = gemm_tn(jobs[k].A, jobs[k].lda, jobs[k].N, jobs[k].B, jobs[k].ldb, jobs[k].Kc, 1, nullptr, jobs[k].M,
-                                   jobs[k].dst, part, s);
-            if (rc) return rc;
+            L2D_TRY(gemm_tn(jobs[k].A, jobs[k].lda, jobs[k].N, jobs[k].B, jobs[k].ldb, jobs[k].Kc, 1, nullptr, jobs[k].M,
+                                   jobs[k].dst, part, s));
         }
         return LARA2DGS_OK;
     }
@@ -1111,7 +1109,7 @@ int gemm_tn_group(const TnJob *jobs, int count, float *part, hipStream_t s) {
     if (ringable) {
         static const hipError_t attr = hipFuncSetAttribute((const void *)gemm_tn_ring_kernel<false>,
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, TR_RING * TR_STAGE);
-        if (attr != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(attr);
         const int cus = cu_count();
         TnRingGroup g{};
         AccGroup a{};
@@ -1136,9 +1134,9 @@ int gemm_tn_group(const TnJob *jobs, int count, float *part, hipStream_t s) {
             if (wgs <= cus && off_f * 4 <= TN_PART_BYTES) break;
             if (cg > (1 << 20)) return LARA2DGS_E_INVALID;
         }
-        hipLaunchKernelGGL(gemm_tn_ring_kernel<false>, dim3(g.first_wg[count]), dim3(512), TR_RING * TR_STAGE, s, g);
-        hipLaunchKernelGGL(accum_partials4_group_kernel, dim3(a.first_wg[count]), dim3(256), 0, s, a);
-        return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+        L2D_LAUNCH_IN_SCOPE(s, gemm_tn_ring_kernel<false>, dim3(g.first_wg[count]), dim3(512), TR_RING * TR_STAGE, g);
+        L2D_LAUNCH_IN_SCOPE(s, accum_partials4_group_kernel, dim3(a.first_wg[count]), dim3(256), 0, a);
+        return LARA2DGS_OK;
     }
     // about 1280 workgroups (five per CU: the kernel is latency-bound below four), splits in multiples of 8 (one per XCD), at
     // least 256 token rows per split
@@ -1171,9 +1169,9 @@ int gemm_tn_group(const TnJob *jobs, int count, float *part, hipStream_t s) {
         base -= 8;
     }
     if (off_f * 4 > TN_PART_BYTES) return LARA2DGS_E_INVALID;
-    hipLaunchKernelGGL((gemm_bf16_tn_lds_kernel<false>), dim3(g.first_slot[count] * 8), dim3(256), 0, s, g);
-    hipLaunchKernelGGL(accum_partials4_group_kernel, dim3(a.first_wg[count]), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_tn_lds_kernel<false>), dim3(g.first_slot[count] * 8), dim3(256), 0, g);
+    L2D_LAUNCH_IN_SCOPE(s, accum_partials4_group_kernel, dim3(a.first_wg[count]), dim3(256), 0, a);
+    return LARA2DGS_OK;
 }
 
 // LayerNorm backward + the reductions of its partial sums into dgamma, dbeta, dbias (any may be null)
@@ -1192,7 +1190,7 @@ struct RedList {
     }
     int launch(hipStream_t s) {
         if (overflow) return LARA2DGS_E_INVALID;
-        if (g.count) hipLaunchKernelGGL(reduce_group_kernel, dim3(wgs), dim3(1024), 0, s, g);
+        if (g.count) L2D_LAUNCH_IN_SCOPE(s, reduce_group_kernel, dim3(wgs), dim3(1024), 0, g);
         g.count = 0; wgs = 0;
         return LARA2DGS_OK;
     }
@@ -1204,31 +1202,32 @@ int ln_bwd(const void *dy, bool dy_bf16, const float *x, const float *gamma, flo
            unsigned short *dx_bf16, float *dgamma, float *dbeta, float *dbias, float *part, int M, hipStream_t s,
            RedList *later = nullptr) {
     const int blocks = (M + LNB_ROWS - 1) / LNB_ROWS;
-    if (dy_bf16) hipLaunchKernelGGL(ln_bwd_kernel<true>, dim3(blocks), dim3(256), 0, s, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
-    else hipLaunchKernelGGL(ln_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
+    if (dy_bf16) L2D_LAUNCH_IN_SCOPE(s, ln_bwd_kernel<true>, dim3(blocks), dim3(256), 0, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
+    else L2D_LAUNCH_IN_SCOPE(s, ln_bwd_kernel<false>, dim3(blocks), dim3(256), 0, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
     if (later) {
         later->add(dgamma, part, 256, blocks, 768);
         later->add(dbeta, part + 256, 256, blocks, 768);
         later->add(dbias, part + 512, 256, blocks, 768);
     } else {
-        hipLaunchKernelGGL(accum_ln_partials_kernel, dim3(4, 3), dim3(1024), 0, s, dgamma, dbeta, dbias, part, blocks);
+        L2D_LAUNCH_IN_SCOPE(s, accum_ln_partials_kernel, dim3(4, 3), dim3(1024), 0, dgamma, dbeta, dbias, part, blocks);
     }
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    return LARA2DGS_OK;
 }
 
 int colsum_bf16(const unsigned short *src, int rows, int C, float *dst, float *part, hipStream_t s) {
     const int blocks = (rows + 63) / 64;
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3(blocks), dim3(256), 0, s, src, part, rows, C);
-    hipLaunchKernelGGL(accum_partials_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, dst, part, C, blocks, (size_t)C);
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    L2D_LAUNCH_IN_SCOPE(s, colsum_bf16_kernel, dim3(blocks), dim3(256), 0, src, part, rows, C);
+    L2D_LAUNCH_IN_SCOPE(s, accum_partials_kernel, dim3((C + 63) / 64), dim3(1024), 0, dst, part, C, blocks, (size_t)C);
+    return LARA2DGS_OK;
 }
 
 template <int EPI>
-void gemm_nt(const unsigned short *A, const unsigned short *W, void *C, int M, int N, int K, const float *resid,
+int gemm_nt(const unsigned short *A, const unsigned short *W, void *C, int M, int N, int K, const float *resid,
              unsigned short *C2, hipStream_t s, float *colsum = nullptr) {
     GemmP p{};
     p.A = A; p.W = W; p.C = C; p.resid = resid; p.C2 = C2; p.M = M; p.N = N; p.K = K; p.colsum = colsum;
-    hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, EPI>), dim3((M + 127) / 128, (N + 127) / 128), dim3(256), 0, s, p);
+    L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, EPI>), dim3((M + 127) / 128, (N + 127) / 128), dim3(256), 0, p);
+    return LARA2DGS_OK;
 }
 
 // What a block's forward leaves behind for its backward (lara_groupblock_forward_train), in bytes from the
@@ -1286,13 +1285,13 @@ int block_forward_keep(int M, int cond_dim, const float *x_in, const unsigned sh
     {
         GemmP p{};
         p.A = cond_bf16; p.W = w->wkv; p.C = kv; p.M = Mkv; p.N = 512; p.K = cond_dim;
-        if (launch_gemm_ring<0, 0>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_gemm_ring<0, 0>(p, s));
     }
     {
         unsigned short *wqp = (unsigned short *)(save + L.wpack), *wop = wqp + 65536;
-        hipLaunchKernelGGL(pack_weight_frag_kernel, dim3(64), dim3(256), 0, s, w->wq, wqp, w->wo, wop);
-        hipLaunchKernelGGL(group_attn_fused2_kernel<true>, dim3((G + 3) / 4), dim3(64), 0, s, x_in, w->ln1_w, w->ln1_b, w->eps, wqp, kv, wop,
-                           x1, G, xn1, q, o);
+        L2D_LAUNCH_IN_SCOPE(s, pack_weight_frag_kernel, dim3(64), dim3(256), 0, w->wq, wqp, w->wo, wop);
+        L2D_LAUNCH_IN_SCOPE(s, group_attn_fused2_kernel<true>, dim3((G + 3) / 4), dim3(64), 0, x_in, w->ln1_w, w->ln1_b, w->eps, wqp, kv, wop,
+                            x1, G, xn1, q, o);
     }
 #ifndef LARA_MLP_UNFUSED
     (void)lnb;
@@ -1300,27 +1299,27 @@ int block_forward_keep(int M, int cond_dim, const float *x_in, const unsigned sh
         MlpP p{};
         p.x1 = x1; p.x2 = x2; p.ln2_w = w->ln2_w; p.ln2_b = w->ln2_b; p.b1 = w->b1; p.b2 = w->b2; p.ln3_w = w->ln3_w; p.ln3_b = w->ln3_b;
         p.w1 = w->w1; p.w2 = w->w2; p.xn3 = xn3; p.stats = (float2 *)(save + L.stats); p.xn2 = xn2; p.z = z; p.h = h; p.eps = w->eps; p.M = M;
-        if (launch_mlp_fused<1>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_mlp_fused<1>(p, s));
     }
 #else       // (rounds 2-5: four launches; tools/build_variant.sh -DLARA_MLP_UNFUSED for A/B runs)
-    hipLaunchKernelGGL(ln_cast_kernel, dim3(lnb), dim3(256), 0, s, x1, w->ln2_w, w->ln2_b, w->eps, xn2, (float2 *)nullptr, M);
+    L2D_LAUNCH_IN_SCOPE(s, ln_cast_kernel, dim3(lnb), dim3(256), 0, x1, w->ln2_w, w->ln2_b, w->eps, xn2, (float2 *)nullptr, M);
     {
         GemmP p{};
         p.A = xn2; p.W = w->w1; p.C = h; p.C2 = z; p.bias = w->b1; p.M = M; p.N = 512; p.K = 256;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 6>), dim3((M + 127) / 128, 4), dim3(256), 0, s, p);
+        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 6>), dim3((M + 127) / 128, 4), dim3(256), 0, p);
     }
     {
         GemmP p{};
         p.A = h; p.W = w->w2; p.C = x2; p.resid = x1; p.bias = w->b2; p.M = M; p.N = 256; p.K = 512;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, s, p);
+        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, p);
     }
-    hipLaunchKernelGGL(ln_cast_kernel, dim3(lnb), dim3(256), 0, s, x2, w->ln3_w, w->ln3_b, w->eps, xn3,
-                       (float2 *)(save + L.stats), M);
+    L2D_LAUNCH_IN_SCOPE(s, ln_cast_kernel, dim3(lnb), dim3(256), 0, x2, w->ln3_w, w->ln3_b, w->eps, xn3,
+                        (float2 *)(save + L.stats), M);
 #endif
 #ifdef LARA_MLP_UNFUSED
-    if (hipMemsetAsync(xn3 + (size_t)M * 256, 0, 512, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+    L2D_HIP(hipMemsetAsync(xn3 + (size_t)M * 256, 0, 512, s));
 #endif      // (the fused kernel zero-fills row M of xn3: mlp_fused.h)
-    return hipGetLastError() == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    return LARA2DGS_OK;
 }
 
 bool block_weights_ok(const lara_groupblock_weights *w) {
@@ -1362,10 +1361,9 @@ int lara_groupblock_forward_train(int32_t scenes, int32_t R, int32_t cond_dim, c
     hipStream_t s = (hipStream_t)stream;
     const SaveWs L = save_layout(M);
     char *save = (char *)saved;
-    int rc;
     {
         L2D_PROF("gbt_forward", s);
-        if ((rc = block_forward_keep(M, cond_dim, x_in, cond_bf16, w, save, s))) return rc;
+        L2D_TRY(block_forward_keep(M, cond_dim, x_in, cond_bf16, w, save, s));
     }
     {
         L2D_PROF("gb_conv3d", s);
@@ -1373,9 +1371,8 @@ int lara_groupblock_forward_train(int32_t scenes, int32_t R, int32_t cond_dim, c
         p.A = (const unsigned short *)(save + L.xn3); p.W = w->wconv; p.C = x_out; p.resid = (const float *)(save + L.x2);
         p.M = M; p.N = 256; p.K = 27 * 256; p.R = R; p.Cin = 256; p.stats = (const float2 *)(save + L.stats);
         p.gamma = w->ln3_w; p.beta = w->ln3_b; p.zero_off = (uint32_t)((size_t)M * 512);
-        if (launch_gemm_ring<1, 4>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_gemm_ring<1, 4>(p, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -1400,10 +1397,9 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
     const BwdWs L = bwd_layout(M);
     const SaveWs S = save_layout(M);
     char *ws = (char *)workspace;
-    int rc;
     if (!saved) {  // nothing kept from the forward: run it again into our own save area
         L2D_PROF("gbb_recompute", s);
-        if ((rc = block_forward_keep(M, cond_dim, x_in, cond_bf16, w, ws + L.save, s))) return rc;
+        L2D_TRY(block_forward_keep(M, cond_dim, x_in, cond_bf16, w, ws + L.save, s));
     }
     const char *sv = saved ? (const char *)saved : ws + L.save;
     const unsigned short *xn1 = (const unsigned short *)(sv + S.xn1), *q = (const unsigned short *)(sv + S.q);
@@ -1429,15 +1425,14 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
     (void)lnpart;
     int *nbr = (int *)(ws + L.nbr);
     if (!chained) {  // (a chained call finds the zero row, the neighbour table and bf16(g) where the call before left them)
-        if (hipMemsetAsync(gb + (size_t)M * 256, 0, 512, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
-        hipLaunchKernelGGL(neighbour_table_kernel, dim3((M + 255) / 256), dim3(256), 0, s, nbr, M, R, M, 512);
-        hipLaunchKernelGGL(cast_bf16_kernel, dim3((unsigned)(((size_t)M * 64 + 255) / 256)), dim3(256), 0, s, g, gb, (size_t)M * 64);
-        L2D_CHECK_LAUNCH();
+        L2D_HIP(hipMemsetAsync(gb + (size_t)M * 256, 0, 512, s));
+        L2D_LAUNCH_IN_SCOPE(s, neighbour_table_kernel, dim3((M + 255) / 256), dim3(256), 0, nbr, M, R, M, 512);
+        L2D_LAUNCH_IN_SCOPE(s, cast_bf16_kernel, dim3((unsigned)(((size_t)M * 64 + 255) / 256)), dim3(256), 0, g, gb, (size_t)M * 64);
     }
     // ---- x_out = pn + cnn(pn), pn = norm3(x2)  (network.py:94-100) ----
     {
         L2D_PROF("gbb_dw_conv", s);
-        if ((rc = gemm_tn(gb, 256, 256, xn3, 256, 256, 27, nbr, M, dw->wconv, tnpart, s))) return rc;
+        L2D_TRY(gemm_tn(gb, 256, 256, xn3, 256, 256, 27, nbr, M, dw->wconv, tnpart, s));
     }
     // d pn = g + cnn^T(g): the same implicit GEMM with the taps mirrored and in/out swapped; and behind it the backward of
     // pn = norm3(x2) -- in the product's epilogue where the tile holds whole rows (EPI 9, mfma_gemm.h), as a pass of its own otherwise.
@@ -1451,7 +1446,7 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
         if (ring2_shape(p, 1)) {
             L2D_PROF("gbb_dx_conv", s);
             p.C2 = gb3; p.lnx = x2; p.stats = (const float2 *)(sv + S.stats); p.gamma = w->ln3_w; p.colsum = lnp4;
-            if (launch_gemm_ring<1, 9>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+            L2D_HIP(launch_gemm_ring<1, 9>(p, s));
             const int tiles = (M + RT - 1) / RT;
             red.add(dw->ln3_w, lnp4, 256, tiles, 768);
             red.add(dw->ln3_b, lnp4 + 256, 256, tiles, 768);
@@ -1459,13 +1454,12 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
         } else {
             {
                 L2D_PROF("gbb_dx_conv", s);
-                if (launch_gemm_ring<1, 1>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+                L2D_HIP(launch_gemm_ring<1, 1>(p, s));
             }
             L2D_PROF("gbb_ln_bwd", s);
-            if ((rc = ln_bwd(g, false, x2, w->ln3_w, w->eps, nullptr, g, gb3, dw->ln3_w, dw->ln3_b, dw->b2, lnp4, M, s, &red))) return rc;
+            L2D_TRY(ln_bwd(g, false, x2, w->ln3_w, w->eps, nullptr, g, gb3, dw->ln3_w, dw->ln3_b, dw->b2, lnp4, M, s, &red));
         }
     }
-    L2D_CHECK_LAUNCH();
     // ---- x2 = x1 + mlp(norm2(x1)) ----
 #ifndef LARA_MLP_UNFUSED
     {
@@ -1479,47 +1473,46 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
         const int tiles = (M + 127) / 128;
 #ifdef LARA_MLP_BWD_LN
         p.g = g; p.gout = gb2; p.part_ln = lnp4 + 2 * lnset;
-        if (launch_mlp_fused<2>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_mlp_fused<2>(p, s));
         red.add(dw->ln2_w, lnp4 + 2 * lnset, 256, tiles, 768);
         red.add(dw->ln2_b, lnp4 + 2 * lnset + 256, 256, tiles, 768);
 #else
         p.gout = tmpb;
-        if (launch_mlp_fused<3>(p, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_HIP(launch_mlp_fused<3>(p, s));
 #endif
         red.add(dw->b1, lnp4 + lnset, 512, tiles, 512);
     }
 #ifndef LARA_MLP_BWD_LN
     {
         L2D_PROF("gbb_ln_bwd", s);
-        if ((rc = ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red))) return rc;
+        L2D_TRY(ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red));
     }
 #endif
 #else
     {
         L2D_PROF("gbb_dx_mlp", s);
         // dz = (g2 W2) * gelu'(z); its column sums per 128-row tile (= the pieces of db1) come out of the same epilogue
-        gemm_nt<7>(gb3, wt->w2_t, dzb, M, 512, 256, nullptr, z, s, lnp4 + lnset);
+        L2D_TRY(gemm_nt<7>(gb3, wt->w2_t, dzb, M, 512, 256, nullptr, z, s, lnp4 + lnset));
         red.add(dw->b1, lnp4 + lnset, 512, (M + 127) / 128, 512);
-        gemm_nt<0>(dzb, wt->w1_t, tmpb, M, 256, 512, nullptr, nullptr, s);   // bf16: see ln_bwd_kernel
+        L2D_TRY(gemm_nt<0>(dzb, wt->w1_t, tmpb, M, 256, 512, nullptr, nullptr, s));   // bf16: see ln_bwd_kernel
     }
     {
         L2D_PROF("gbb_ln_bwd", s);
-        if ((rc = ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red))) return rc;
+        L2D_TRY(ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red));
     }
 #endif
-    L2D_CHECK_LAUNCH();
     // ---- x1 = x0 + cross_attn(norm1(x0), cond, cond) ----
     {
         L2D_PROF("gbb_dx_attn", s);
-        gemm_nt<0>(gb2, wt->wo_t, dob, M, 256, 256, nullptr, nullptr, s);
-        hipLaunchKernelGGL(group_attn_bwd_kernel, dim3((G + 1) / 2), dim3(256), 0, s, q, kv, dob, dq, dkv, G, ld_dkv);
-        if (!dkv_ext) gemm_nt<1>(dkv, wt->wkv_t, dcond, Mkv, cond_dim, 512, dcond, nullptr, s);
-        gemm_nt<0>(dq, wt->wq_t, tmpb, M, 256, 256, nullptr, nullptr, s);
+        L2D_TRY(gemm_nt<0>(gb2, wt->wo_t, dob, M, 256, 256, nullptr, nullptr, s));
+        L2D_LAUNCH_IN_SCOPE(s, group_attn_bwd_kernel, dim3((G + 1) / 2), dim3(256), 0, q, kv, dob, dq, dkv, G, ld_dkv);
+        if (!dkv_ext) L2D_TRY(gemm_nt<1>(dkv, wt->wkv_t, dcond, Mkv, cond_dim, 512, dcond, nullptr, s));
+        L2D_TRY(gemm_nt<0>(dq, wt->wq_t, tmpb, M, 256, 256, nullptr, nullptr, s));
     }
     {
         L2D_PROF("gbb_ln_bwd", s);
-        if ((rc = ln_bwd(tmpb, true, x_in, w->ln1_w, w->eps, g, g, gb, dw->ln1_w, dw->ln1_b, nullptr, lnp4 + 3 * lnset, M, s, &red))) return rc;
-        if ((rc = red.launch(s))) return rc;      // dgamma / dbeta of the three LayerNorms, b2, b1: eight column reductions, one launch
+        L2D_TRY(ln_bwd(tmpb, true, x_in, w->ln1_w, w->eps, g, g, gb, dw->ln1_w, dw->ln1_b, nullptr, lnp4 + 3 * lnset, M, s, &red));
+        L2D_TRY(red.launch(s));      // dgamma / dbeta of the three LayerNorms, b2, b1: eight column reductions, one launch
     }
     {
         L2D_PROF("gbb_dw_linear", s);      // dW2, dW1, dWo, dWq, dWkv
@@ -1528,9 +1521,8 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
                                {gb2, 256, 256, o, 256, 256, M, dw->wo},
                                {dq, 256, 256, xn1, 256, 256, M, dw->wq},
                                {dkv, ld_dkv, 512, cond_bf16, cond_dim, cond_dim, Mkv, dw->wkv}};
-        if ((rc = gemm_tn_group(jobs, 5, tnpart, s))) return rc;
+        L2D_TRY(gemm_tn_group(jobs, 5, tnpart, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -1558,18 +1550,16 @@ int lara_voltrans_head_backward(int32_t scenes, int32_t R, const float *x, const
     float *tmpf = (float *)(ws + off); off += up256((size_t)M * 1024);
     float *lnpart = (float *)(ws + off); off += up256(((size_t)(M + 63) / 64) * 4 * (size_t)max(768, N8));
     float *tnpart = (float *)(ws + off);
-    int rc;
     L2D_PROF("vtb_head", s);
-    hipLaunchKernelGGL(ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, ln_w, ln_b, eps, xn, (float2 *)nullptr, M);
+    L2D_LAUNCH_IN_SCOPE(s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, ln_w, ln_b, eps, xn, (float2 *)nullptr, M);
     {
         const size_t n = (size_t)M * 2 * Cout;
-        hipLaunchKernelGGL(deconv_grad_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dout, dog, M, R, Cout);
+        L2D_LAUNCH_IN_SCOPE(s, deconv_grad_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dout, dog, M, R, Cout);
     }
-    if ((rc = colsum_bf16(dog, M, N8, d_bias8, lnpart, s))) return rc;
-    if ((rc = gemm_tn(dog, N8, N8, xn, 256, 256, 1, nullptr, M, d_wdeconv, tnpart, s))) return rc;
-    gemm_nt<0>(dog, wdeconv_t, tmpf, M, 256, N8, nullptr, nullptr, s);   // (bf16 rows in the fp32-sized region)
-    if ((rc = ln_bwd(tmpf, true, x, ln_w, eps, nullptr, g, nullptr, d_ln_w, d_ln_b, nullptr, lnpart, M, s))) return rc;
-    L2D_CHECK_LAUNCH();
+    L2D_TRY(colsum_bf16(dog, M, N8, d_bias8, lnpart, s));
+    L2D_TRY(gemm_tn(dog, N8, N8, xn, 256, 256, 1, nullptr, M, d_wdeconv, tnpart, s));
+    L2D_TRY(gemm_nt<0>(dog, wdeconv_t, tmpf, M, 256, N8, nullptr, nullptr, s));   // (bf16 rows in the fp32-sized region)
+    L2D_TRY(ln_bwd(tmpf, true, x, ln_w, eps, nullptr, g, nullptr, d_ln_w, d_ln_b, nullptr, lnpart, M, s));
     return LARA2DGS_OK;
 }
 
@@ -1583,9 +1573,7 @@ int lara_gemm_nt_bf16(int32_t M, int32_t N, int32_t K, const uint16_t *A, const 
     if ((size_t)M * K * 2 >= (1ull << 32) || (size_t)N * K * 2 >= (1ull << 32)) return LARA2DGS_E_INVALID;  // 32-bit operand offsets
     GemmP p{};
     p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K;
-    const hipError_t e = c_fp32 ? launch_gemm_ring<0, 8>(p, (hipStream_t)stream) : launch_gemm_ring<0, 0>(p, (hipStream_t)stream);
-    if (e != hipSuccess) { l2d_set_hip_error(e); return LARA2DGS_E_LAUNCH; }
-    L2D_CHECK_LAUNCH();
+    L2D_HIP(c_fp32 ? launch_gemm_ring<0, 8>(p, (hipStream_t)stream) : launch_gemm_ring<0, 0>(p, (hipStream_t)stream));
     return LARA2DGS_OK;
 }
 
@@ -1609,8 +1597,7 @@ int lara_groupattn_core_backward(int32_t G, const uint16_t *q, const uint16_t *k
     if (G < 0) return LARA2DGS_E_INVALID;
     if (G == 0) return LARA2DGS_OK;
     if (!q || !kv || !d_o || !dq || !dkv) return LARA2DGS_E_INVALID;
-    hipLaunchKernelGGL(group_attn_bwd_kernel, dim3((G + 1) / 2), dim3(256), 0, (hipStream_t)stream, q, kv, d_o, dq, dkv, G, 512);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, group_attn_bwd_kernel, dim3((G + 1) / 2), dim3(256), 0, q, kv, d_o, dq, dkv, G, 512);
     return LARA2DGS_OK;
 }
 

@@ -12,6 +12,7 @@
 // No atomics: a call is bit-reproducible and a scene's row does not depend on the batch it is in.  HBM-bound: the image pass
 // needs 24 bytes per pixel (two images, three floats), the depth pass 9 or 12.
 #include "common.h"
+#include "wave.h"
 #include "../../include/lara_eval.h"
 
 namespace {
@@ -36,17 +37,6 @@ __device__ __forceinline__ int ev_at(const EvView &v, const int n, const int c, 
     int xv = v_base, xr = x - x_of_v_base;
     while (xr >= v.Wv) { xr -= v.Wv; xv++; }
     return n * v.sN + c * v.sC + y * v.sY + xv * v.sV + xr * v.sX;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // partial[(n * tiles + tile) * 4 + {0: sum (x - y)^2 over the owned pixels of all channels, 1 + c: sum of channel c's SSIM map}]
@@ -366,20 +356,19 @@ int lara_eval_scores(int32_t B, int32_t H, int32_t W, const lara_image_view *X, 
         for (int t = 0; t < EV_WIN; t++) { win.w[t] = window11[t]; w1 += (double)window11[t]; }
         const double ws = w1 * w1;
         const EvShift sh{(float)(0.5 * ws), (float)(0.5 * (ws - 1.0)), (float)(0.25 * ws * (ws - 1.0))};
-        hipLaunchKernelGGL(eval_image_kernel, dim3(tx, ty, (unsigned)B), dim3(256), 0, s, ev_from_c(X), ev_from_c(Y), H, W, win, sh,
-                           EV_C1, EV_C2, img_partial);
+        L2D_LAUNCH_IN_SCOPE(s, eval_image_kernel, dim3(tx, ty, (unsigned)B), dim3(256), 0, ev_from_c(X), ev_from_c(Y), H, W, win, sh,
+                            EV_C1, EV_C2, img_partial);
     }
     if (depth) {
         EvDepth p;
         p.V = Vd; p.H = Hd; p.W = Wd; p.pred = depth_pred; p.gt = tar_dep; p.msk = tar_msk; p.msk_bytes = msk_elem_bytes; p.n_thr = n_thr;
         for (int k = 0; k < LARA_EVAL_MAX_THRESHOLDS; k++) p.thr[k] = k < n_thr ? (float)thresholds[k] : 0.0f;
-        hipLaunchKernelGGL(eval_depth_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, s, p, dep_partial);
+        L2D_LAUNCH_IN_SCOPE(s, eval_depth_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, p, dep_partial);
     }
-    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)B), dim3(256), 0, s, image ? (const double *)img_partial : (const double *)nullptr,
-                       tiles, 3.0 * (double)H * (double)W,
-                       image ? 1.0 / ((double)(H - (EV_WIN - 1)) * (double)(W - (EV_WIN - 1))) : 0.0,
-                       depth ? (const double *)dep_partial : (const double *)nullptr, blocks, scores);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, eval_finish_kernel, dim3((unsigned)B), dim3(256), 0, image ? (const double *)img_partial : (const double *)nullptr,
+                        tiles, 3.0 * (double)H * (double)W,
+                        image ? 1.0 / ((double)(H - (EV_WIN - 1)) * (double)(W - (EV_WIN - 1))) : 0.0,
+                        depth ? (const double *)dep_partial : (const double *)nullptr, blocks, scores);
     return LARA2DGS_OK;
 }
 
@@ -397,9 +386,8 @@ int lara_eval_quantize_frames(int32_t n, int32_t H, int32_t W, int64_t pix_sV, i
     const bool vec = W % 4 == 0 && pix_sV % 4 == 0 && pix_sY % 4 == 0 && al(image, 16) && al(rend_normal, 16) && al(acc_map, 16) &&
                      al(frames, 4) && al(normal_frames, 4);
     L2D_PROF("eval_quantize", s);
-    if (vec) hipLaunchKernelGGL(eval_quantize_kernel<4>, dim3((unsigned)((pixels / 4 + 255) / 256)), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(eval_quantize_kernel<1>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, p);
-    L2D_CHECK_LAUNCH();
+    if (vec) L2D_LAUNCH_IN_SCOPE(s, eval_quantize_kernel<4>, dim3((unsigned)((pixels / 4 + 255) / 256)), dim3(256), 0, p);
+    else L2D_LAUNCH_IN_SCOPE(s, eval_quantize_kernel<1>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, p);
     return LARA2DGS_OK;
 }
 

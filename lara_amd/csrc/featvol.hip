@@ -106,12 +106,6 @@ __device__ __forceinline__ void load_x(const FvP &p, const int t, const int lane
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // LayerNorm statistics of the lane's row slice (two passes, as torch's reference does over the row)
 __device__ __forceinline__ void ln_stats(const FvP &p, const int lane, const float (&x)[4][4], float &mean, float &rstd) {
     float s = 0.f;
@@ -172,8 +166,6 @@ __global__ void __launch_bounds__(256) modln_kernel(const FvP p, const unsigned 
         *(float4 *)(y + (size_t)t * p.C + c) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
-
-__device__ __forceinline__ float bfr(const float x) { return bf2f(f2bf(x)); }   // round to bf16
 
 // Feature-map position of grid point s in view (b, v), as the reference computes it under bf16 autocast: the two matmuls of
 // `projection` (network.py:182-187) on bf16 operands with bf16 results (the translation added in fp32), the division and the
@@ -539,9 +531,8 @@ bool channels_last(const FvP &p, const void *x, const void *dx) {
 // act, the Linear's operand and its bf16 product [shift | scale]
 int linear_fwd(const FvP &p, char *ws, const FvWs &L, hipStream_t s) {
     unsigned short *act = (unsigned short *)(ws + L.act), *wk = (unsigned short *)(ws + L.wk);
-    hipLaunchKernelGGL(act_kernel, dim3((p.Tp + 255) / 256), dim3(256), 0, s, p, act);
-    hipLaunchKernelGGL(wprep_kernel, dim3((2 * p.C * FV_KA + 255) / 256), dim3(256), 0, s, p, wk);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, act_kernel, dim3((p.Tp + 255) / 256), dim3(256), 0, p, act);
+    L2D_LAUNCH_IN_SCOPE(s, wprep_kernel, dim3((2 * p.C * FV_KA + 255) / 256), dim3(256), 0, p, wk);
     return lara_gemm_nt_bf16(p.Tp, 2 * p.C, FV_KA, act, wk, ws + L.mod, 0, s);
 }
 
@@ -573,16 +564,15 @@ int lara_featvol_forward(const lara_featvol_dims *d, const float *img_feats, con
     {
         L2D_PROF("featvol_modln", s);
         const unsigned short *mod = (const unsigned short *)(ws + L.mod);
-        if (channels_last(p, img_feats, img_feats)) hipLaunchKernelGGL(modln_kernel<true>, dim3((p.T + 3) / 4), dim3(256), 0, s, p, mod, y);
-        else hipLaunchKernelGGL(modln_kernel<false>, dim3((p.T + 3) / 4), dim3(256), 0, s, p, mod, y);
+        if (channels_last(p, img_feats, img_feats)) L2D_LAUNCH_IN_SCOPE(s, modln_kernel<true>, dim3((p.T + 3) / 4), dim3(256), 0, p, mod, y);
+        else L2D_LAUNCH_IN_SCOPE(s, modln_kernel<false>, dim3((p.T + 3) / 4), dim3(256), 0, p, mod, y);
     }
     {
         L2D_PROF(layout == LARA_FEATVOL_TOKENS ? "featvol_sample_tokens" : "featvol_sample_volume", s);
         const dim3 grid2((p.S + FV_PTS - 1) / FV_PTS, p.B);
-        if (layout == LARA_FEATVOL_TOKENS) hipLaunchKernelGGL(sample_kernel<true>, grid2, dim3(256), 0, s, p, (const float *)y, out);
-        else hipLaunchKernelGGL(sample_kernel<false>, grid2, dim3(256), 0, s, p, (const float *)y, out);
+        if (layout == LARA_FEATVOL_TOKENS) L2D_LAUNCH_IN_SCOPE(s, sample_kernel<true>, grid2, dim3(256), 0, p, (const float *)y, out);
+        else L2D_LAUNCH_IN_SCOPE(s, sample_kernel<false>, grid2, dim3(256), 0, p, (const float *)y, out);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -612,40 +602,34 @@ int lara_featvol_backward(const lara_featvol_dims *d, const float *img_feats, co
     }
     int *bins = (int *)(ws + L.bins);
     int2 *ents = (int2 *)(ws + L.ents);
-    {
-        L2D_PROF("featvol_index", s);
-        hipLaunchKernelGGL(index_kernel, dim3(p.B * p.V), dim3(256), 0, s, p, bins, ents);
-    }
+    L2D_LAUNCH("featvol_index", s, index_kernel, dim3(p.B * p.V), dim3(256), 0, p, bins, ents);
     unsigned short *dmod = (unsigned short *)(ws + L.dmod);
     float *part = (float *)(ws + L.part);
     const int nblk = min(FV_TOK_BLOCKS, (p.T + 3) / 4);
     {
         L2D_PROF("featvol_token_bwd", s);
-        if (p.Tp > p.T && hipMemsetAsync(dmod + (size_t)p.T * 2 * p.C, 0, (size_t)(p.Tp - p.T) * 2 * p.C * 2, s) != hipSuccess)
-            return LARA2DGS_E_LAUNCH;
+        if (p.Tp > p.T) L2D_HIP(hipMemsetAsync(dmod + (size_t)p.T * 2 * p.C, 0, (size_t)(p.Tp - p.T) * 2 * p.C * 2, s));
         const unsigned short *mod = (const unsigned short *)(ws + L.mod);
         if (channels_last(p, img_feats, dx))
-            hipLaunchKernelGGL(token_bwd_kernel<true>, dim3(nblk), dim3(256), 0, s, p, mod, bins, ents, g, dx, dmod, part);
-        else hipLaunchKernelGGL(token_bwd_kernel<false>, dim3(nblk), dim3(256), 0, s, p, mod, bins, ents, g, dx, dmod, part);
+            L2D_LAUNCH_IN_SCOPE(s, token_bwd_kernel<true>, dim3(nblk), dim3(256), 0, p, mod, bins, ents, g, dx, dmod, part);
+        else L2D_LAUNCH_IN_SCOPE(s, token_bwd_kernel<false>, dim3(nblk), dim3(256), 0, p, mod, bins, ents, g, dx, dmod, part);
     }
     {
         L2D_PROF("featvol_param_grads", s);
-        hipLaunchKernelGGL(sum_parts_kernel, dim3((2 * p.C + 255) / 256), dim3(256), 0, s, (const float *)part, nblk, 2 * p.C, d_ln_w,
-                           d_ln_b, p.C);
+        L2D_LAUNCH_IN_SCOPE(s, sum_parts_kernel, dim3((2 * p.C + 255) / 256), dim3(256), 0, (const float *)part, nblk, 2 * p.C, d_ln_w,
+                            d_ln_b, p.C);
         if (d_view_embed && p.E > 0) {
             float *ep = (float *)(ws + L.epart);
-            hipLaunchKernelGGL(embed_part_kernel, dim3(FV_EMB_BLOCKS), dim3(256), 0, s, p, g, ep);
-            hipLaunchKernelGGL(sum_parts_kernel, dim3((p.V * p.E + 255) / 256), dim3(256), 0, s, (const float *)ep, FV_EMB_BLOCKS,
-                               p.V * p.E, d_view_embed, d_view_embed, p.V * p.E);
+            L2D_LAUNCH_IN_SCOPE(s, embed_part_kernel, dim3(FV_EMB_BLOCKS), dim3(256), 0, p, g, ep);
+            L2D_LAUNCH_IN_SCOPE(s, sum_parts_kernel, dim3((p.V * p.E + 255) / 256), dim3(256), 0, (const float *)ep, FV_EMB_BLOCKS,
+                                p.V * p.E, d_view_embed, d_view_embed, p.V * p.E);
         }
         float *prod = (float *)(ws + L.prod);
-        if (hipMemsetAsync(prod, 0, (size_t)2 * p.C * FV_KA * 4, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
-        L2D_CHECK_LAUNCH();
+        L2D_HIP(hipMemsetAsync(prod, 0, (size_t)2 * p.C * FV_KA * 4, s));
         if ((rc = lara_gemm_tn_bf16(p.Tp, 2 * p.C, FV_KA, dmod, (const uint16_t *)(ws + L.act), prod, ws + L.tn, s)) != LARA2DGS_OK)
             return rc;
-        hipLaunchKernelGGL(split_dw_kernel, dim3((2 * p.C * 33 + 255) / 256), dim3(256), 0, s, (const float *)prod, 2 * p.C, d_mlp_w, d_mlp_b);
+        L2D_LAUNCH_IN_SCOPE(s, split_dw_kernel, dim3((2 * p.C * 33 + 255) / 256), dim3(256), 0, (const float *)prod, 2 * p.C, d_mlp_w, d_mlp_b);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 

@@ -2,6 +2,7 @@
 // include/lara_finedec.h for the algebra.  One wave = 32 points; the three folded products run on the matrix cores in fp32
 // with the folded weights (45 KB forward, 83 KB backward) in LDS; workgroups are persistent and walk tiles of 128 points.
 #include "common.h"
+#include "wave.h"
 #include "../../include/lara_finedec.h"
 
 namespace {
@@ -23,8 +24,6 @@ constexpr int FD = 80, NH = 8, CD = 8, NV = 4, HID = 64, SH = 12, TQ = NH * CD; 
 //    half-wave and k = row(tile, r, 1) from the upper one -- register r of every lane, as it stands.  The reduction
 //    index is just walked in that order, and the A operand (the weights, staged in LDS with k as the slow index) is
 //    read at the matching rows.  Nothing is transposed, nothing leaves the registers between the products.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 __device__ __forceinline__ int crow(const int tile, const int r, const int hf) { return tile * 32 + (r >> 2) * 8 + hf * 4 + (r & 3); }
 __device__ __forceinline__ f32x16 mfma2(const float a, const float b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -368,17 +367,13 @@ fine_ln_fwd_kernel(const int n, const float *__restrict__ x_g, const float *__re
 
 // wave-wide sum in six DPP adds; the total lands in lane 63 (the shuffle-based butterfly is six LDS permutes per value:
 // with 160 values per wave the kernel was bound by them)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_term(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
-}
 __device__ __forceinline__ float wave_sum_to_lane63(float x) {
-    x += dpp_term<0xB1, 0xf>(x);    // quad_perm [1,0,3,2]
-    x += dpp_term<0x4E, 0xf>(x);    // quad_perm [2,3,0,1]
-    x += dpp_term<0x141, 0xf>(x);   // row_half_mirror
-    x += dpp_term<0x140, 0xf>(x);   // row_mirror: every lane of a 16-lane row holds the row's sum
-    x += dpp_term<0x142, 0xa>(x);   // row_bcast:15 into rows 1 and 3
-    x += dpp_term<0x143, 0xc>(x);   // row_bcast:31 into rows 2 and 3
+    x += dpp_move<0xB1, 0xf>(x);    // quad_perm [1,0,3,2]
+    x += dpp_move<0x4E, 0xf>(x);    // quad_perm [2,3,0,1]
+    x += dpp_move<0x141, 0xf>(x);   // row_half_mirror
+    x += dpp_move<0x140, 0xf>(x);   // row_mirror: every lane of a 16-lane row holds the row's sum
+    x += dpp_move<0x142, 0xa>(x);   // row_bcast:15 into rows 1 and 3
+    x += dpp_move<0x143, 0xc>(x);   // row_bcast:31 into rows 2 and 3
     return x;
 }
 
@@ -581,11 +576,7 @@ int lara_fine_decoder_forward(int32_t n, const float *xn, const float *pf, const
     if (n == 0) return LARA2DGS_OK;
     if (!xn || !pf || !Wqk || !W1ov || !b1 || !W2 || !b2 || !sh) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("fine_decoder_fwd", s);
-        hipLaunchKernelGGL(fine_decoder_fwd_kernel, dim3(fd_grid(n)), dim3(256), 0, s, n, xn, pf, Wqk, W1ov, b1, W2, b2, sh);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("fine_decoder_fwd", s, fine_decoder_fwd_kernel, dim3(fd_grid(n)), dim3(256), 0, n, xn, pf, Wqk, W1ov, b1, W2, b2, sh);
     return LARA2DGS_OK;
 }
 
@@ -601,14 +592,12 @@ int lara_fine_decoder_backward(int32_t n, const float *xn, const float *pf, cons
         L2D_PROF("fine_decoder_bwd", s);
         static bool lds_set = false;
         if (!lds_set) {     // 83 KB of folded weights (both orientations): beyond the 64 KB a kernel gets without asking
-            if (hipFuncSetAttribute((const void *)fine_decoder_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    L_BWD_END * 4) != hipSuccess) return LARA2DGS_E_LAUNCH;
+            L2D_HIP(hipFuncSetAttribute((const void *)fine_decoder_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L_BWD_END * 4));
             lds_set = true;
         }
-        hipLaunchKernelGGL(fine_decoder_bwd_kernel, dim3(fd_grid(n) < 512u ? fd_grid(n) : 512u), dim3(256), L_BWD_END * 4, s, n, xn, pf,
-                           Wqk, W1ov, b1, W2, b2, d_sh, d_xn, d_pf, U, HID_, DH, DT);
+        L2D_LAUNCH_IN_SCOPE(s, fine_decoder_bwd_kernel, dim3(fd_grid(n) < 512u ? fd_grid(n) : 512u), dim3(256), L_BWD_END * 4, n, xn, pf,
+                            Wqk, W1ov, b1, W2, b2, d_sh, d_xn, d_pf, U, HID_, DH, DT);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -620,18 +609,16 @@ int lara_fine_decoder_wgrad(int32_t n, const float *xn, const float *U, const fl
     if (n < 0 || !out) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
-        hipError_t e = hipMemsetAsync(out, 0, (size_t)FW_OUT * 4, s);
-        if (e != hipSuccess) { l2d_set_hip_error(e); return LARA2DGS_E_LAUNCH; }
+        L2D_HIP(hipMemsetAsync(out, 0, (size_t)FW_OUT * 4, s));
         return LARA2DGS_OK;
     }
     if (!xn || !U || !HID_ || !DH || !DT || !d_sh || !workspace) return LARA2DGS_E_INVALID;
     const int slabs = (n + FW_SLAB - 1) / FW_SLAB;
     {
         L2D_PROF("fine_decoder_wgrad", s);
-        hipLaunchKernelGGL(fine_wgrad_kernel, dim3((unsigned)slabs), dim3(192), 0, s, n, xn, U, HID_, DH, DT, d_sh, (float *)workspace);
-        hipLaunchKernelGGL(fine_wgrad_reduce_kernel, dim3((FW_OUT + 63) / 64), dim3(256), 0, s, (const float *)workspace, slabs, out);
+        L2D_LAUNCH_IN_SCOPE(s, fine_wgrad_kernel, dim3((unsigned)slabs), dim3(192), 0, n, xn, U, HID_, DH, DT, d_sh, (float *)workspace);
+        L2D_LAUNCH_IN_SCOPE(s, fine_wgrad_reduce_kernel, dim3((FW_OUT + 63) / 64), dim3(256), 0, (const float *)workspace, slabs, out);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -643,12 +630,8 @@ int lara_fine_ln_forward(int32_t n, const float *x, const float *gamma, const fl
     if (n == 0) return LARA2DGS_OK;
     if (!x || !gamma || !beta || !xn || !stats) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("fine_ln_fwd", s);
-        hipLaunchKernelGGL(fine_ln_fwd_kernel, dim3((unsigned)lara_fine_ln_blocks(n)), dim3(256), 0, s, n, x, gamma, beta, eps, xn,
-                           (float2 *)stats);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("fine_ln_fwd", s, fine_ln_fwd_kernel, dim3((unsigned)lara_fine_ln_blocks(n)), dim3(256), 0, n, x, gamma, beta, eps, xn,
+               (float2 *)stats);
     return LARA2DGS_OK;
 }
 
@@ -658,12 +641,8 @@ int lara_fine_ln_backward(int32_t n, const float *x, const float *gamma, const f
     if (n == 0) return LARA2DGS_OK;
     if (!x || !gamma || !stats || !d_xn || !d_x || !partials) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("fine_ln_bwd", s);
-        hipLaunchKernelGGL(fine_ln_bwd_kernel, dim3((unsigned)lara_fine_ln_blocks(n)), dim3(256), 0, s, n, x, gamma,
-                           (const float2 *)stats, d_xn, d_x, partials);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("fine_ln_bwd", s, fine_ln_bwd_kernel, dim3((unsigned)lara_fine_ln_blocks(n)), dim3(256), 0, n, x, gamma,
+               (const float2 *)stats, d_xn, d_x, partials);
     return LARA2DGS_OK;
 }
 

@@ -20,17 +20,13 @@ namespace {
 
 // wave-wide sum, the same value in every lane: six DPP adds (the total lands in lane 63) and one v_readlane -- the
 // __shfl_xor butterfly is six LDS permutes per value, and a LayerNorm row needs two of them back to back
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_part(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
-}
 __device__ __forceinline__ float wave_total(float x) {
-    x += dpp_part<0xB1, 0xf>(x);    // quad_perm [1,0,3,2]
-    x += dpp_part<0x4E, 0xf>(x);    // quad_perm [2,3,0,1]
-    x += dpp_part<0x141, 0xf>(x);   // row_half_mirror
-    x += dpp_part<0x140, 0xf>(x);   // row_mirror
-    x += dpp_part<0x142, 0xa>(x);   // row_bcast:15
-    x += dpp_part<0x143, 0xc>(x);   // row_bcast:31
+    x += dpp_move<0xB1, 0xf>(x);    // quad_perm [1,0,3,2]
+    x += dpp_move<0x4E, 0xf>(x);    // quad_perm [2,3,0,1]
+    x += dpp_move<0x141, 0xf>(x);   // row_half_mirror
+    x += dpp_move<0x140, 0xf>(x);   // row_mirror
+    x += dpp_move<0x142, 0xa>(x);   // row_bcast:15
+    x += dpp_move<0x143, 0xc>(x);   // row_bcast:31
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }
 

@@ -50,6 +50,7 @@ loss_terms_kernel(const LsP p, float *__restrict__ partials) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         float v = s[q];
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
         if (lane == 0) red[wave][q] = v;
@@ -131,17 +132,19 @@ int lara_loss_terms_forward(int32_t B, int32_t V, int32_t H, int32_t W, const fl
     if ((rend_normal != nullptr) != (depth_normal != nullptr) || (rend_normal && !acc_map)) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)B * V * H * W;
-    if (n == 0) return hipMemsetAsync(terms, 0, 4 * sizeof(float), s) == hipSuccess ? LARA2DGS_OK : LARA2DGS_E_LAUNCH;
+    if (n == 0) {
+        L2D_HIP(hipMemsetAsync(terms, 0, 4 * sizeof(float), s));
+        return LARA2DGS_OK;
+    }
     if (!tar_rgb || !image) return LARA2DGS_E_INVALID;
     const LsP p{B, V, H, W, n, tar_rgb, image, image_fine, rend_dist, rend_normal, depth_normal, acc_map};
     const int blocks = (int)((n + LS_PIX - 1) / LS_PIX);
     {
         L2D_PROF("loss_terms_fwd", s);
-        hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(256), 0, s, p, partials);
-        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(1024), 0, s, partials, blocks, (float)(1.0 / (3.0 * (double)n)),
-                           (float)(1.0 / (double)n), terms);
+        L2D_LAUNCH_IN_SCOPE(s, loss_terms_kernel, dim3(blocks), dim3(256), 0, p, partials);
+        L2D_LAUNCH_IN_SCOPE(s, loss_reduce_kernel, dim3(1), dim3(1024), 0, partials, blocks, (float)(1.0 / (3.0 * (double)n)),
+                            (float)(1.0 / (double)n), terms);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -158,11 +161,7 @@ int lara_loss_terms_backward(int32_t B, int32_t V, int32_t H, int32_t W, const f
     const LsP p{B, V, H, W, n, tar_rgb, image, image_fine, nullptr, rend_normal, depth_normal, acc_map};
     const LsB o{g_terms, d_image, d_image_fine, d_rend_dist, d_rend_normal, d_depth_normal, (float)(1.0 / (3.0 * (double)n)),
                 (float)(1.0 / (double)n)};
-    {
-        L2D_PROF("loss_terms_bwd", s);
-        hipLaunchKernelGGL(loss_terms_bwd_kernel, dim3((unsigned)((n + LS_PIX - 1) / LS_PIX)), dim3(256), 0, s, p, o);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("loss_terms_bwd", s, loss_terms_bwd_kernel, dim3((unsigned)((n + LS_PIX - 1) / LS_PIX)), dim3(256), 0, p, o);
     return LARA2DGS_OK;
 }
 

@@ -17,12 +17,10 @@
 //   lp_finish_kernel         one workgroup per scene adds the partials of each tap in a fixed order, divides by the pixel count.
 // No atomics: a call is bit-reproducible and a scene's row does not depend on the batch it is in.
 #include "common.h"
+#include "wave.h"
 #include "../../include/lara_lpips.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LP_BM = 128, LP_BK = 32, LP_LD = 36;       // pixel tile, K chunk, LDS row length (floats; 16-byte aligned rows)
 constexpr int LP_CO = 16;                                // output channels per thread of the first-layer kernel
@@ -214,17 +212,6 @@ lp_maxpool_kernel(const float *__restrict__ x, float *__restrict__ y, const int 
     ((float4 *)y)[g] = m;
 }
 
-__device__ __forceinline__ double lp_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float lp_wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // partial[b * gridDim.x + block] = sum over the block's pixels of sum_c lin[c] (f0 / (|f0| + eps) - f1 / (|f1| + eps))^2
 __global__ void __launch_bounds__(256)
 lp_dist_kernel(const float *__restrict__ F, const int B, const long long HW, const int C, const float *__restrict__ lin,
@@ -248,7 +235,7 @@ lp_dist_kernel(const float *__restrict__ F, const int B, const long long HW, con
         }
 #pragma unroll
         for (int j = 0; j < LP_MAXC / 64; j++) { sa = fmaf(a[j], a[j], sa); sc = fmaf(c[j], c[j], sc); }
-        const float na = sqrtf(lp_wave_sum(sa)) + 1e-10f, nc = sqrtf(lp_wave_sum(sc)) + 1e-10f;
+        const float na = sqrtf(wave_sum(sa)) + 1e-10f, nc = sqrtf(wave_sum(sc)) + 1e-10f;
         float t = 0.f;
 #pragma unroll
         for (int j = 0; j < LP_MAXC / 64; j++) {
@@ -257,7 +244,7 @@ lp_dist_kernel(const float *__restrict__ F, const int B, const long long HW, con
         }
         acc += (double)t;
     }
-    acc = lp_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -365,18 +352,21 @@ LpView lp_from_c(const lara_image_view *v) {
     return m;
 }
 
-void lp_launch_mfma(const LpConv &p, hipStream_t s) {
+int lp_launch_mfma(const LpConv &p, hipStream_t s) {
     const long long mt = (p.M + LP_BM - 1) / LP_BM;
-    if (p.Cout % 128 == 0) hipLaunchKernelGGL(lp_conv_mfma_kernel<2>, dim3((unsigned)(mt * (p.Cout / 128))), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(lp_conv_mfma_kernel<1>, dim3((unsigned)(mt * (p.Cout / 64))), dim3(256), 0, s, p);
+    if (p.Cout % 128 == 0) L2D_LAUNCH_IN_SCOPE(s, lp_conv_mfma_kernel<2>, dim3((unsigned)(mt * (p.Cout / 128))), dim3(256), 0, p);
+    else L2D_LAUNCH_IN_SCOPE(s, lp_conv_mfma_kernel<1>, dim3((unsigned)(mt * (p.Cout / 64))), dim3(256), 0, p);
+    return LARA2DGS_OK;
 }
-void lp_launch_image(const LpImage &p, hipStream_t s) {
-    hipLaunchKernelGGL(lp_conv_image_kernel, dim3((unsigned)((p.M + 255) / 256), (unsigned)(p.Cout / LP_CO)), dim3(256), 0, s, p);
+int lp_launch_image(const LpImage &p, hipStream_t s) {
+    L2D_LAUNCH_IN_SCOPE(s, lp_conv_image_kernel, dim3((unsigned)((p.M + 255) / 256), (unsigned)(p.Cout / LP_CO)), dim3(256), 0, p);
+    return LARA2DGS_OK;
 }
-void lp_launch_pool(const float *x, float *y, int N, int H, int W, int C, int k, int st, hipStream_t s) {
+int lp_launch_pool(const float *x, float *y, int N, int H, int W, int C, int k, int st, hipStream_t s) {
     const int Ho = lp_out(H, k, st, 0), Wo = lp_out(W, k, st, 0);
     const long long total = (long long)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(lp_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, H, W, C / 4, Ho, Wo, k, st, total);
+    L2D_LAUNCH_IN_SCOPE(s, lp_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, x, y, H, W, C / 4, Ho, Wo, k, st, total);
+    return LARA2DGS_OK;
 }
 
 }  // namespace
@@ -410,10 +400,10 @@ int lara_lpips_forward(const lara_lpips_net *net, int32_t B, int32_t H, int32_t 
             p.w = L.w; p.bias = L.bias; p.y = buf[cur];
             p.H = H; p.W = W; p.Cout = L.cout; p.Ho = P.out_h[0]; p.Wo = P.out_w[0]; p.k = L.k; p.stride = L.stride; p.pad = L.pad; p.relu = 1;
             p.M = 2ll * B * p.Ho * p.Wo;
-            lp_launch_image(p, s);
+            L2D_TRY(lp_launch_image(p, s));
         } else {
             if (L.pool_k > 0) {
-                lp_launch_pool(buf[cur], buf[cur ^ 1], 2 * B, P.out_h[i - 1], P.out_w[i - 1], L.cin, L.pool_k, L.pool_s, s);
+                L2D_TRY(lp_launch_pool(buf[cur], buf[cur ^ 1], 2 * B, P.out_h[i - 1], P.out_w[i - 1], L.cin, L.pool_k, L.pool_s, s));
                 cur ^= 1;
             }
             LpConv p;
@@ -421,12 +411,12 @@ int lara_lpips_forward(const lara_lpips_net *net, int32_t B, int32_t H, int32_t 
             p.H = P.pool_h[i]; p.W = P.pool_w[i]; p.Cin = L.cin; p.Cout = L.cout; p.Ho = P.out_h[i]; p.Wo = P.out_w[i];
             p.k = L.k; p.stride = L.stride; p.pad = L.pad; p.relu = 1;
             p.M = 2ll * B * p.Ho * p.Wo;
-            lp_launch_mfma(p, s);
+            L2D_TRY(lp_launch_mfma(p, s));
             cur ^= 1;
         }
         if (L.tap) {
-            hipLaunchKernelGGL(lp_dist_kernel, dim3((unsigned)P.tap_blocks[tap], (unsigned)B), dim3(256), 0, s, (const float *)buf[cur], B,
-                               P.tap_pixels[tap], P.tap_c[tap], net->lin[tap], partial + P.part_off[tap]);
+            L2D_LAUNCH_IN_SCOPE(s, lp_dist_kernel, dim3((unsigned)P.tap_blocks[tap], (unsigned)B), dim3(256), 0, (const float *)buf[cur], B,
+                                P.tap_pixels[tap], P.tap_c[tap], net->lin[tap], partial + P.part_off[tap]);
             tap++;
         }
     }
@@ -436,8 +426,7 @@ int lara_lpips_forward(const lara_lpips_net *net, int32_t B, int32_t H, int32_t 
         f.blocks[k] = P.tap_blocks[k];
         f.inv_pixels[k] = 1.0 / (double)P.tap_pixels[k];
     }
-    hipLaunchKernelGGL(lp_finish_kernel, dim3((unsigned)B), dim3(256), 0, s, (const double *)partial, f, scores);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, lp_finish_kernel, dim3((unsigned)B), dim3(256), 0, (const double *)partial, f, scores);
     return LARA2DGS_OK;
 }
 
@@ -459,21 +448,19 @@ int lara_lpips_conv2d(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout
         p.w = w; p.bias = bias; p.y = y;
         p.H = H; p.W = W; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo; p.k = k; p.stride = stride; p.pad = pad; p.relu = relu;
         p.M = M;
-        lp_launch_image(p, s);
+        L2D_TRY(lp_launch_image(p, s));
     } else {
         if (!lp_mfma_ok(Cin, Cout)) return LARA2DGS_E_INVALID;
         const LpConv p{x, w, bias, y, H, W, Cin, Cout, Ho, Wo, k, stride, pad, relu, M};
-        lp_launch_mfma(p, s);
+        L2D_TRY(lp_launch_mfma(p, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
 int lara_lpips_maxpool(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t s, const float *x, float *y, void *stream) {
     if (N <= 0 || C <= 0 || C % 4 != 0 || k <= 0 || s <= 0 || H < k || W < k || !x || !y) return LARA2DGS_E_INVALID;
     L2D_PROF("lpips_maxpool", (hipStream_t)stream);
-    lp_launch_pool(x, y, N, H, W, C, k, s, (hipStream_t)stream);
-    L2D_CHECK_LAUNCH();
+    L2D_TRY(lp_launch_pool(x, y, N, H, W, C, k, s, (hipStream_t)stream));
     return LARA2DGS_OK;
 }
 

@@ -217,12 +217,8 @@ int lara_mesh_crop(int64_t nv, int64_t T, const float *vertices, const int32_t *
     if (T == 0) return LARA2DGS_OK;
     if (!vertices || !triangles || !keep || !err) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("mesh_crop", s);
-        hipLaunchKernelGGL(crop_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, nv, T, vertices, triangles, box[0], box[1], box[2], box[3],
-                           box[4], box[5], keep, err);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("mesh_crop", s, crop_kernel, grid_of(T), dim3(MC_BLOCK), 0, nv, T, vertices, triangles, box[0], box[1], box[2], box[3],
+               box[4], box[5], keep, err);
     return LARA2DGS_OK;
 }
 
@@ -232,12 +228,8 @@ int lara_mesh_compact_rows(int64_t n, int32_t width, const void *src, const int3
     if (n == 0) return LARA2DGS_OK;
     if (!src || !keep || !ends || !dst) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("mesh_compact_rows", s);
-        hipLaunchKernelGGL(compact_kernel, grid_of(n), dim3(MC_BLOCK), 0, s, n, (int)width, (const int32_t *)src, keep, ends,
-                           (int32_t *)dst);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("mesh_compact_rows", s, compact_kernel, grid_of(n), dim3(MC_BLOCK), 0, n, (int)width, (const int32_t *)src, keep, ends,
+               (int32_t *)dst);
     return LARA2DGS_OK;
 }
 
@@ -249,48 +241,27 @@ int lara_mesh_cluster_labels(int64_t T, const int32_t *triangles, int64_t capaci
     if (!triangles || !keys || !owner || !adj || !label || !work) return LARA2DGS_E_INVALID;
     if (capacity < 6 * T || (capacity & (capacity - 1)) || capacity > MAX_ROWS) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(keys, 0xff, (size_t)capacity * sizeof(uint64_t), s) != hipSuccess ||
-        hipMemsetAsync(owner, 0x7f, (size_t)capacity * sizeof(int32_t), s) != hipSuccess ||     // 0x7f7f7f7f > any triangle
-        hipMemsetAsync(work, 0, 2 * sizeof(int32_t), s) != hipSuccess)
-        return LARA2DGS_E_LAUNCH;
-    {
-        L2D_PROF("mesh_edge_insert", s);
-        hipLaunchKernelGGL(edge_insert_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, T, triangles, capacity, keys, owner, adj, label,
-                           work + 1);
-    }
-    L2D_CHECK_LAUNCH();
-    {
-        L2D_PROF("mesh_edge_owner", s);
-        hipLaunchKernelGGL(edge_owner_kernel, grid_of(3 * T), dim3(MC_BLOCK), 0, s, 3 * T, (const int32_t *)owner, adj);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_HIP(hipMemsetAsync(keys, 0xff, (size_t)capacity * sizeof(uint64_t), s));
+    L2D_HIP(hipMemsetAsync(owner, 0x7f, (size_t)capacity * sizeof(int32_t), s));     // 0x7f7f7f7f > any triangle
+    L2D_HIP(hipMemsetAsync(work, 0, 2 * sizeof(int32_t), s));
+    L2D_LAUNCH("mesh_edge_insert", s, edge_insert_kernel, grid_of(T), dim3(MC_BLOCK), 0, T, triangles, capacity, keys, owner, adj, label,
+               work + 1);
+    L2D_LAUNCH("mesh_edge_owner", s, edge_owner_kernel, grid_of(3 * T), dim3(MC_BLOCK), 0, 3 * T, (const int32_t *)owner, adj);
     int log2t = 0;
     while (((int64_t)1 << log2t) < T) log2t++;
     const int max_rounds = 2 * log2t + 8;
     for (int r = 1; r <= max_rounds; r++) {
-        if (hipMemsetAsync(work, 0, sizeof(int32_t), s) != hipSuccess) return LARA2DGS_E_LAUNCH;
-        {
-            L2D_PROF("mesh_hook", s);
-            hipLaunchKernelGGL(hook_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, T, (const int32_t *)adj, label, work);
-        }
-        L2D_CHECK_LAUNCH();
-        {
-            L2D_PROF("mesh_jump", s);
-            hipLaunchKernelGGL(jump_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, T, label, work);
-        }
-        L2D_CHECK_LAUNCH();
+        L2D_HIP(hipMemsetAsync(work, 0, sizeof(int32_t), s));
+        L2D_LAUNCH("mesh_hook", s, hook_kernel, grid_of(T), dim3(MC_BLOCK), 0, T, (const int32_t *)adj, label, work);
+        L2D_LAUNCH("mesh_jump", s, jump_kernel, grid_of(T), dim3(MC_BLOCK), 0, T, label, work);
         int32_t h[2] = {0, 0};          // the round's host read: (changed, error)
-        hipError_t e = hipMemcpyAsync(h, work, sizeof(h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            l2d_set_hip_error(e);
-            return LARA2DGS_E_LAUNCH;
-        }
+        L2D_HIP(hipMemcpyAsync(h, work, sizeof(h), hipMemcpyDeviceToHost, s));
+        L2D_HIP(hipStreamSynchronize(s));
         if (rounds) *rounds = r;
-        if (h[1]) return LARA2DGS_E_LAUNCH;       // a probe sequence ran through the whole table
+        if (h[1]) L2D_FAIL_INTERNAL();            // a probe sequence ran through the whole table
         if (!h[0]) return LARA2DGS_OK;
     }
-    return LARA2DGS_E_LAUNCH;                     // no fixpoint within the round bound
+    L2D_FAIL_INTERNAL();                          // no fixpoint within the round bound
 }
 
 int lara_mesh_cluster_stats(int64_t nv, int64_t T, const float *vertices, const int32_t *triangles, const int32_t *label,
@@ -301,17 +272,9 @@ int lara_mesh_cluster_stats(int64_t nv, int64_t T, const float *vertices, const 
     if (C == 0 || !vertices || !triangles || !label || !root_ends || !clusters || !counts || !area_acc || !area || !err)
         return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("mesh_cluster_stats", s);
-        hipLaunchKernelGGL(stats_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, nv, T, vertices, triangles, label, root_ends, clusters,
-                           (unsigned long long *)counts, (unsigned long long *)area_acc, err);
-    }
-    L2D_CHECK_LAUNCH();
-    {
-        L2D_PROF("mesh_area_finish", s);
-        hipLaunchKernelGGL(area_finish_kernel, grid_of(C), dim3(MC_BLOCK), 0, s, C, (const unsigned long long *)area_acc, area);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("mesh_cluster_stats", s, stats_kernel, grid_of(T), dim3(MC_BLOCK), 0, nv, T, vertices, triangles, label, root_ends, clusters,
+               (unsigned long long *)counts, (unsigned long long *)area_acc, err);
+    L2D_LAUNCH("mesh_area_finish", s, area_finish_kernel, grid_of(C), dim3(MC_BLOCK), 0, C, (const unsigned long long *)area_acc, area);
     return LARA2DGS_OK;
 }
 
@@ -321,12 +284,8 @@ int lara_mesh_keep_clusters(int64_t nv, int64_t T, const int32_t *triangles, con
     if (T == 0) return LARA2DGS_OK;
     if (!triangles || !clusters || !counts || !threshold || !keep || !referenced || !err) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("mesh_keep_clusters", s);
-        hipLaunchKernelGGL(keep_kernel, grid_of(T), dim3(MC_BLOCK), 0, s, nv, T, triangles, clusters, counts, threshold, keep,
-                           referenced, err);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("mesh_keep_clusters", s, keep_kernel, grid_of(T), dim3(MC_BLOCK), 0, nv, T, triangles, clusters, counts, threshold, keep,
+               referenced, err);
     return LARA2DGS_OK;
 }
 
@@ -336,11 +295,7 @@ int lara_mesh_remap(int64_t nv, int64_t T, const int32_t *triangles, const int64
     if (T == 0) return LARA2DGS_OK;
     if (!triangles || !vertex_ends || !out || !err) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("mesh_remap", s);
-        hipLaunchKernelGGL(remap_kernel, grid_of(3 * T), dim3(MC_BLOCK), 0, s, nv, 3 * T, triangles, vertex_ends, out, err);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("mesh_remap", s, remap_kernel, grid_of(3 * T), dim3(MC_BLOCK), 0, nv, 3 * T, triangles, vertex_ends, out, err);
     return LARA2DGS_OK;
 }
 

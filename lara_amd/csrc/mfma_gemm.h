@@ -2,30 +2,9 @@
 // LayerNorm+cast, and an LDS-tiled NT GEMM with fused epilogues / implicit 3x3x3 convolution.
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// fp32 -> bf16, round to nearest even, on gfx950's v_cvt_pk_bf16_f32 (two values per instruction; the integer form
-// u += 0x7fff + ((u >> 16) & 1) >> 16 is three half-rate instructions per value, and a kernel that rounds hundreds of values per lane
-// -- the fused attention step: 512 -- spent 40 % of its vector instructions on it).  Same result for every finite input and inf.
-// (through the compiler's own conversion, not inline asm: an asm statement that reads an MFMA accumulator is invisible to the
-// hazard recognizer -- the first version did exactly that behind the attention's P.V product and produced NaNs)
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned f2bf2(float lo, float hi) {   // bf16(lo) | bf16(hi) << 16
-    const f32x2_t v = {lo, hi};
-    const bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-    unsigned u;
-    __builtin_memcpy(&u, &r, 4);
-    return u;
-}
-__device__ __forceinline__ unsigned short f2bf(float f) { return (unsigned short)f2bf2(f, f); }
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 
 // ---- LayerNorm(C = 256) + bf16 cast: one wave per token, 4 channels per lane ---------------------
 __global__ void __launch_bounds__(256)
@@ -36,11 +15,13 @@ ln_cast_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
     if (tok >= tokens) return;
     const float4 v = ((const float4 *)(x + (size_t)tok * 256))[lane];
     float s = v.x + v.y + v.z + v.w;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
     const float mean = s * (1.0f / 256.0f);
     const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d4 = v.w - mean;
     float q = a * a + b * b + c * c + d4 * d4;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) q += __shfl_xor(q, d, 64);
     const float rstd = 1.0f / sqrtf(q * (1.0f / 256.0f) + eps);
@@ -886,14 +867,10 @@ static inline hipError_t launch_gemm_ring(const GemmP &p, hipStream_t s) {
         static const hipError_t attr2 = hipFuncSetAttribute((const void *)gemm_ring2_kernel<AMODE, EPI>,
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, RING * RTILE);
         if (attr2 != hipSuccess) return attr2;
-        hipLaunchKernelGGL((gemm_ring2_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512),
-                           RING * RTILE, s, p);
-        return hipSuccess;
+        return L2D_LAUNCH_ERR(s, (gemm_ring2_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512), RING * RTILE, p);
     }
     if (EPI == 9) return hipErrorInvalidValue;   // (the fused LayerNorm backward needs gemm_ring2_kernel's shapes: callers check ring2_shape)
-    hipLaunchKernelGGL((gemm_ring_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512),
-                       RING * RTILE, s, p);
-    return hipSuccess;
+    return L2D_LAUNCH_ERR(s, (gemm_ring_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512), RING * RTILE, p);
 }
 static inline bool ring2_shape(const GemmP &p, const int amode) { return p.K % 128 == 0 && (!amode || p.Cin % 128 == 0); }
 

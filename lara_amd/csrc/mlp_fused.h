@@ -184,11 +184,13 @@ mlp_fused_kernel(const MlpP p) {
         for (int i = 0; i < 16; i++) {
             const int tok = wave * 16 + i;
             float s = v[i].x + v[i].y + v[i].z + v[i].w;         // (ln_cast_kernel's arithmetic, operation for operation)
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
             const float mean = s * (1.0f / 256.0f);
             const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d4 = v[i].w - mean;
             float q = a * a + b * b + c * c + d4 * d4;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) q += __shfl_xor(q, d, 64);
             const float rstd = 1.0f / sqrtf(q * (1.0f / 256.0f) + p.eps);
@@ -438,17 +440,20 @@ mlp_fused_kernel(const MlpP p) {
                 const int lrow = wave * 8 + t, row = bm0 + (lrow >> 5) * 64 + i * 32 + (lrow & 31);
                 const float4 v = xv[t], k = kv[t], d = ((const float4 *)(bounce + lrow * 256))[lane];
                 float s = v.x + v.y + v.z + v.w;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
                 const float mean = s * (1.0f / 256.0f);
                 const float c0 = v.x - mean, c1 = v.y - mean, c2 = v.z - mean, c3 = v.w - mean;
                 float q = c0 * c0 + c1 * c1 + c2 * c2 + c3 * c3;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
                 const float rstd = 1.0f / sqrtf(q * (1.0f / 256.0f) + p.eps);
                 const float h0 = c0 * rstd, h1 = c1 * rstd, h2 = c2 * rstd, h3 = c3 * rstd;
                 const float a0 = d.x * gam.x, a1 = d.y * gam.y, a2 = d.z * gam.z, a3 = d.w * gam.w;
                 float sa = a0 + a1 + a2 + a3, sh = a0 * h0 + a1 * h1 + a2 * h2 + a3 * h3;
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sh += __shfl_xor(sh, o, 64); }
                 sa *= (1.0f / 256.0f); sh *= (1.0f / 256.0f);
@@ -562,8 +567,7 @@ static inline hipError_t launch_mlp_fused(const MlpP &p, hipStream_t s) {
     static_assert(MODE < 2 || MF_NW == 8, "the backward's epilogue deals 64-row halves to eight waves");
     static const hipError_t attr = hipFuncSetAttribute((const void *)mlp_fused_kernel<MODE, MF_NW>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((mlp_fused_kernel<MODE, MF_NW>), dim3((p.M + Cfg::TM - 1) / Cfg::TM), dim3(64 * MF_NW), Cfg::LDS, s, p);
-    return hipGetLastError();
+    return L2D_LAUNCH_ERR(s, (mlp_fused_kernel<MODE, MF_NW>), dim3((p.M + Cfg::TM - 1) / Cfg::TM), dim3(64 * MF_NW), Cfg::LDS, p);
 }
 
 }  // namespace

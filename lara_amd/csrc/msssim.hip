@@ -191,6 +191,7 @@ msssim_maps_kernel(const MsView X, const MsView Y, const int C, const int H, con
         }
     }
     if (MODE == 0) {
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) { s_ssim += __shfl_xor(s_ssim, d, 64); s_cs += __shfl_xor(s_cs, d, 64); }
         if ((tid & 63) == 0) { red[0][tid >> 6] = s_ssim; red[1][tid >> 6] = s_cs; }
@@ -212,6 +213,7 @@ msssim_means_kernel(const float *__restrict__ partial, const int tiles, const fl
         a += partial[((size_t)nc * tiles + t) * 2];
         b += partial[((size_t)nc * tiles + t) * 2 + 1];
     }
+// (kept open-coded: through wave_sum this unit's device code comes out different)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
     if (lane == 0) { means[2 * nc] = a * inv_count; means[2 * nc + 1] = b * inv_count; }
@@ -376,19 +378,18 @@ int lara_ms_ssim_forward(int32_t N, int32_t C, int32_t H, int32_t W, const lara_
     for (int l = 0; l < MS_LEVELS; l++) {
         const int Hl = P.H[l], Wl = P.W[l], Hb = Hl - 10, Wb = Wl - 10;
         const dim3 grid((Wb + MS_T - 1) / MS_T, (Hb + MS_T - 1) / MS_T, (unsigned)N);
-        hipLaunchKernelGGL(msssim_maps_kernel<0>, grid, dim3(256), 0, s, xv, yv, C, Hl, Wl, win, MS_C1, MS_C2, workspace + P.partial,
-                           (const float *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL(msssim_means_kernel, dim3(NC), dim3(64), 0, s, workspace + P.partial, (int)(grid.x * grid.y),
-                           1.0f / ((float)Hb * (float)Wb), means + (size_t)l * NC * 2);
+        L2D_LAUNCH_IN_SCOPE(s, msssim_maps_kernel<0>, grid, dim3(256), 0, xv, yv, C, Hl, Wl, win, MS_C1, MS_C2, workspace + P.partial,
+                            (const float *)nullptr, (float *)nullptr);
+        L2D_LAUNCH_IN_SCOPE(s, msssim_means_kernel, dim3(NC), dim3(64), 0, workspace + P.partial, (int)(grid.x * grid.y),
+                            1.0f / ((float)Hb * (float)Wb), means + (size_t)l * NC * 2);
         if (l + 1 < MS_LEVELS) {
             const int Ho = P.H[l + 1], Wo = P.W[l + 1];
-            hipLaunchKernelGGL(msssim_pool_kernel, dim3((Wo + 63) / 64, (Ho + 3) / 4, (unsigned)N), dim3(256), 0, s, xv, yv, C, Hl, Wl, Ho, Wo,
-                               workspace + P.x[l + 1], workspace + P.y[l + 1]);
+            L2D_LAUNCH_IN_SCOPE(s, msssim_pool_kernel, dim3((Wo + 63) / 64, (Ho + 3) / 4, (unsigned)N), dim3(256), 0, xv, yv, C, Hl, Wl, Ho, Wo,
+                                workspace + P.x[l + 1], workspace + P.y[l + 1]);
             xv = planar(workspace + P.x[l + 1], C, Ho, Wo);
             yv = planar(workspace + P.y[l + 1], C, Ho, Wo);
         }
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -408,14 +409,13 @@ int lara_ms_ssim_backward(int32_t N, int32_t C, int32_t H, int32_t W, const lara
         const MsView xv = l ? planar(workspace + P.x[l], C, Hl, Wl) : from_c(X);
         const MsView yv = l ? planar(workspace + P.y[l], C, Hl, Wl) : from_c(Y);
         const MsView dv = l ? planar(workspace + P.dx[l], C, Hl, Wl) : from_c(dX);
-        hipLaunchKernelGGL(msssim_maps_kernel<1>, dim3((Wb + MS_T - 1) / MS_T, (Hb + MS_T - 1) / MS_T, (unsigned)N), dim3(256), 0, s, xv, yv, C,
-                           Hl, Wl, win, MS_C1, MS_C2, (float *)nullptr, d_means + (size_t)l * NC * 2, workspace + P.G);
+        L2D_LAUNCH_IN_SCOPE(s, msssim_maps_kernel<1>, dim3((Wb + MS_T - 1) / MS_T, (Hb + MS_T - 1) / MS_T, (unsigned)N), dim3(256), 0, xv, yv, C,
+                            Hl, Wl, win, MS_C1, MS_C2, (float *)nullptr, d_means + (size_t)l * NC * 2, workspace + P.G);
         const bool has_next = l + 1 < MS_LEVELS;
-        hipLaunchKernelGGL(msssim_back_kernel, dim3((Wl + MS_T - 1) / MS_T, (Hl + MS_T - 1) / MS_T, (unsigned)N), dim3(256), 0, s, xv, yv, dv, C,
-                           Hl, Wl, win, (const float *)(workspace + P.G), has_next ? (const float *)(workspace + P.dx[l + 1]) : (const float *)nullptr,
-                           has_next ? P.H[l + 1] : 0, has_next ? P.W[l + 1] : 0);
+        L2D_LAUNCH_IN_SCOPE(s, msssim_back_kernel, dim3((Wl + MS_T - 1) / MS_T, (Hl + MS_T - 1) / MS_T, (unsigned)N), dim3(256), 0, xv, yv, dv, C,
+                            Hl, Wl, win, (const float *)(workspace + P.G), has_next ? (const float *)(workspace + P.dx[l + 1]) : (const float *)nullptr,
+                            has_next ? P.H[l + 1] : 0, has_next ? P.W[l + 1] : 0);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 

@@ -204,19 +204,22 @@ point_feats_bwd_kernel(const PfP p, const float4 *__restrict__ packed, const flo
 }
 
 template <int VP>
-void launch_fwd(const PfP &p, const float4 *packed, float *out, hipStream_t s) {
+int launch_fwd(const PfP &p, const float4 *packed, float *out, hipStream_t s) {
     const size_t threads = (size_t)p.n * VP;
-    hipLaunchKernelGGL((point_feats_fwd_kernel<VP>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p, packed, out);
+    L2D_LAUNCH_IN_SCOPE(s, (point_feats_fwd_kernel<VP>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p, packed, out);
+    return LARA2DGS_OK;
 }
 template <int VP>
-void launch_bwd(const PfP &p, const float4 *packed, const float *g_out, float *d_points, float *dpacked, hipStream_t s) {
+int launch_bwd(const PfP &p, const float4 *packed, const float *g_out, float *d_points, float *dpacked, hipStream_t s) {
     const size_t threads = (size_t)p.n * VP;
-    hipLaunchKernelGGL((point_feats_bwd_kernel<VP>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p, packed, g_out,
-                       d_points, dpacked);
+    L2D_LAUNCH_IN_SCOPE(s, (point_feats_bwd_kernel<VP>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p, packed, g_out,
+                        d_points, dpacked);
+    return LARA2DGS_OK;
 }
-void launch_pack(const PfP &p, float4 *packed, hipStream_t s) {
+int launch_pack(const PfP &p, float4 *packed, hipStream_t s) {
     const size_t n = (size_t)p.V * p.h * p.w;
-    hipLaunchKernelGGL(pack_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, packed);
+    L2D_LAUNCH_IN_SCOPE(s, pack_stack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p, packed);
+    return LARA2DGS_OK;
 }
 
 // ---- rows of several row-major fp32 tensors through one index list, one thread per (row, float) --------------------------------
@@ -283,10 +286,9 @@ int lara_voxel_rows(int32_t n, int32_t width, const int64_t *vox, const float *s
     const unsigned blocks = (unsigned)(((long long)n * c4 + 255) / 256);
     {
         L2D_PROF(backward ? "voxel_rows_bwd" : "voxel_rows_fwd", s);
-        if (backward) hipLaunchKernelGGL(voxel_rows_bwd_kernel, dim3(blocks), dim3(256), 0, s, n, c4, (const long long *)vox, (const float4 *)src, (float4 *)dst);
-        else hipLaunchKernelGGL(voxel_rows_fwd_kernel, dim3(blocks), dim3(256), 0, s, n, c4, (const long long *)vox, (const float4 *)src, (float4 *)dst);
+        if (backward) L2D_LAUNCH_IN_SCOPE(s, voxel_rows_bwd_kernel, dim3(blocks), dim3(256), 0, n, c4, (const long long *)vox, (const float4 *)src, (float4 *)dst);
+        else L2D_LAUNCH_IN_SCOPE(s, voxel_rows_fwd_kernel, dim3(blocks), dim3(256), 0, n, c4, (const long long *)vox, (const float4 *)src, (float4 *)dst);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -313,16 +315,15 @@ int lara_point_feats_forward_concat(int32_t n, int32_t V, int32_t row_views, int
     float4 *packed = (float4 *)workspace;
     {
         L2D_PROF("point_feats_pack", s);
-        launch_pack(p, packed, s);
+        L2D_TRY(launch_pack(p, packed, s));
     }
     {
         L2D_PROF("point_feats_fwd", s);
-        if (V == 1) launch_fwd<1>(p, packed, out, s);
-        else if (V == 2) launch_fwd<2>(p, packed, out, s);
-        else if (V <= 4) launch_fwd<4>(p, packed, out, s);
-        else launch_fwd<8>(p, packed, out, s);
+        if (V == 1) L2D_TRY(launch_fwd<1>(p, packed, out, s));
+        else if (V == 2) L2D_TRY(launch_fwd<2>(p, packed, out, s));
+        else if (V <= 4) L2D_TRY(launch_fwd<4>(p, packed, out, s));
+        else L2D_TRY(launch_fwd<8>(p, packed, out, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -351,20 +352,19 @@ int lara_point_feats_backward_concat(int32_t n, int32_t V, int32_t row_views, in
     float *dpacked = maps ? (float *)workspace + npix * 8 : nullptr;
     {
         L2D_PROF("point_feats_pack", s);
-        launch_pack(p, packed, s);   // (stateless: the forward's stack is rebuilt rather than kept alive)
-        if (maps && hipMemsetAsync(dpacked, 0, npix * 32, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_TRY(launch_pack(p, packed, s));   // (stateless: the forward's stack is rebuilt rather than kept alive)
+        if (maps) L2D_HIP(hipMemsetAsync(dpacked, 0, npix * 32, s));
     }
     {
         L2D_PROF("point_feats_bwd", s);
-        if (V == 1) launch_bwd<1>(p, packed, g_out, d_points, dpacked, s);
-        else if (V == 2) launch_bwd<2>(p, packed, g_out, d_points, dpacked, s);
-        else if (V <= 4) launch_bwd<4>(p, packed, g_out, d_points, dpacked, s);
-        else launch_bwd<8>(p, packed, g_out, d_points, dpacked, s);
+        if (V == 1) L2D_TRY(launch_bwd<1>(p, packed, g_out, d_points, dpacked, s));
+        else if (V == 2) L2D_TRY(launch_bwd<2>(p, packed, g_out, d_points, dpacked, s));
+        else if (V <= 4) L2D_TRY(launch_bwd<4>(p, packed, g_out, d_points, dpacked, s));
+        else L2D_TRY(launch_bwd<8>(p, packed, g_out, d_points, dpacked, s));
         if (maps)
-            hipLaunchKernelGGL(unpack_grad_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, p, (const float4 *)dpacked, npix,
-                               d_image, d_acc_map, d_depth);
+            L2D_LAUNCH_IN_SCOPE(s, unpack_grad_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, p, (const float4 *)dpacked, npix,
+                                d_image, d_acc_map, d_depth);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -388,10 +388,9 @@ int lara_take_rows(int32_t n, const int64_t *idx, int32_t count, const lara_rows
     const unsigned blocks = (unsigned)(((int64_t)n * total + 255) / 256);
     {
         L2D_PROF(scatter ? "take_rows_bwd" : "take_rows_fwd", s);
-        if (scatter) hipLaunchKernelGGL(take_rows_kernel<true>, dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(take_rows_kernel<false>, dim3(blocks), dim3(256), 0, s, p);
+        if (scatter) L2D_LAUNCH_IN_SCOPE(s, take_rows_kernel<true>, dim3(blocks), dim3(256), 0, p);
+        else L2D_LAUNCH_IN_SCOPE(s, take_rows_kernel<false>, dim3(blocks), dim3(256), 0, p);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 

@@ -674,10 +674,10 @@ int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, b
     const dim3 grid((unsigned)((v.P + 255) / 256) * (unsigned)n), block(256);
     const int use_lds = v.tiles <= L2D_LDS_HIST_TILES;
     const size_t lds_bytes = use_lds ? (size_t)v.tiles * 4 : 0;
-#define L2D_PREV(DEG)                                                                                    \
-    hipLaunchKernelGGL(preprocess_fwd_views_kernel<DEG>, grid, block, lds_bytes, s, v, pv, means3D, shs, \
-                       colors_precomp, opacities, (const float2 *)scales, (const float4 *)rotations,     \
-                       transmat_precomp, use_lds)
+#define L2D_PREV(DEG)                                                                                     \
+    L2D_LAUNCH_IN_SCOPE(s, preprocess_fwd_views_kernel<DEG>, grid, block, lds_bytes, v, pv, means3D, shs, \
+                        colors_precomp, opacities, (const float2 *)scales, (const float4 *)rotations,     \
+                        transmat_precomp, use_lds)
     {
         L2D_PROF(multi ? "preprocess_fwd_views" : "preprocess_fwd", s);
         switch (colors_precomp ? 0 : v.deg) {
@@ -688,16 +688,14 @@ int launch_preprocess_fwd_views(const ViewDev &v, int n, const ViewDev *views, b
         }
     }
 #undef L2D_PREV
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present,
                         hipStream_t s) {
     if (P == 0) return LARA2DGS_OK;
-    hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D,
-                       viewmatrix, present);
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH_IN_SCOPE(s, mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, P, means3D,
+                        viewmatrix, present);
     return LARA2DGS_OK;
 }
 
@@ -718,11 +716,11 @@ int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, b
     }
     const dim3 grid((v.P + 255) / 256), block(256);
     const bool fold = n > 1 || accumulate;
-#define L2D_PREBV(DEG)                                                                                                  \
-    hipLaunchKernelGGL((fold ? preprocess_bwd_views_kernel<DEG, true> : preprocess_bwd_views_kernel<DEG, false>), grid, \
-                       block, 0, s, v, bv, accumulate, means3D, shs, colors_precomp, (const float2 *)scales,            \
-                       (const float4 *)rotations, transmat_precomp, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,      \
-                       dL_dopacities, (float2 *)dL_dscales, (float4 *)dL_drotations, dL_dtransmat)
+#define L2D_PREBV(DEG)                                                                                                      \
+    L2D_LAUNCH_IN_SCOPE(s, (fold ? preprocess_bwd_views_kernel<DEG, true> : preprocess_bwd_views_kernel<DEG, false>), grid, \
+                        block, 0, v, bv, accumulate, means3D, shs, colors_precomp, (const float2 *)scales,                  \
+                        (const float4 *)rotations, transmat_precomp, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors,         \
+                        dL_dopacities, (float2 *)dL_dscales, (float4 *)dL_drotations, dL_dtransmat)
     {
         L2D_PROF(multi ? "preprocess_bwd_views" : "preprocess_bwd", s);
         switch (colors_precomp ? 0 : v.deg) {
@@ -733,6 +731,5 @@ int launch_preprocess_bwd_views(const ViewDev &v, int n, const ViewDev *views, b
         }
     }
 #undef L2D_PREBV
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }

@@ -55,11 +55,7 @@ extern "C" int lara_build_rays_out(int32_t n_views, int32_t Hs, int32_t Ws, floa
     if ((int64_t)Hs * Ws > 0x7fffffff) return LARA2DGS_E_INVALID;
     if (!c2ws || !ixts || !rays || n_views > 65535) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("build_rays", s);
-        hipLaunchKernelGGL(build_rays_kernel, dim3((Hs * Ws + 255) / 256, n_views), dim3(256), 0, s, Hs, Ws, scale,
-                           c2ws, ixts, rays);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("build_rays", s, build_rays_kernel, dim3((Hs * Ws + 255) / 256, n_views), dim3(256), 0, Hs, Ws, scale,
+               c2ws, ixts, rays);
     return LARA2DGS_OK;
 }

@@ -204,12 +204,8 @@ int lara_activate_gaussians_forward(int64_t P, const float *opacity, const float
     if (P == 0) return LARA2DGS_OK;
     if (!opacity || !opacity_out || (scales && !scales_out) || (rotations && !rotations_out)) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("activate_fwd", s);
-        hipLaunchKernelGGL(activate_fwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, opacity, (const float2 *)scales,
-                           (const float4 *)rotations, opacity_out, (float2 *)scales_out, (float4 *)rotations_out);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("activate_fwd", s, activate_fwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, P, opacity, (const float2 *)scales,
+               (const float4 *)rotations, opacity_out, (float2 *)scales_out, (float4 *)rotations_out);
     return LARA2DGS_OK;
 }
 
@@ -220,13 +216,9 @@ int lara_activate_gaussians_backward(int64_t P, const float *opacity_act, const 
     if (P == 0) return LARA2DGS_OK;
     if ((d_opacity && !opacity_act) || (d_scales && !scales_act) || (d_rotations && !rotations)) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    {
-        L2D_PROF("activate_bwd", s);
-        hipLaunchKernelGGL(activate_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, opacity_act,
-                           (const float2 *)scales_act, (const float4 *)rotations, g_opacity, (const float2 *)g_scales,
-                           (const float4 *)g_rotations, d_opacity, (float2 *)d_scales, (float4 *)d_rotations);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("activate_bwd", s, activate_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, P, opacity_act,
+               (const float2 *)scales_act, (const float4 *)rotations, g_opacity, (const float2 *)g_scales,
+               (const float4 *)g_rotations, d_opacity, (float2 *)d_scales, (float4 *)d_rotations);
     return LARA2DGS_OK;
 }
 
@@ -240,12 +232,8 @@ int lara_surface_maps_forward_views(int32_t n_views, int32_t H, int32_t W, const
     hipStream_t s = (hipStream_t)stream;
     SurfP p{H, W, color, allmap, rays, rots, depth_ratio, n_views};
     const size_t HW = (size_t)H * W;
-    {
-        L2D_PROF("surface_fwd", s);
-        hipLaunchKernelGGL(surface_fwd_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n_views), dim3(256), 0, s, p, image, depth,
-                           acc_map, rend_normal, depth_normal, rend_dist);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("surface_fwd", s, surface_fwd_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n_views), dim3(256), 0, p, image, depth,
+               acc_map, rend_normal, depth_normal, rend_dist);
     return LARA2DGS_OK;
 }
 
@@ -260,12 +248,8 @@ int lara_surface_maps_backward_views(int32_t n_views, int32_t H, int32_t W, cons
     hipStream_t s = (hipStream_t)stream;
     SurfP p{H, W, color, allmap, rays, rots, depth_ratio, n_views};
     const size_t HW = (size_t)H * W;
-    {
-        L2D_PROF("surface_bwd", s);
-        hipLaunchKernelGGL(surface_bwd_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n_views), dim3(256), 0, s, p, g_image, g_depth,
-                           g_acc_map, g_rend_normal, g_depth_normal, g_rend_dist, d_color, d_allmap);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("surface_bwd", s, surface_bwd_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n_views), dim3(256), 0, p, g_image, g_depth,
+               g_acc_map, g_rend_normal, g_depth_normal, g_rend_dist, d_color, d_allmap);
     return LARA2DGS_OK;
 }
 

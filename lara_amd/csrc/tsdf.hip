@@ -196,11 +196,7 @@ int lara_tsdf_integrate(int32_t res, const float *origin, float voxel_length, fl
     const int64_t nvox = (int64_t)res * res * res;
     const TsdfP p{res, origin[0], origin[1], origin[2], voxel_length, sdf_trunc, n_views, H, W, depth, color, intrinsics, extrinsics,
                   depth_trunc, tsdf, weight, rgb};
-    {
-        L2D_PROF("tsdf_integrate", s);
-        hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, s, p);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tsdf_integrate", s, tsdf_integrate_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, p);
     return LARA2DGS_OK;
 }
 
@@ -220,18 +216,11 @@ int lara_tsdf_integrate_blocks(int32_t res, const float *origin, float voxel_len
     const size_t nb3 = (size_t)nb * nb * nb;
     const TsdfP p{res, origin[0], origin[1], origin[2], voxel_length, sdf_trunc, n_views, H, W, depth, color, intrinsics, extrinsics,
                   depth_trunc, tsdf, weight, rgb};
-    if (hipMemsetAsync(touched, 0, nb3 * n_views, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
-    {
-        L2D_PROF("tsdf_touch", s);
-        const int samples = ((H + depth_sampling_stride - 1) / depth_sampling_stride) * ((W + depth_sampling_stride - 1) / depth_sampling_stride);
-        hipLaunchKernelGGL(tsdf_touch_kernel, dim3((unsigned)((samples + 255) / 256), (unsigned)n_views), dim3(256), 0, s, p,
-                           depth_sampling_stride, cam_to_world, touched);
-    }
-    {
-        L2D_PROF("tsdf_integrate_blocks", s);
-        hipLaunchKernelGGL(tsdf_integrate_blocks_kernel, dim3((unsigned)(nb3 * (TB * TB * TB / 256))), dim3(256), 0, s, p, touched, allocated);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_HIP(hipMemsetAsync(touched, 0, nb3 * n_views, s));
+    const int samples = ((H + depth_sampling_stride - 1) / depth_sampling_stride) * ((W + depth_sampling_stride - 1) / depth_sampling_stride);
+    L2D_LAUNCH("tsdf_touch", s, tsdf_touch_kernel, dim3((unsigned)((samples + 255) / 256), (unsigned)n_views), dim3(256), 0, p,
+               depth_sampling_stride, cam_to_world, touched);
+    L2D_LAUNCH("tsdf_integrate_blocks", s, tsdf_integrate_blocks_kernel, dim3((unsigned)(nb3 * (TB * TB * TB / 256))), dim3(256), 0, p, touched, allocated);
     return LARA2DGS_OK;
 }
 
@@ -239,12 +228,12 @@ static int mc_params(int32_t res, const float *origin, float voxel_length, const
                      McP *p) {
     if (res <= 0 || res > 2048 || res % TB || !(voxel_length > 0.f) || !origin || !tsdf || !weight || !rgb) return LARA2DGS_E_INVALID;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LARA2DGS_E_LAUNCH;
+    L2D_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) L2D_FAIL_INTERNAL();
     if (!mc_tables_loaded[dev]) {
-        if (hipMemcpyToSymbol(HIP_SYMBOL(c_mc_ntri), MC_NTRI, sizeof(MC_NTRI)) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(c_mc_tri), MC_TRI, sizeof(MC_TRI)) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(c_mc_edge), MC_EDGE_CORNERS, sizeof(MC_EDGE_CORNERS)) != hipSuccess)
-            return LARA2DGS_E_LAUNCH;
+        L2D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_mc_ntri), MC_NTRI, sizeof(MC_NTRI)));
+        L2D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_mc_tri), MC_TRI, sizeof(MC_TRI)));
+        L2D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_mc_edge), MC_EDGE_CORNERS, sizeof(MC_EDGE_CORNERS)));
         mc_tables_loaded[dev] = true;
     }
     *p = McP{res, origin[0], origin[1], origin[2], voxel_length, tsdf, weight, rgb};
@@ -259,11 +248,7 @@ int lara_tsdf_mesh_count(int32_t res, const float *origin, float voxel_length, c
     if (!counts) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int nb = res / TB;
-    {
-        L2D_PROF("tsdf_mesh_count", s);
-        hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)((size_t)nb * nb * nb * (TB * TB * TB / 256))), dim3(256), 0, s, p, allocated, counts);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tsdf_mesh_count", s, mc_count_kernel, dim3((unsigned)((size_t)nb * nb * nb * (TB * TB * TB / 256))), dim3(256), 0, p, allocated, counts);
     return LARA2DGS_OK;
 }
 
@@ -276,12 +261,8 @@ int lara_tsdf_mesh_emit(int32_t res, const float *origin, float voxel_length, co
     if (!counts || !ends || !vertices || !colors || !edge_keys) return LARA2DGS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int nb = res / TB;
-    {
-        L2D_PROF("tsdf_mesh_emit", s);
-        hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)((size_t)nb * nb * nb * (TB * TB * TB / 256))), dim3(256), 0, s, p, allocated, counts,
-                           ends, vertices, colors, edge_keys);
-    }
-    L2D_CHECK_LAUNCH();
+    L2D_LAUNCH("tsdf_mesh_emit", s, mc_emit_kernel, dim3((unsigned)((size_t)nb * nb * nb * (TB * TB * TB / 256))), dim3(256), 0, p, allocated, counts,
+               ends, vertices, colors, edge_keys);
     return LARA2DGS_OK;
 }
 

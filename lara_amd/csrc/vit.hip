@@ -29,10 +29,7 @@ constexpr int VT_PD = 768;         // 3 x 16 x 16 patch row
 constexpr int VT_LNB = 256;        // ln_bwd_kernel blocks (gamma / beta partial rows)
 constexpr int VT_CSP = 64;         // column-sum partial rows
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-
-typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
 __device__ __forceinline__ bf16x8 as_frag(const uint4 u) {
     bf16x8 f;
@@ -48,14 +45,6 @@ __device__ __forceinline__ bf16x8 frag_acc(const f32x4 a, const f32x4 b) {   // 
 __device__ __forceinline__ f32x4 mfma16(const bf16x8 a, const bf16x8 b, const f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ float bfr(const float v) { return bf2f(f2bf(v)); }   // round to bf16 and back
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // weights: bf16 copy (row-major as given) or bf16 transpose
 __global__ void __launch_bounds__(256) wcast_kernel(const float *__restrict__ src, const size_t n, unsigned short *__restrict__ dst) {
@@ -695,35 +684,30 @@ BlkPtr blk_ptrs(char *base, const BlkOff &b) {
     return p;
 }
 
-#define VT_PROF(name, ...)                                    \
+// a call that returns a LARA2DGS status, under its profile label
+#define VT_PROF(name, call)                                   \
     do {                                                      \
         L2D_PROF(name, s);                                    \
-        __VA_ARGS__;                                          \
-    } while (0)
-
-#define VT_RC(call)                                           \
-    do {                                                      \
-        const int rc__ = (call);                              \
-        if (rc__ != LARA2DGS_OK) return rc__;                 \
+        L2D_TRY(call);                                        \
     } while (0)
 
 int cast_w(const float *src, size_t n, unsigned short *dst, hipStream_t s) {
-    hipLaunchKernelGGL(wcast_kernel, dim3(nblk(n)), dim3(256), 0, s, src, n, dst);
+    L2D_LAUNCH_IN_SCOPE(s, wcast_kernel, dim3(nblk(n)), dim3(256), 0, src, n, dst);
     return LARA2DGS_OK;
 }
 int trans_w(const float *src, int R, int Cc, unsigned short *dst, hipStream_t s) {
-    hipLaunchKernelGGL(wtrans_kernel, dim3((Cc + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src, R, Cc, dst);
+    L2D_LAUNCH_IN_SCOPE(s, wtrans_kernel, dim3((Cc + 31) / 32, (R + 31) / 32), dim3(256), 0, src, R, Cc, dst);
     return LARA2DGS_OK;
 }
 // bias gradient: fixed-order column sums of bf16 rows
 int colsum(const unsigned short *src, int rows, int ncol, float *part, float *out, hipStream_t s) {
-    hipLaunchKernelGGL(colsum_part_kernel, dim3((ncol + 255) / 256, VT_CSP), dim3(256), 0, s, src, rows, ncol, part);
-    hipLaunchKernelGGL(sum_parts_kernel, dim3((ncol + 255) / 256), dim3(256), 0, s, (const float *)part, VT_CSP, ncol, out, out, ncol);
+    L2D_LAUNCH_IN_SCOPE(s, colsum_part_kernel, dim3((ncol + 255) / 256, VT_CSP), dim3(256), 0, src, rows, ncol, part);
+    L2D_LAUNCH_IN_SCOPE(s, sum_parts_kernel, dim3((ncol + 255) / 256), dim3(256), 0, (const float *)part, VT_CSP, ncol, out, out, ncol);
     return LARA2DGS_OK;
 }
 // dW [N, K] = dY^T X  (written)
 int wgrad(int Mp, int N, int K, const unsigned short *dY, const unsigned short *X, float *dW, void *tn, hipStream_t s) {
-    if (hipMemsetAsync(dW, 0, (size_t)N * K * 4, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+    L2D_HIP(hipMemsetAsync(dW, 0, (size_t)N * K * 4, s));
     return lara_gemm_tn_bf16(Mp, N, K, dY, X, dW, tn, s);
 }
 
@@ -768,11 +752,11 @@ int lara_vit_forward(const lara_vit_dims *d, const float *images, const float *c
     float *x0 = train ? (float *)(sv + sl.blk0 + sl.b.xin) : (float *)(ws + fl.xa);
     {
         PatchP pp{images, g.s[0], g.s[1], g.s[2], g.s[3], g.s[4], g.NP, g.Pp, g.hw, g.w, g.views};
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(patch_kernel, dim3(nblk((size_t)g.Pp * VT_PD / 2)), dim3(256), 0, s, pp, (unsigned *)patches));
+        L2D_LAUNCH("vit_elementwise", s, patch_kernel, dim3(nblk((size_t)g.Pp * VT_PD / 2)), dim3(256), 0, pp, (unsigned *)patches);
         VT_PROF("vit_elementwise", cast_w(P(params, 2), (size_t)C * VT_PD, (unsigned short *)(ws + fl.wpatch), s));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(g.Pp, C, VT_PD, patches, (const uint16_t *)(ws + fl.wpatch), acc, 1, s)));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(tokens_kernel, dim3(nblk((size_t)g.M * C)), dim3(256), 0, s, (const float *)acc, P(params, 3), P(params, 0),
-                           P(params, 1), g.N, g.T, C, x0));
+        VT_PROF("vit_products", lara_gemm_nt_bf16(g.Pp, C, VT_PD, patches, (const uint16_t *)(ws + fl.wpatch), acc, 1, s));
+        L2D_LAUNCH("vit_elementwise", s, tokens_kernel, dim3(nblk((size_t)g.M * C)), dim3(256), 0, (const float *)acc, P(params, 3), P(params, 0),
+                   P(params, 1), g.N, g.T, C, x0);
     }
     AttnP ap{};
     ap.T = g.T; ap.Tp = g.Tp; ap.C = C; ap.heads = g.heads; ap.vt = vt;
@@ -791,35 +775,33 @@ int lara_vit_forward(const lara_vit_dims *d, const float *images, const float *c
         VT_PROF("vit_elementwise", cast_w(P(params, bp(i, 4)), (size_t)C * C, wp, s));
         VT_PROF("vit_elementwise", cast_w(P(params, bp(i, 8)), (size_t)F * C, w1, s));
         VT_PROF("vit_elementwise", cast_w(P(params, bp(i, 10)), (size_t)C * F, w2, s));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_fwd_kernel<false>, dim3((g.Mp + 3) / 4), dim3(256), 0, s, (const float *)b.xin, P(params, bp(i, 0)),
-                           P(params, bp(i, 1)), g.M, g.Mp, g.T, C, g.eps, (void *)b.xn1, b.st1));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(g.Mp, 3 * C, C, b.xn1, wq, acc, 1, s)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(qkv_split_kernel, dim3(nblk((size_t)3 * g.NH * g.Tp * VT_HD)), dim3(256), 0, s, (const float *)acc,
-                           P(params, bp(i, 3)), g.N, g.T, g.Tp, C, b.q, b.k, b.v));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, (const unsigned short *)b.v, g.NH, g.Tp, vt));
-        if (g.Mp > g.M && hipMemsetAsync(b.o + mc, 0, (size_t)(g.Mp - g.M) * C * 2, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_LAUNCH("vit_layernorm", s, ln_fwd_kernel<false>, dim3((g.Mp + 3) / 4), dim3(256), 0, (const float *)b.xin, P(params, bp(i, 0)),
+                   P(params, bp(i, 1)), g.M, g.Mp, g.T, C, g.eps, (void *)b.xn1, b.st1);
+        VT_PROF("vit_products", lara_gemm_nt_bf16(g.Mp, 3 * C, C, b.xn1, wq, acc, 1, s));
+        L2D_LAUNCH("vit_attention", s, qkv_split_kernel, dim3(nblk((size_t)3 * g.NH * g.Tp * VT_HD)), dim3(256), 0, (const float *)acc,
+                   P(params, bp(i, 3)), g.N, g.T, g.Tp, C, b.q, b.k, b.v);
+        L2D_LAUNCH("vit_attention", s, head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, (const unsigned short *)b.v, g.NH, g.Tp, vt);
+        if (g.Mp > g.M) L2D_HIP(hipMemsetAsync(b.o + mc, 0, (size_t)(g.Mp - g.M) * C * 2, s));
         ap.q = b.q; ap.k = b.k; ap.o = b.o; ap.lse = b.lse;
-        if (train) VT_PROF("vit_attention", hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, ap));
-        else VT_PROF("vit_attention", hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, ap));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(g.Mp, C, C, b.o, wp, acc, 1, s)));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(residual_kernel, dim3(nblk(mc)), dim3(256), 0, s, (const float *)acc, P(params, bp(i, 5)), (const float *)b.xin,
-                           g.M, C, b.xmid));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_fwd_kernel<false>, dim3((g.Mp + 3) / 4), dim3(256), 0, s, (const float *)b.xmid, P(params, bp(i, 6)),
-                           P(params, bp(i, 7)), g.M, g.Mp, g.T, C, g.eps, (void *)b.xn2, b.st2));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(g.Mp, F, C, b.xn2, w1, acc, 1, s)));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(fc1_kernel, dim3(nblk((size_t)g.Mp * F)), dim3(256), 0, s, (const float *)acc, P(params, bp(i, 9)), g.M, g.Mp, F,
-                           train ? b.h : (unsigned short *)nullptr, gb));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(g.Mp, C, F, gb, w2, acc, 1, s)));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(residual_kernel, dim3(nblk(mc)), dim3(256), 0, s, (const float *)acc, P(params, bp(i, 11)), (const float *)b.xmid,
-                           g.M, C, b.xout));
-        L2D_CHECK_LAUNCH();
+        if (train) L2D_LAUNCH("vit_attention", s, attn_fwd_kernel<true>, dim3(g.Tp / 64, g.NH), dim3(256), 0, ap);
+        else L2D_LAUNCH("vit_attention", s, attn_fwd_kernel<false>, dim3(g.Tp / 64, g.NH), dim3(256), 0, ap);
+        VT_PROF("vit_products", lara_gemm_nt_bf16(g.Mp, C, C, b.o, wp, acc, 1, s));
+        L2D_LAUNCH("vit_elementwise", s, residual_kernel, dim3(nblk(mc)), dim3(256), 0, (const float *)acc, P(params, bp(i, 5)), (const float *)b.xin,
+                   g.M, C, b.xmid);
+        L2D_LAUNCH("vit_layernorm", s, ln_fwd_kernel<false>, dim3((g.Mp + 3) / 4), dim3(256), 0, (const float *)b.xmid, P(params, bp(i, 6)),
+                   P(params, bp(i, 7)), g.M, g.Mp, g.T, C, g.eps, (void *)b.xn2, b.st2);
+        VT_PROF("vit_products", lara_gemm_nt_bf16(g.Mp, F, C, b.xn2, w1, acc, 1, s));
+        L2D_LAUNCH("vit_elementwise", s, fc1_kernel, dim3(nblk((size_t)g.Mp * F)), dim3(256), 0, (const float *)acc, P(params, bp(i, 9)), g.M, g.Mp, F,
+                   train ? b.h : (unsigned short *)nullptr, gb);
+        VT_PROF("vit_products", lara_gemm_nt_bf16(g.Mp, C, F, gb, w2, acc, 1, s));
+        L2D_LAUNCH("vit_elementwise", s, residual_kernel, dim3(nblk(mc)), dim3(256), 0, (const float *)acc, P(params, bp(i, 11)), (const float *)b.xmid,
+                   g.M, C, b.xout);
     }
     {
         const float *xf = train ? (const float *)(sv + sl.xfin) : (const float *)(ws + ((depth & 1) ? fl.xb : fl.xa));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_fwd_kernel<true>, dim3((g.M + 3) / 4), dim3(256), 0, s, xf, P(params, bp(depth, 0)), P(params, bp(depth, 1)),
-                           g.M, g.M, g.T, C, g.eps, (void *)out, stf));
+        L2D_LAUNCH("vit_layernorm", s, ln_fwd_kernel<true>, dim3((g.M + 3) / 4), dim3(256), 0, xf, P(params, bp(depth, 0)), P(params, bp(depth, 1)),
+                   g.M, g.M, g.T, C, g.eps, (void *)out, stf);
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 
@@ -841,11 +823,11 @@ int lara_vit_backward(const lara_vit_dims *d, const float *const *params, const 
     void *tn = ws + bl.tn;
     const size_t hd = (size_t)g.NH * g.Tp * VT_HD;
     {
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_bwd_kernel<true>, dim3(VT_LNB), dim3(256), 0, s, (const void *)grad, (const float *)(sv + sl.xfin),
-                           (const float2 *)(sv + sl.stf), P(params, bp(depth, 0)), M, g.T, C, dres, part));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, (const float *)part, VT_LNB, 2 * C,
-                           grads[bp(depth, 0)], grads[bp(depth, 1)], C));
-        if (Mp > M && hipMemsetAsync(dqkv + (size_t)M * 3 * C, 0, (size_t)(Mp - M) * 3 * C * 2, s) != hipSuccess) return LARA2DGS_E_LAUNCH;
+        L2D_LAUNCH("vit_layernorm", s, ln_bwd_kernel<true>, dim3(VT_LNB), dim3(256), 0, (const void *)grad, (const float *)(sv + sl.xfin),
+                   (const float2 *)(sv + sl.stf), P(params, bp(depth, 0)), M, g.T, C, dres, part);
+        L2D_LAUNCH("vit_layernorm", s, sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, (const float *)part, VT_LNB, 2 * C,
+                   grads[bp(depth, 0)], grads[bp(depth, 1)], C);
+        if (Mp > M) L2D_HIP(hipMemsetAsync(dqkv + (size_t)M * 3 * C, 0, (size_t)(Mp - M) * 3 * C * 2, s));
     }
     AttnP ap{};
     ap.T = g.T; ap.Tp = g.Tp; ap.C = C; ap.heads = g.heads;
@@ -858,50 +840,48 @@ int lara_vit_backward(const lara_vit_dims *d, const float *const *params, const 
         VT_PROF("vit_elementwise", trans_w(P(params, bp(i, 8)), F, C, w1T, s));
         VT_PROF("vit_elementwise", trans_w(P(params, bp(i, 10)), C, F, w2T, s));
         // MLP half: x'' = x' + fc2(GELU(fc1(LN2(x'))))
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(rows_bf16_kernel, dim3(nblk((size_t)Mp * C)), dim3(256), 0, s, (const float *)dres, M, Mp, C, dy));
+        L2D_LAUNCH("vit_elementwise", s, rows_bf16_kernel, dim3(nblk((size_t)Mp * C)), dim3(256), 0, (const float *)dres, M, Mp, C, dy);
         VT_PROF("vit_elementwise", colsum(dy, Mp, C, part, grads[bp(i, 11)], s));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(gelu_kernel, dim3(nblk((size_t)Mp * F)), dim3(256), 0, s, (const unsigned short *)b.h, (size_t)Mp * F, gb));
-        VT_PROF("vit_products", VT_RC(wgrad(Mp, C, F, dy, gb, grads[bp(i, 10)], tn, s)));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(Mp, F, C, dy, w2T, dh, 0, s)));
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(gelu_bwd_kernel, dim3(nblk((size_t)Mp * F)), dim3(256), 0, s, (const unsigned short *)b.h, (size_t)Mp * F, dh));
+        L2D_LAUNCH("vit_elementwise", s, gelu_kernel, dim3(nblk((size_t)Mp * F)), dim3(256), 0, (const unsigned short *)b.h, (size_t)Mp * F, gb);
+        VT_PROF("vit_products", wgrad(Mp, C, F, dy, gb, grads[bp(i, 10)], tn, s));
+        VT_PROF("vit_products", lara_gemm_nt_bf16(Mp, F, C, dy, w2T, dh, 0, s));
+        L2D_LAUNCH("vit_elementwise", s, gelu_bwd_kernel, dim3(nblk((size_t)Mp * F)), dim3(256), 0, (const unsigned short *)b.h, (size_t)Mp * F, dh);
         VT_PROF("vit_elementwise", colsum(dh, Mp, F, part, grads[bp(i, 9)], s));
-        VT_PROF("vit_products", VT_RC(wgrad(Mp, F, C, dh, b.xn2, grads[bp(i, 8)], tn, s)));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(Mp, C, F, dh, w1T, dxn, 0, s)));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_bwd_kernel<false>, dim3(VT_LNB), dim3(256), 0, s, (const void *)dxn, (const float *)b.xmid,
-                           (const float2 *)b.st2, P(params, bp(i, 6)), M, g.T, C, dres, part));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, (const float *)part, VT_LNB, 2 * C,
-                           grads[bp(i, 6)], grads[bp(i, 7)], C));
+        VT_PROF("vit_products", wgrad(Mp, F, C, dh, b.xn2, grads[bp(i, 8)], tn, s));
+        VT_PROF("vit_products", lara_gemm_nt_bf16(Mp, C, F, dh, w1T, dxn, 0, s));
+        L2D_LAUNCH("vit_layernorm", s, ln_bwd_kernel<false>, dim3(VT_LNB), dim3(256), 0, (const void *)dxn, (const float *)b.xmid,
+                   (const float2 *)b.st2, P(params, bp(i, 6)), M, g.T, C, dres, part);
+        L2D_LAUNCH("vit_layernorm", s, sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, (const float *)part, VT_LNB, 2 * C,
+                   grads[bp(i, 6)], grads[bp(i, 7)], C);
         // attention half: x' = x + proj(attn(qkv(LN1(x))))
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(rows_bf16_kernel, dim3(nblk((size_t)Mp * C)), dim3(256), 0, s, (const float *)dres, M, Mp, C, dy));
+        L2D_LAUNCH("vit_elementwise", s, rows_bf16_kernel, dim3(nblk((size_t)Mp * C)), dim3(256), 0, (const float *)dres, M, Mp, C, dy);
         VT_PROF("vit_elementwise", colsum(dy, Mp, C, part, grads[bp(i, 5)], s));
-        VT_PROF("vit_products", VT_RC(wgrad(Mp, C, C, dy, b.o, grads[bp(i, 4)], tn, s)));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(Mp, C, C, dy, wpT, dob, 0, s)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(head_split_kernel, dim3(nblk(hd)), dim3(256), 0, s, (const unsigned short *)dob, g.N, g.T, g.Tp, C, u16(bl.doh)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(attn_dvec_kernel, dim3(nblk((size_t)g.NH * g.Tp)), dim3(256), 0, s, (const unsigned short *)u16(bl.doh),
-                           (const unsigned short *)b.o, g.NH, g.T, g.Tp, C, (float *)(ws + bl.dvec)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, (const unsigned short *)u16(bl.doh), g.NH, g.Tp, u16(bl.dot)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, (const unsigned short *)b.q, g.NH, g.Tp, u16(bl.qt)));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, (const unsigned short *)b.k, g.NH, g.Tp, u16(bl.kt)));
+        VT_PROF("vit_products", wgrad(Mp, C, C, dy, b.o, grads[bp(i, 4)], tn, s));
+        VT_PROF("vit_products", lara_gemm_nt_bf16(Mp, C, C, dy, wpT, dob, 0, s));
+        L2D_LAUNCH("vit_attention", s, head_split_kernel, dim3(nblk(hd)), dim3(256), 0, (const unsigned short *)dob, g.N, g.T, g.Tp, C, u16(bl.doh));
+        L2D_LAUNCH("vit_attention", s, attn_dvec_kernel, dim3(nblk((size_t)g.NH * g.Tp)), dim3(256), 0, (const unsigned short *)u16(bl.doh),
+                   (const unsigned short *)b.o, g.NH, g.T, g.Tp, C, (float *)(ws + bl.dvec));
+        L2D_LAUNCH("vit_attention", s, head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, (const unsigned short *)u16(bl.doh), g.NH, g.Tp, u16(bl.dot));
+        L2D_LAUNCH("vit_attention", s, head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, (const unsigned short *)b.q, g.NH, g.Tp, u16(bl.qt));
+        L2D_LAUNCH("vit_attention", s, head_t_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, (const unsigned short *)b.k, g.NH, g.Tp, u16(bl.kt));
         ap.q = b.q; ap.k = b.k; ap.v = b.v; ap.lse_in = b.lse;
-        VT_PROF("vit_attention", hipLaunchKernelGGL(attn_dq_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, ap));
-        VT_PROF("vit_attention", hipLaunchKernelGGL(attn_dkv_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, s, ap));
+        L2D_LAUNCH("vit_attention", s, attn_dq_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, ap);
+        L2D_LAUNCH("vit_attention", s, attn_dkv_kernel, dim3(g.Tp / 64, g.NH), dim3(256), 0, ap);
         VT_PROF("vit_elementwise", colsum(dqkv, Mp, 3 * C, part, grads[bp(i, 3)], s));
-        VT_PROF("vit_products", VT_RC(wgrad(Mp, 3 * C, C, dqkv, b.xn1, grads[bp(i, 2)], tn, s)));
-        VT_PROF("vit_products", VT_RC(lara_gemm_nt_bf16(Mp, C, 3 * C, dqkv, wqT, dxn, 0, s)));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(ln_bwd_kernel<false>, dim3(VT_LNB), dim3(256), 0, s, (const void *)dxn, (const float *)b.xin,
-                           (const float2 *)b.st1, P(params, bp(i, 0)), M, g.T, C, dres, part));
-        VT_PROF("vit_layernorm", hipLaunchKernelGGL(sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, (const float *)part, VT_LNB, 2 * C,
-                           grads[bp(i, 0)], grads[bp(i, 1)], C));
-        L2D_CHECK_LAUNCH();
+        VT_PROF("vit_products", wgrad(Mp, 3 * C, C, dqkv, b.xn1, grads[bp(i, 2)], tn, s));
+        VT_PROF("vit_products", lara_gemm_nt_bf16(Mp, C, 3 * C, dqkv, wqT, dxn, 0, s));
+        L2D_LAUNCH("vit_layernorm", s, ln_bwd_kernel<false>, dim3(VT_LNB), dim3(256), 0, (const void *)dxn, (const float *)b.xin,
+                   (const float2 *)b.st1, P(params, bp(i, 0)), M, g.T, C, dres, part);
+        L2D_LAUNCH("vit_layernorm", s, sum_parts_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, (const float *)part, VT_LNB, 2 * C,
+                   grads[bp(i, 0)], grads[bp(i, 1)], C);
     }
     {
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(tokens_bwd_kernel, dim3(nblk((size_t)g.T * C)), dim3(256), 0, s, (const float *)dres, g.N, g.T, C, grads[1], grads[0]));
+        L2D_LAUNCH("vit_elementwise", s, tokens_bwd_kernel, dim3(nblk((size_t)g.T * C)), dim3(256), 0, (const float *)dres, g.N, g.T, C, grads[1], grads[0]);
         unsigned short *dconv = u16(bl.dconv);
-        VT_PROF("vit_elementwise", hipLaunchKernelGGL(dconv_kernel, dim3(nblk((size_t)g.Pp * C)), dim3(256), 0, s, (const float *)dres, g.N, g.T, C, g.Pp, dconv));
+        L2D_LAUNCH("vit_elementwise", s, dconv_kernel, dim3(nblk((size_t)g.Pp * C)), dim3(256), 0, (const float *)dres, g.N, g.T, C, g.Pp, dconv);
         VT_PROF("vit_elementwise", colsum(dconv, g.Pp, C, part, grads[3], s));
-        VT_PROF("vit_products", VT_RC(wgrad(g.Pp, C, VT_PD, dconv, (const unsigned short *)(sv + sl.patches), grads[2], tn, s)));
+        VT_PROF("vit_products", wgrad(g.Pp, C, VT_PD, dconv, (const unsigned short *)(sv + sl.patches), grads[2], tn, s));
     }
-    L2D_CHECK_LAUNCH();
     return LARA2DGS_OK;
 }
 

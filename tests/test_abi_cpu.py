@@ -461,3 +461,91 @@ def test_a_forward_that_does_not_fit_is_repeated_before_the_operator_returns(mon
     with pytest.raises(RuntimeError, match="32-bit pair index"):
         rz._run_forward(bucket, 3, enqueue_huge)
     rz.reset_capacity_history()
+
+
+# ---- the HIP layer's one launch-and-check path (lara_amd/csrc/launch.h), checked on the sources as text -------------------------
+
+CSRC = os.path.join(ROOT, "lara_amd", "csrc")
+LAUNCH_HEADER = "launch.h"
+# launches kept outside the shared helper on purpose: (file, reason); at most five
+LAUNCH_ALLOW_LIST = ()
+# every profile label and how often it is written: the first argument of L2D_PROF, of the labeled launch L2D_LAUNCH and of
+# vit.hip's VT_PROF alias.  tools/* and tests/test_pipeline.py read profiles by these names.
+PROFILE_LABELS = {
+    "activate_bwd": 1, "activate_fwd": 1, "build_rays": 1, "bwd_order": 1, "coarse_decoder_bwd": 1,
+    "coarse_decoder_fwd": 1, "composite_bwd": 1, "composite_bwd_color": 1, "composite_fwd": 1,
+    "composite_fwd_only": 1, "eval_quantize": 1, "eval_scores": 1, "featvol_grad_transpose": 1, "featvol_index": 1,
+    "featvol_linear": 2, "featvol_modln": 1, "featvol_param_grads": 1, "featvol_sample_tokens": 1,
+    "featvol_sample_volume": 1, "featvol_token_bwd": 1, "fine_decoder_bwd": 1, "fine_decoder_fwd": 1,
+    "fine_decoder_wgrad": 1, "fine_ln_bwd": 1, "fine_ln_fwd": 1, "ga_fused": 1, "ga_gemm_kv": 1, "gb_conv3d": 2,
+    "gb_ln2": 1, "gb_ln3": 1, "gb_mlp1": 1, "gb_mlp2": 1, "gb_mlp_fused": 1, "gbb_dw_conv": 1, "gbb_dw_linear": 1,
+    "gbb_dx_attn": 1, "gbb_dx_conv": 2, "gbb_dx_mlp": 2, "gbb_ln_bwd": 4, "gbb_recompute": 1, "gbt_forward": 1,
+    "loss_terms_bwd": 1, "loss_terms_fwd": 1, "lpips_conv2d": 1, "lpips_forward": 1, "lpips_maxpool": 1,
+    "mesh_area_finish": 1, "mesh_cluster_stats": 1, "mesh_compact_rows": 1, "mesh_crop": 1, "mesh_edge_insert": 1,
+    "mesh_edge_owner": 1, "mesh_hook": 1, "mesh_jump": 1, "mesh_keep_clusters": 1, "mesh_remap": 1, "ms_ssim_bwd": 1,
+    "ms_ssim_fwd": 1, "point_feats_bwd": 1, "point_feats_fwd": 1, "point_feats_pack": 2, "preprocess_bwd": 1,
+    "preprocess_bwd_views": 1, "preprocess_fwd": 1, "preprocess_fwd_views": 1, "scatter": 1, "subset_compact": 1,
+    "subset_pair_base": 1, "surface_bwd": 1, "surface_fwd": 1, "take_rows_bwd": 1, "take_rows_fwd": 1, "tile_scan": 2,
+    "tile_sort": 1, "tsdf_integrate": 1, "tsdf_integrate_blocks": 1, "tsdf_mesh_count": 1, "tsdf_mesh_emit": 1,
+    "tsdf_touch": 1, "vit_attention": 11, "vit_elementwise": 25, "vit_layernorm": 9, "vit_products": 14,
+    "voxel_rows_bwd": 1, "voxel_rows_fwd": 1, "vt_deconv": 1, "vt_ln": 1, "vtb_head": 1,
+}
+
+
+def _csrc_sources():
+    out = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h")):
+            with open(os.path.join(CSRC, name)) as f:
+                out[name] = f.read()
+    return out
+
+
+def _first_argument(text, i):
+    """text[i:] up to the first comma or closing bracket at depth 0 (string literals skipped)."""
+    depth, j = 0, i
+    while True:
+        c = text[j]
+        if c == '"':
+            j = text.index('"', j + 1)
+        elif c in "([{":
+            depth += 1
+        elif c in ")]}":
+            if depth == 0:
+                break
+            depth -= 1
+        elif c == "," and depth == 0:
+            break
+        j += 1
+    return text[i:j]
+
+
+def _profile_labels(sources):
+    labels = {}
+    for text in sources.values():
+        for m in re.finditer(r"\b(?:L2D_PROF|VT_PROF|L2D_LAUNCH)\(", text):
+            for lit in re.findall(r'"([^"]*)"', _first_argument(text, m.end())):
+                labels[lit] = labels.get(lit, 0) + 1
+    return labels
+
+
+def test_launch_failures_go_through_the_one_checked_path():
+    src = _csrc_sources()
+    assert len(LAUNCH_ALLOW_LIST) <= 5
+    allowed = {f for f, _ in LAUNCH_ALLOW_LIST}
+    # (a) the status is produced by the shared helpers alone; abi.hip only names it in lara2dgs_error_string
+    holders = sorted(n for n, t in src.items() if "LARA2DGS_E_LAUNCH" in t)
+    assert holders == ["abi.hip", LAUNCH_HEADER], holders
+    abi = src["abi.hip"]
+    start = abi.index("lara2dgs_error_string")
+    body = abi[start:abi.index("\n}", start)]
+    assert abi.count("LARA2DGS_E_LAUNCH") == 1 and "case LARA2DGS_E_LAUNCH:" in body
+    # (b) kernels are launched inside the shared helper only
+    for token in ("hipLaunchKernelGGL", "<<<"):
+        where = sorted(n for n, t in src.items() if token in t and n != LAUNCH_HEADER and n not in allowed)
+        assert where == [], (token, where)
+    assert "hipLaunchKernelGGL" in src[LAUNCH_HEADER]
+    # (c) and the launch error is read there only
+    assert sorted(n for n, t in src.items() if "hipGetLastError" in t) == [LAUNCH_HEADER]
+    # (d) the profile labels are the ones the tools know, each as often as before
+    assert _profile_labels(src) == PROFILE_LABELS
