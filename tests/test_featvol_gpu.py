@@ -5,7 +5,12 @@ Tolerances.  The kernels mirror bf16 autocast (the reference trains bf16-mixed):
 |diff| <= 2e-2 * max|ref| (the Linear's fp32 sums are ordered differently, which can move a bf16 rounding of shift / scale, and
 the bf16 sample positions with it: the `test_pointfeat.py` position budget, at bf16 resolution) and the gradients to 5e-2 of the
 largest entry; against the fp32 fixture every error is at most twice autocast's own error (fixture bf16 vs fixture fp32) plus
-1e-3 of the largest entry, as in `test_groupatt.py`.  Everything the kernels compute twice -- layouts, strides, runs -- is bitwise."""
+1e-3 of the largest entry, as in `test_groupatt.py`.  Everything the kernels compute twice -- layouts, strides, runs -- is bitwise.
+
+These are the COARSE bars: they are sized for bf16 noise at the reference's own shapes, and a dropped (point, tap) entry, a texel
+list cut short or a border tap with the wrong weight would pass them.  The tight ones -- every fp32 element within its own
+accumulation bound of a bf16-faithful fp64 reference, at the shapes where the kernels take another path -- are in
+tests/test_featvol_faithful_gpu.py."""
 import pytest
 import torch
 
