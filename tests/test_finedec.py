@@ -88,7 +88,11 @@ def test_hip_forward_fine_matches_the_reference_fixture():
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 100_003])
 def test_hip_forward_fine_vs_oracle_ragged_sizes(n):
-    """Sizes around the 256-point tile and one that takes several trips of the persistent workgroups."""
+    """Sizes around a 256-row LayerNorm block and a large one, against the fp32 torch restatement at whole-tensor bars.  The
+    decoder kernels walk tiles of 128 points (32 per wave), and at n = 100003 < 1024 x 128 the forward's persistent loop takes
+    no second trip (the backward's 512 workgroups take two).  The tile, wave and slab boundaries, the second forward trip and
+    the element-by-element bounds are in tests/test_finedec_f64_gpu.py (cases: tests/finedec_cases.py, reference:
+    oracle/finedec_f64.py, without a GPU: tests/test_finedec_f64.py)."""
     from lara_amd.fine import _FineDecoder, _fold_fine_weights
     torch.manual_seed(n)
     dec = FineDecoderRef()
