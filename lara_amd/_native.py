@@ -18,7 +18,7 @@ import re
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (LARA2DGS_LIB: another build of the same library -- kernel A/B experiments, tools/build_variant.sh; never a CPU path)
+# (LARA2DGS_LIB: another build of the same library -- kernel A/B experiments, `make -C lara_amd/csrc VARIANT=<tag> EXTRA=...`; never a CPU path)
 LIB_PATH = os.environ.get("LARA2DGS_LIB") or os.path.join(_HERE, "liblara2dgs.so")
 ABI_VERSION = 10
 

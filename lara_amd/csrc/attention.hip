@@ -7,8 +7,9 @@
 //
 // Kernels (bf16 operands, fp32 accumulate -- what the reference runs under bf16-mixed autocast):
 //   ln_cast          LayerNorm(256) + cast to bf16, one wave per token             HBM-bound
-//   gemm_bf16_nt     C[M,N] = A[M,K] W[N,K]^T on v_mfma_f32_32x32x16_bf16; used for the Q, K|V and
-//                    output projections (epilogue: bf16 store, or fp32 store + residual add)
+//   gemm_ring(2)     C[M,N] = A[M,K] W[N,K]^T on v_mfma_f32_32x32x16_bf16 behind an LDS-DMA ring (mfma_gemm.h): the K|V
+//                    projection (bf16 store).  The Q and output projections run inside group_attn_fused2_kernel;
+//                    gemm_bf16_nt_kernel serves the encoder's backward and head only
 //   group_attn       QK^T, softmax over the 4 keys, and AV on v_mfma_f32_16x16x16_bf16.  The tiny
 //                    per-(group, head) problems (8x16 . 16x4 and 8x4 . 4x16) are packed four groups
 //                    to a tile: S^T = K Q^T puts a query's four scores into the four accumulator

@@ -626,11 +626,8 @@ __device__ __forceinline__ void quad_reduce_scatter16(const float dp[3], const f
 // the wave instructions, and it keeps the backward free of floating-point atomics.
 constexpr int SLAB_WIN = 128;     // list entries staged per window (one per thread of the two staging waves)
 constexpr int SLAB_CHUNK = 128;   // entries per slab round (two ballot words)
-#ifndef L2D_SLAB_POOL
-#define L2D_SLAB_POOL 374
-#endif
-constexpr int SLAB_POOL = L2D_SLAB_POOL;    // (entry, 2x2 block) slots per round (tools/build_variant.sh -DL2D_SLAB_POOL=n for A/B runs); 374: the
-                                            // kernel's LDS must stay below 53 248 bytes for three workgroups per CU (384 slots: two, 460 us)
+constexpr int SLAB_POOL = 374;    // (entry, 2x2 block) slots per round: the kernel's LDS must stay below 53 248 bytes for three
+                                  // workgroups per CU (384 slots: two, 460 us)
 constexpr int SLAB_F = 24;        // floats per slot: 22 quad-reduced sums, padded to 96 bytes (36 KB in all)
 // MAPS = false: the call has a gradient on the COLOUR image only (dL_dallmap is NULL = zero: LaRa's fine pass always, its coarse pass
 // for the first 1000 iterations -- lightning/loss.py:35-60 puts the distortion and normal terms on the coarse maps alone).  Then
@@ -639,21 +636,12 @@ constexpr int SLAB_F = 24;        // floats per slot: 22 quad-reduced sums, padd
 // term that is left is computed as in the full kernel, contraction for contraction: the two give the same bits for seven planes of
 // zeros (tests/test_raster_parity_gpu.py, tools/color_only_check.py).
 constexpr int SLAB_F_COLOR = 16;
-#ifdef L2D_COLOR_OCC4      // A/B: the colour-only form at four workgroups per CU (384 slots = 24 KB, 128 VGPRs, 20 bytes of scratch): measured
-                           // 285 -> 270 us per view at init statistics, 77 -> 87 us trained-like (same box, two pairs) -- not shipped
-constexpr int SLAB_POOL_COLOR = SLAB_POOL;
-#else
+// (The colour-only form at four workgroups per CU -- 384 slots = 24 KB, 128 VGPRs, 20 bytes of scratch -- measured 285 -> 270 us per
+// view at init statistics, 77 -> 87 us trained-like, same box, two pairs: not shipped.)
 constexpr int SLAB_POOL_COLOR = SLAB_POOL * SLAB_F / SLAB_F_COLOR;
-#endif
 
 template <bool MAPS>
-#ifdef L2D_BWD_WAVES       // waves per SIMD the register allocation aims at (tools/build_variant.sh -DL2D_BWD_WAVES=n for A/B runs)
-__global__ void __launch_bounds__(256, L2D_BWD_WAVES)
-#elif defined(L2D_COLOR_OCC4)
-__global__ void __launch_bounds__(256, MAPS ? 1 : 4)
-#else
 __global__ void __launch_bounds__(256)
-#endif
 composite_bwd_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint2 *__restrict__ ranges,
                      const uint32_t *__restrict__ point_list, const float4 *__restrict__ geom,
                      const uint32_t *__restrict__ tile_order, const float4 *__restrict__ cullbox,
@@ -1075,10 +1063,8 @@ composite_bwd_kernel(ViewDev v, const uint32_t *__restrict__ header, const uint2
                 // (two trips per loop iteration: the five state registers alternate instead of being copied at the loop's top)
                 while (__ballot((mm | q1 | q2 | q3) != 0u) != 0ull) {
                     trip();
-#ifndef L2D_WALK_NO_UNROLL
                     if (__ballot((mm | q1 | q2 | q3) != 0u) == 0ull) break;
                     trip();
-#endif
                 }
             }
             __syncthreads();        // the round's slots are written

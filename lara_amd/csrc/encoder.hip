@@ -98,16 +98,10 @@ int lara_groupblock_forward(int32_t scenes, int32_t R, int32_t cond_dim, float *
                                     x, workspace, stream);
     if (rc) return rc;
     unsigned short *xn = (unsigned short *)workspace;
-    unsigned short *hid = xn + (size_t)M * 256;  // [M, 512]
     float2 *stats = (float2 *)((char *)workspace + (size_t)M * 256 * 2 * 4);
-#ifndef LARA_MLP_UNFUSED
-    char *zero_row = (char *)xn + (size_t)M * 512;      // row M of xn: written by the fused MLP kernel (the hidden tensor's old place)
-#else
-    char *zero_row = (char *)workspace + (size_t)M * 256 * 2 * 4 + (size_t)M * 8;
-#endif
+    char *zero_row = (char *)xn + (size_t)M * 512;      // row M of xn: zero-filled by the fused MLP kernel (mlp_fused.h)
     // 2. MLP + norm3: ONE kernel per 128-row tile (mlp_fused.h); the hidden tensor never leaves the CU
-#ifndef LARA_MLP_UNFUSED
-    (void)hid;
+    // (rounds 2-5 ran four launches -- LayerNorm, two products, LayerNorm; the A/B is profiles/r06_ab_mlp_fused_step.log)
     {
         L2D_PROF("gb_mlp_fused", s);
         MlpP p{};
@@ -115,28 +109,7 @@ int lara_groupblock_forward(int32_t scenes, int32_t R, int32_t cond_dim, float *
         p.w1 = w->w1; p.w2 = w->w2; p.xn3 = xn; p.stats = stats; p.eps = w->eps; p.M = M;
         L2D_HIP(launch_mlp_fused<0>(p, s));
     }
-#else       // (rounds 2-5: four launches; tools/build_variant.sh -DLARA_MLP_UNFUSED for A/B runs)
-    L2D_LAUNCH("gb_ln2", s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, w->ln2_w, w->ln2_b, w->eps, xn,
-               (float2 *)nullptr, M);
-    {
-        L2D_PROF("gb_mlp1", s);
-        GemmP p{};
-        p.A = xn; p.W = w->w1; p.C = hid; p.bias = w->b1; p.M = M; p.N = 512; p.K = 256;
-        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 2>), dim3((M + 127) / 128, 4), dim3(256), 0, p);
-    }
-    {
-        L2D_PROF("gb_mlp2", s);
-        GemmP p{};
-        p.A = hid; p.W = w->w2; p.C = x; p.resid = x; p.bias = w->b2; p.M = M; p.N = 256; p.K = 512;
-        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, p);
-    }
-    // 3. norm3 + convolution + residual on the normalised activations
-    L2D_LAUNCH("gb_ln3", s, ln_cast_kernel, dim3((M + 3) / 4), dim3(256), 0, x, w->ln3_w, w->ln3_b, w->eps, xn,
-               stats, M);
-#endif
-#ifdef LARA_MLP_UNFUSED
-    L2D_HIP(hipMemsetAsync(zero_row, 0, 512, s));
-#endif      // (the fused kernel zero-fills the row behind xn's last: mlp_fused.h)
+    // 3. convolution + residual on the normalised activations
     {
         L2D_PROF("gb_conv3d", s);
         GemmP p{};

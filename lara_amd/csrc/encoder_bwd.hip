@@ -1174,7 +1174,7 @@ int gemm_tn_group(const TnJob *jobs, int count, float *part, hipStream_t s) {
     return LARA2DGS_OK;
 }
 
-// LayerNorm backward + the reductions of its partial sums into dgamma, dbeta, dbias (any may be null)
+// LayerNorm backward + the reductions of its partial sums into dgamma, dbeta (either may be null)
 // pending column reductions of a block (reduce_group_kernel)
 struct RedList {
     RedGroup g{};
@@ -1196,20 +1196,19 @@ struct RedList {
     }
 };
 
-// `later`: the three reductions are queued there (the caller launches them with others) instead of launched here; `part` must
-// then stay untouched until it does
+// `later`: the two reductions are queued there (the caller launches them with others) instead of launched here; `part` must
+// then stay untouched until it does.  (The kernel's third set of sums, the column sums of dx, has no taker: the only LayerNorm
+// with a bias gradient in front of it is norm3, whose backward runs in the convolution's epilogue, EPI 9.)
 int ln_bwd(const void *dy, bool dy_bf16, const float *x, const float *gamma, float eps, const float *skip, float *dx,
-           unsigned short *dx_bf16, float *dgamma, float *dbeta, float *dbias, float *part, int M, hipStream_t s,
-           RedList *later = nullptr) {
+           unsigned short *dx_bf16, float *dgamma, float *dbeta, float *part, int M, hipStream_t s, RedList *later = nullptr) {
     const int blocks = (M + LNB_ROWS - 1) / LNB_ROWS;
     if (dy_bf16) L2D_LAUNCH_IN_SCOPE(s, ln_bwd_kernel<true>, dim3(blocks), dim3(256), 0, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
     else L2D_LAUNCH_IN_SCOPE(s, ln_bwd_kernel<false>, dim3(blocks), dim3(256), 0, dy, x, gamma, eps, skip, dx, dx_bf16, part, M);
     if (later) {
         later->add(dgamma, part, 256, blocks, 768);
         later->add(dbeta, part + 256, 256, blocks, 768);
-        later->add(dbias, part + 512, 256, blocks, 768);
     } else {
-        L2D_LAUNCH_IN_SCOPE(s, accum_ln_partials_kernel, dim3(4, 3), dim3(1024), 0, dgamma, dbeta, dbias, part, blocks);
+        L2D_LAUNCH_IN_SCOPE(s, accum_ln_partials_kernel, dim3(4, 3), dim3(1024), 0, dgamma, dbeta, (float *)nullptr, part, blocks);
     }
     return LARA2DGS_OK;
 }
@@ -1222,10 +1221,9 @@ int colsum_bf16(const unsigned short *src, int rows, int C, float *dst, float *p
 }
 
 template <int EPI>
-int gemm_nt(const unsigned short *A, const unsigned short *W, void *C, int M, int N, int K, const float *resid,
-             unsigned short *C2, hipStream_t s, float *colsum = nullptr) {
+int gemm_nt(const unsigned short *A, const unsigned short *W, void *C, int M, int N, int K, const float *resid, hipStream_t s) {
     GemmP p{};
-    p.A = A; p.W = W; p.C = C; p.resid = resid; p.C2 = C2; p.M = M; p.N = N; p.K = K; p.colsum = colsum;
+    p.A = A; p.W = W; p.C = C; p.resid = resid; p.M = M; p.N = N; p.K = K;
     L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, EPI>), dim3((M + 127) / 128, (N + 127) / 128), dim3(256), 0, p);
     return LARA2DGS_OK;
 }
@@ -1251,7 +1249,7 @@ SaveWs save_layout(int64_t M) {
 }
 // scratch of lara_groupblock_backward (followed by a SaveWs for the recompute mode)
 struct BwdWs {
-    size_t gb, tmpf, dzb, dq, dkv, dob, nbr, lnpart, tnpart, save, gb3, gb2, lnpart4, total;
+    size_t gb, tmpf, dzb, dq, dkv, dob, nbr, tnpart, save, gb3, gb2, lnpart4, total;
 };
 BwdWs bwd_layout(int64_t M) {
     BwdWs w{};
@@ -1261,7 +1259,7 @@ BwdWs bwd_layout(int64_t M) {
     w.gb = take(b256 + 512);   // + a zeroed row, as above
     w.tmpf = take(f256); w.dzb = take(b512); w.dq = take(b256); w.dkv = take(b256); w.dob = take(b256);
     w.nbr = take((size_t)27 * M * 4);
-    w.lnpart = take(((size_t)(M + 63) / 64) * 768 * 4);
+    take(((size_t)(M + 63) / 64) * 768 * 4);   // (no user since the block's reductions moved to lnpart4; reserved so that the layout does not move)
     w.tnpart = take(TN_PART_BYTES);
     w.save = take(save_layout(M).total);
     w.gb3 = take(b256); w.gb2 = take(b256);
@@ -1274,7 +1272,7 @@ BwdWs bwd_layout(int64_t M) {
 int block_forward_keep(int M, int cond_dim, const float *x_in, const unsigned short *cond_bf16,
                        const lara_groupblock_weights *w, char *save, hipStream_t s) {
     const SaveWs L = save_layout(M);
-    const int G = M / 8, Mkv = G * 4, lnb = (M + 3) / 4;
+    const int G = M / 8, Mkv = G * 4;
     unsigned short *xn1 = (unsigned short *)(save + L.xn1), *q = (unsigned short *)(save + L.q), *kv = (unsigned short *)(save + L.kv);
     unsigned short *o = (unsigned short *)(save + L.o), *xn2 = (unsigned short *)(save + L.xn2), *z = (unsigned short *)(save + L.z);
     unsigned short *h = (unsigned short *)(save + L.h), *xn3 = (unsigned short *)(save + L.xn3);
@@ -1293,32 +1291,13 @@ int block_forward_keep(int M, int cond_dim, const float *x_in, const unsigned sh
         L2D_LAUNCH_IN_SCOPE(s, group_attn_fused2_kernel<true>, dim3((G + 3) / 4), dim3(64), 0, x_in, w->ln1_w, w->ln1_b, w->eps, wqp, kv, wop,
                             x1, G, xn1, q, o);
     }
-#ifndef LARA_MLP_UNFUSED
-    (void)lnb;
     {   // norm2 -> fc1 -> GELU -> fc2 -> + x1 -> norm3 as one kernel per 128-row tile (mlp_fused.h); leaves xn2, z, h, x2, xn3, stats
+        // and zero-fills row M of xn3.  (Rounds 2-5 ran four launches here; the A/B is profiles/r06_ab_mlp_fused_step.log)
         MlpP p{};
         p.x1 = x1; p.x2 = x2; p.ln2_w = w->ln2_w; p.ln2_b = w->ln2_b; p.b1 = w->b1; p.b2 = w->b2; p.ln3_w = w->ln3_w; p.ln3_b = w->ln3_b;
         p.w1 = w->w1; p.w2 = w->w2; p.xn3 = xn3; p.stats = (float2 *)(save + L.stats); p.xn2 = xn2; p.z = z; p.h = h; p.eps = w->eps; p.M = M;
         L2D_HIP(launch_mlp_fused<1>(p, s));
     }
-#else       // (rounds 2-5: four launches; tools/build_variant.sh -DLARA_MLP_UNFUSED for A/B runs)
-    L2D_LAUNCH_IN_SCOPE(s, ln_cast_kernel, dim3(lnb), dim3(256), 0, x1, w->ln2_w, w->ln2_b, w->eps, xn2, (float2 *)nullptr, M);
-    {
-        GemmP p{};
-        p.A = xn2; p.W = w->w1; p.C = h; p.C2 = z; p.bias = w->b1; p.M = M; p.N = 512; p.K = 256;
-        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 6>), dim3((M + 127) / 128, 4), dim3(256), 0, p);
-    }
-    {
-        GemmP p{};
-        p.A = h; p.W = w->w2; p.C = x2; p.resid = x1; p.bias = w->b2; p.M = M; p.N = 256; p.K = 512;
-        L2D_LAUNCH_IN_SCOPE(s, (gemm_bf16_nt_kernel<0, 3>), dim3((M + 127) / 128, 2), dim3(256), 0, p);
-    }
-    L2D_LAUNCH_IN_SCOPE(s, ln_cast_kernel, dim3(lnb), dim3(256), 0, x2, w->ln3_w, w->ln3_b, w->eps, xn3,
-                        (float2 *)(save + L.stats), M);
-#endif
-#ifdef LARA_MLP_UNFUSED
-    L2D_HIP(hipMemsetAsync(xn3 + (size_t)M * 256, 0, 512, s));
-#endif      // (the fused kernel zero-fills row M of xn3: mlp_fused.h)
     return LARA2DGS_OK;
 }
 
@@ -1386,6 +1365,10 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
     if (scenes == 0) return LARA2DGS_OK;
     if (!x_in || !cond_bf16 || !g || (!dcond && !dkv_ext) || !workspace) return LARA2DGS_E_INVALID;
     if (dkv_ext && (lddkv < 512 || (lddkv & 7))) return LARA2DGS_E_INVALID;
+    // the convolution's input gradient runs on gemm_ring2_kernel with norm3's backward in its epilogue (EPI 9), which needs
+    // K % 128 == 0 and Cin % 128 == 0: true by construction, the block's channel count is fixed at 256
+    constexpr int CONV_CIN = 256, CONV_K = 27 * CONV_CIN;
+    static_assert(CONV_K % 128 == 0 && CONV_CIN % 128 == 0, "gemm_ring2_kernel's shapes (launch_gemm_ring has nothing else for a convolution)");
     if (!wt->wq_t || !wt->wkv_t || !wt->wo_t || !wt->w1_t || !wt->w2_t ||
         !wt->wconv_t || !dw->ln1_w || !dw->ln1_b || !dw->wq || !dw->wkv || !dw->wo || !dw->ln2_w || !dw->ln2_b ||
         !dw->w1 || !dw->b1 || !dw->w2 || !dw->b2 || !dw->ln3_w || !dw->ln3_b || !dw->wconv)
@@ -1416,13 +1399,12 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
     const int ld_dkv = dkv_ext ? lddkv : 512;
     unsigned short *dob = (unsigned short *)(ws + L.dob);
     unsigned short *tmpb = (unsigned short *)(ws + L.tmpf);   // dX of the MLP / of the Q projection, bf16 [M, 256]
-    float *lnpart = (float *)(ws + L.lnpart), *tnpart = (float *)(ws + L.tnpart);
+    float *tnpart = (float *)(ws + L.tnpart);
     // the block's four sets of per-workgroup partial column sums (three LayerNorm backward passes, the b1 gradient) live side by
     // side and are reduced by ONE launch at the end of the block
     const size_t lnset = ((size_t)(M + LNB_ROWS - 1) / LNB_ROWS) * 768;
     float *lnp4 = (float *)(ws + L.lnpart4);
     RedList red;
-    (void)lnpart;
     int *nbr = (int *)(ws + L.nbr);
     if (!chained) {  // (a chained call finds the zero row, the neighbour table and bf16(g) where the call before left them)
         L2D_HIP(hipMemsetAsync(gb + (size_t)M * 256, 0, 512, s));
@@ -1435,83 +1417,48 @@ int lara_groupblock_backward(int32_t scenes, int32_t R, int32_t cond_dim, const 
         L2D_TRY(gemm_tn(gb, 256, 256, xn3, 256, 256, 27, nbr, M, dw->wconv, tnpart, s));
     }
     // d pn = g + cnn^T(g): the same implicit GEMM with the taps mirrored and in/out swapped; and behind it the backward of
-    // pn = norm3(x2) -- in the product's epilogue where the tile holds whole rows (EPI 9, mfma_gemm.h), as a pass of its own otherwise.
+    // pn = norm3(x2) in the product's epilogue, whose tile holds whole rows (EPI 9, mfma_gemm.h).
     // The bf16 copy of g that each LayerNorm backward leaves goes to its own buffer (gb3 behind norm3, gb2 behind norm2, gb --
     // the one the next block's convolution gathers from -- behind norm1), so that the five weight gradients of the block's linear
     // layers, whose operands are then all alive at the end of the block, run as ONE grouped product (gemm_tn_group).
     {
+        L2D_PROF("gbb_dx_conv", s);
         GemmP p{};
-        p.A = gb; p.W = wt->wconv_t; p.C = g; p.resid = g; p.M = M; p.N = 256; p.K = 27 * 256;
-        p.R = R; p.Cin = 256; p.zero_off = (uint32_t)((size_t)M * 512);
-        if (ring2_shape(p, 1)) {
-            L2D_PROF("gbb_dx_conv", s);
-            p.C2 = gb3; p.lnx = x2; p.stats = (const float2 *)(sv + S.stats); p.gamma = w->ln3_w; p.colsum = lnp4;
-            L2D_HIP(launch_gemm_ring<1, 9>(p, s));
-            const int tiles = (M + RT - 1) / RT;
-            red.add(dw->ln3_w, lnp4, 256, tiles, 768);
-            red.add(dw->ln3_b, lnp4 + 256, 256, tiles, 768);
-            red.add(dw->b2, lnp4 + 512, 256, tiles, 768);
-        } else {
-            {
-                L2D_PROF("gbb_dx_conv", s);
-                L2D_HIP(launch_gemm_ring<1, 1>(p, s));
-            }
-            L2D_PROF("gbb_ln_bwd", s);
-            L2D_TRY(ln_bwd(g, false, x2, w->ln3_w, w->eps, nullptr, g, gb3, dw->ln3_w, dw->ln3_b, dw->b2, lnp4, M, s, &red));
-        }
+        p.A = gb; p.W = wt->wconv_t; p.C = g; p.resid = g; p.M = M; p.N = 256; p.K = CONV_K;
+        p.R = R; p.Cin = CONV_CIN; p.zero_off = (uint32_t)((size_t)M * 512);
+        p.C2 = gb3; p.lnx = x2; p.stats = (const float2 *)(sv + S.stats); p.gamma = w->ln3_w; p.colsum = lnp4;
+        L2D_HIP(launch_gemm_ring<1, 9>(p, s));
+        const int tiles = (M + RT - 1) / RT;
+        red.add(dw->ln3_w, lnp4, 256, tiles, 768);
+        red.add(dw->ln3_b, lnp4 + 256, 256, tiles, 768);
+        red.add(dw->b2, lnp4 + 512, 256, tiles, 768);
     }
     // ---- x2 = x1 + mlp(norm2(x1)) ----
-#ifndef LARA_MLP_UNFUSED
     {
         // dz = (g2 W2) * gelu'(z) and dy = dz W1 as ONE kernel per 128-row tile (mlp_fused.h): dz stays in LDS between the two products
-        // (it still leaves for the weight gradient of fc1), its per-tile column sums are the pieces of db1.  LARA_MLP_BWD_LN: norm2's
-        // backward in the same kernel's epilogue (MODE 2) -- measured slower than the pass of its own (profiles/r06_mlp_fused_phases.txt)
+        // (it still leaves for the weight gradient of fc1), its per-tile column sums are the pieces of db1.  norm2's backward stays a
+        // pass of its own: in this kernel's epilogue it measured slower (profiles/r06_mlp_fused_phases.txt)
         L2D_PROF("gbb_dx_mlp", s);
         MlpP p{};
-        p.gin = gb3; p.w1 = wt->w2_t; p.w2 = wt->w1_t; p.z = z; p.h = dzb; p.x1 = x1; p.ln2_w = w->ln2_w; p.eps = w->eps;
-        p.part_b1 = lnp4 + lnset; p.M = M;
-        const int tiles = (M + 127) / 128;
-#ifdef LARA_MLP_BWD_LN
-        p.g = g; p.gout = gb2; p.part_ln = lnp4 + 2 * lnset;
-        L2D_HIP(launch_mlp_fused<2>(p, s));
-        red.add(dw->ln2_w, lnp4 + 2 * lnset, 256, tiles, 768);
-        red.add(dw->ln2_b, lnp4 + 2 * lnset + 256, 256, tiles, 768);
-#else
-        p.gout = tmpb;
+        p.gin = gb3; p.w1 = wt->w2_t; p.w2 = wt->w1_t; p.z = z; p.h = dzb; p.gout = tmpb; p.part_b1 = lnp4 + lnset; p.M = M;
         L2D_HIP(launch_mlp_fused<3>(p, s));
-#endif
-        red.add(dw->b1, lnp4 + lnset, 512, tiles, 512);
-    }
-#ifndef LARA_MLP_BWD_LN
-    {
-        L2D_PROF("gbb_ln_bwd", s);
-        L2D_TRY(ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red));
-    }
-#endif
-#else
-    {
-        L2D_PROF("gbb_dx_mlp", s);
-        // dz = (g2 W2) * gelu'(z); its column sums per 128-row tile (= the pieces of db1) come out of the same epilogue
-        L2D_TRY(gemm_nt<7>(gb3, wt->w2_t, dzb, M, 512, 256, nullptr, z, s, lnp4 + lnset));
         red.add(dw->b1, lnp4 + lnset, 512, (M + 127) / 128, 512);
-        L2D_TRY(gemm_nt<0>(dzb, wt->w1_t, tmpb, M, 256, 512, nullptr, nullptr, s));   // bf16: see ln_bwd_kernel
     }
     {
         L2D_PROF("gbb_ln_bwd", s);
-        L2D_TRY(ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, nullptr, lnp4 + 2 * lnset, M, s, &red));
+        L2D_TRY(ln_bwd(tmpb, true, x1, w->ln2_w, w->eps, g, g, gb2, dw->ln2_w, dw->ln2_b, lnp4 + 2 * lnset, M, s, &red));
     }
-#endif
     // ---- x1 = x0 + cross_attn(norm1(x0), cond, cond) ----
     {
         L2D_PROF("gbb_dx_attn", s);
-        L2D_TRY(gemm_nt<0>(gb2, wt->wo_t, dob, M, 256, 256, nullptr, nullptr, s));
+        L2D_TRY(gemm_nt<0>(gb2, wt->wo_t, dob, M, 256, 256, nullptr, s));
         L2D_LAUNCH_IN_SCOPE(s, group_attn_bwd_kernel, dim3((G + 1) / 2), dim3(256), 0, q, kv, dob, dq, dkv, G, ld_dkv);
-        if (!dkv_ext) L2D_TRY(gemm_nt<1>(dkv, wt->wkv_t, dcond, Mkv, cond_dim, 512, dcond, nullptr, s));
-        L2D_TRY(gemm_nt<0>(dq, wt->wq_t, tmpb, M, 256, 256, nullptr, nullptr, s));
+        if (!dkv_ext) L2D_TRY(gemm_nt<1>(dkv, wt->wkv_t, dcond, Mkv, cond_dim, 512, dcond, s));
+        L2D_TRY(gemm_nt<0>(dq, wt->wq_t, tmpb, M, 256, 256, nullptr, s));
     }
     {
         L2D_PROF("gbb_ln_bwd", s);
-        L2D_TRY(ln_bwd(tmpb, true, x_in, w->ln1_w, w->eps, g, g, gb, dw->ln1_w, dw->ln1_b, nullptr, lnp4 + 3 * lnset, M, s, &red));
+        L2D_TRY(ln_bwd(tmpb, true, x_in, w->ln1_w, w->eps, g, g, gb, dw->ln1_w, dw->ln1_b, lnp4 + 3 * lnset, M, s, &red));
         L2D_TRY(red.launch(s));      // dgamma / dbeta of the three LayerNorms, b2, b1: eight column reductions, one launch
     }
     {
@@ -1558,8 +1505,8 @@ int lara_voltrans_head_backward(int32_t scenes, int32_t R, const float *x, const
     }
     L2D_TRY(colsum_bf16(dog, M, N8, d_bias8, lnpart, s));
     L2D_TRY(gemm_tn(dog, N8, N8, xn, 256, 256, 1, nullptr, M, d_wdeconv, tnpart, s));
-    L2D_TRY(gemm_nt<0>(dog, wdeconv_t, tmpf, M, 256, N8, nullptr, nullptr, s));   // (bf16 rows in the fp32-sized region)
-    L2D_TRY(ln_bwd(tmpf, true, x, ln_w, eps, nullptr, g, nullptr, d_ln_w, d_ln_b, nullptr, lnpart, M, s));
+    L2D_TRY(gemm_nt<0>(dog, wdeconv_t, tmpf, M, 256, N8, nullptr, s));   // (bf16 rows in the fp32-sized region)
+    L2D_TRY(ln_bwd(tmpf, true, x, ln_w, eps, nullptr, g, nullptr, d_ln_w, d_ln_b, lnpart, M, s));
     return LARA2DGS_OK;
 }
 
@@ -1589,7 +1536,7 @@ int lara_layernorm256_backward(int32_t rows, const float *dy, const float *x, co
                                const float *skip, float *dx, float *dgamma, float *dbeta, void *workspace,
                                void *stream) {
     if (rows <= 0 || !dy || !x || !gamma || !dx || !dgamma || !dbeta || !workspace) return LARA2DGS_E_INVALID;
-    return ln_bwd(dy, false, x, gamma, eps, skip, dx, nullptr, dgamma, dbeta, nullptr, (float *)workspace, rows, (hipStream_t)stream);
+    return ln_bwd(dy, false, x, gamma, eps, skip, dx, nullptr, dgamma, dbeta, (float *)workspace, rows, (hipStream_t)stream);
 }
 
 int lara_groupattn_core_backward(int32_t G, const uint16_t *q, const uint16_t *kv, const uint16_t *d_o, uint16_t *dq,

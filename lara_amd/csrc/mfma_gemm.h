@@ -1,5 +1,11 @@
-// mfma_gemm.h -- bf16 MFMA building blocks shared by the attention and encoder-block kernels:
-// LayerNorm+cast, and an LDS-tiled NT GEMM with fused epilogues / implicit 3x3x3 convolution.
+// mfma_gemm.h -- bf16 MFMA building blocks shared by the attention and encoder-block kernels: LayerNorm+cast and three
+// kernels for C[M,N] = A[M,K] . W[N,K]^T (bf16 in, fp32 accumulate) with fused epilogues (the EPI table below):
+//   gemm_bf16_nt_kernel   dense A, 128 x 128 tiles, four workgroups per CU: the HBM-bound products -- the backward's input
+//                         gradients of the linear layers (K = 256 / 512) and the head's transposed convolution (EPI 5);
+//   gemm_ring2_kernel     256 x 256 tiles behind a ring of LDS-DMA tile buffers, finely interleaved: the block's 3x3x3 convolution
+//                         and its input gradient as implicit GEMMs (AMODE 1; EPI 4, 9), and dense products with K % 128 == 0;
+//   gemm_ring_kernel      the same ring, coarsely scheduled: dense products whose K is only a multiple of 32 (the K|V projection
+//                         of a cond_dim that is no multiple of 128, lara_gemm_nt_bf16).
 #pragma once
 #include "common.h"
 #include "wave.h"
@@ -33,11 +39,8 @@ ln_cast_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
     if (stats && lane == 0) stats[tok] = make_float2(mean, rstd);  // lets a later epilogue redo the LN in fp32
 }
 
-// ---- C[M,N] = A[M,K] . W[N,K]^T, bf16 in, fp32 accumulate ------------------------------------------
-// Workgroup tile TM x 128 (TM = 128 or 256), K step 32, four waves as 2x2, wave tile (TM/2) x 64 =
-// (TM/64) x 2 MFMA tiles of 32x32.  TM = 256 halves the operand re-reads through L2 (the implicit
-// convolution at 128x128 moved 10.8 GB per launch through L2 for 0.46 TFLOP of work) and needs six
-// instead of eight ds_read_b128 per eight MFMAs.
+// ---- gemm_bf16_nt_kernel: C[M,N] = A[M,K] . W[N,K]^T, bf16 in, fp32 accumulate -------------------------
+// Workgroup tile 128 x 128, K step 32, four waves as 2x2, wave tile 64 x 64 = 2 x 2 MFMA tiles of 32x32.
 // Operand panels are staged through LDS (double buffered, register staging: the next K tile is
 // loaded into VGPRs while the current one feeds the matrix cores).  Both operands have K contiguous,
 // so a fragment is one ds_read_b128; LDS rows are padded from 64 to 80 bytes, which spreads the 16
@@ -45,47 +48,30 @@ ln_cast_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
 // (conflict free).  MFMA 32x32x16 operand map: A[i = lane&31][k = 8*(lane>>5) + e],
 // B[k = 8*(lane>>5) + e][j = lane&31]; C/D: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 //
-// AMODE 1 turns the A operand into the im2col view of a 3x3x3, padding-1 convolution without ever
+// AMODE 1 (the ring kernels) turns the A operand into the im2col view of a 3x3x3, padding-1 convolution without ever
 // materialising it: activations are channels-last rows of a volume of edge R whose rows are ordered
 // group-major (2x2x2 voxel blocks, the order the attention works in), K = 27 * Cin, and K tile kt
 // reads channels [32 kc, 32 kc + 32) of the row of the voxel's (dz, dy, dx) neighbour (zeros outside
-// the volume); W is the weight re-laid as [Cout][tap][Cin], i.e. still K-contiguous.
+// the volume); W is the weight re-laid as [Cout][tap][Cin], i.e. still K-contiguous.  (It ran on this kernel too, on
+// 256 x 128 tiles, until the ring kernels took it: at 128 x 128 it moved 10.8 GB per launch through L2 for 0.46 TFLOP of work.)
 constexpr int GK = 32;
 constexpr int LROW = GK * 2 + 16;  // padded LDS row, bytes
 
 struct GemmP {
     const unsigned short *A, *W;
     void *C;
-    const float *resid;  // EPI 1, 3, 4: fp32 [M, N]
-    const float *bias;   // EPI 2, 3, 5: fp32 [N] (EPI 5: [Cout])
+    const float *resid;  // EPI 1, 4, 9: fp32 [M, N]
+    const float *bias;   // EPI 5: fp32 [Cout]
     int M, N, K;
     int R, Cin;          // AMODE 1 / EPI 5: volume edge, input channels
-    const float2 *stats; // EPI 4: per-row (mean, rstd) of resid
-    const float *gamma, *beta;
+    const float2 *stats; // EPI 4, 9: per-row (mean, rstd) of resid / of lnx
+    const float *gamma, *beta;   // EPI 4; EPI 9: gamma
     int Cout;            // EPI 5
     uint32_t zero_off;   // AMODE 1: byte offset from A of a zeroed row of Cin bf16 (the padding voxels)
-    unsigned short *C2;  // EPI 6: bf16 [M, N] pre-activation out; EPI 7: the same, read
-    float *colsum;       // EPI 7 (gemm_bf16_nt_kernel, optional): [row tiles of 128][N] column sums of the stored bf16 values per row tile;
-                         // EPI 9: [row tiles of 256][3][256] partial column sums (dgamma, dbeta, the bias gradient behind the LayerNorm)
+    unsigned short *C2;  // EPI 9: bf16 [M, 256] out, the fp32 result rounded
+    float *colsum;       // EPI 9: [row tiles of 256][3][256] partial column sums (dgamma, dbeta, the bias gradient behind the LayerNorm)
     const float *lnx;    // EPI 9: fp32 [M, 256], the input of the LayerNorm whose backward the epilogue runs (stats = its mean, rstd)
 };
-
-// 0.5 x (1 + erf(x / sqrt 2)) with erf from Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7) on v_exp / v_rcp
-__device__ __forceinline__ float gelu_erf_grad(const float x) {  // Phi(x) + x phi(x)
-    const float z = fabsf(x) * 0.70710678f;
-    const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float ex = __expf(-z * z);
-    const float cdf = 0.5f * (1.0f + copysignf(1.0f - poly * ex, x));
-    return cdf + x * ex * 0.3989422804f;
-}
-__device__ __forceinline__ float gelu_erf(const float x) {
-    const float z = fabsf(x) * 0.70710678f;
-    const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erf_abs = 1.0f - poly * __expf(-z * z);
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
 
 // row of the group-major token order <-> voxel (b, d, h, w); Gd = R / 2 blocks per edge
 __device__ __forceinline__ void token_to_voxel(const int m, const int R, int &b, int &d, int &h, int &w) {
@@ -122,43 +108,25 @@ __device__ __forceinline__ void xcd_tile(int &rt, int &ct) {
     }
 }
 
-// EPI 0: bf16 store            1: fp32 store of acc + resid        2: bf16 store of gelu(acc + bias)
-//     3: fp32 acc + bias + resid   4: fp32 LN(resid row) + acc (LN redone from stats, gamma, beta)
+// EPI 0: bf16 store            1: fp32 store of acc + resid
+//     4: fp32 LN(resid row) + acc (LN redone from stats, gamma, beta)
 //     5: fp32 acc + bias scattered as a stride-2, kernel-2 transposed convolution (N = 8 * Cout)
-// (training, gemm_bf16_nt_kernel only)
-//     6: z = acc + bias -> bf16 C2, gelu(z) -> bf16 C       7: bf16 store of acc * gelu'(C2)
-//     8: fp32 store
+//     8: fp32 store            9: gemm_ring2_kernel only, see ring_epilogue_lnbwd
+// (2, 3, 6, 7 were the bias / GELU / GELU' epilogues of the MLP's separate products, until mlp_fused.h; the numbers stay retired.)
 // The fused epilogues, applied to four consecutive columns (row, col .. col + 3) of the accumulator tile; `base_out`
-// is EPI 5's output offset of the row's voxel (2d, 2h, 2w).  Shared by both GEMM kernels.
+// is EPI 5's output offset of the row's voxel (2d, 2h, 2w).  Shared by the three GEMM kernels.
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue(const GemmP &p, float4 v, const int row, const int col, const int N,
-                                              const unsigned long long base_out, float4 *stored = nullptr) {
+                                              const unsigned long long base_out) {
+    static_assert(EPI == 0 || EPI == 1 || EPI == 4 || EPI == 5 || EPI == 8, "the epilogues that exist");
     const size_t o = (size_t)row * N + col;
-    if (EPI == 2 || EPI == 3 || EPI == 6) {
-        const float4 bs = *(const float4 *)(p.bias + col);
-        v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w;
-    }
-    if (EPI == 0 || EPI == 2 || EPI == 6 || EPI == 7) {
-        if (EPI == 6) {
-            ushort4 z;
-            z.x = f2bf(v.x); z.y = f2bf(v.y); z.z = f2bf(v.z); z.w = f2bf(v.w);
-            *(ushort4 *)(p.C2 + o) = z;
-        }
-        if (EPI == 7) {
-            const ushort4 z = *(const ushort4 *)(p.C2 + o);
-            v.x *= gelu_erf_grad(bf2f(z.x)); v.y *= gelu_erf_grad(bf2f(z.y));
-            v.z *= gelu_erf_grad(bf2f(z.z)); v.w *= gelu_erf_grad(bf2f(z.w));
-        }
-        if (EPI == 2 || EPI == 6) {  // erf GELU (nn.GELU's default); the result is rounded to bf16 anyway
-            v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
-        }
+    if (EPI == 0) {
         ushort4 h;
         h.x = f2bf(v.x); h.y = f2bf(v.y); h.z = f2bf(v.z); h.w = f2bf(v.w);
         *(ushort4 *)((unsigned short *)p.C + o) = h;
-        if (stored) *stored = make_float4(bf2f(h.x), bf2f(h.y), bf2f(h.z), bf2f(h.w));     // (what a later column sum of C would add up)
     } else if (EPI == 8) {
         *(float4 *)((float *)p.C + o) = v;
-    } else if (EPI == 1 || EPI == 3) {
+    } else if (EPI == 1) {
         const float4 rs = *(const float4 *)(p.resid + o);
         *(float4 *)((float *)p.C + o) = make_float4(v.x + rs.x, v.y + rs.y, v.z + rs.z, v.w + rs.w);
     } else if (EPI == 4) {
@@ -177,9 +145,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP &p, float4 v, const in
     }
 }
 
+// (AMODE, GM and GN keep their places in the list so that the kernel's symbol stays what the committed profiles know)
 template <int AMODE, int EPI, int GM = 128, int GN = 128>
 __global__ void __launch_bounds__(256)
 gemm_bf16_nt_kernel(const GemmP p) {
+    static_assert(AMODE == 0 && GM == 128 && GN == 128, "dense A on 128 x 128 tiles; the convolution runs on the ring kernels");
     constexpr int MI = GM / 64;         // 32-row MFMA tiles per wave along M
     constexpr int NJ = GN / 64;         // 32-column MFMA tiles per wave along N
     constexpr int NA = GM / 64;         // staging passes that carry A rows
@@ -194,7 +164,7 @@ gemm_bf16_nt_kernel(const GemmP p) {
     const int wm = (wave >> 1) * (GM / 2), wn = (wave & 1) * (GN / 2);
     const int r = lane & 31, kh = lane >> 5;
 
-    // staging map: GM + 128 rows (A rows, then W rows) x 4 sixteen-byte chunks per K tile; thread t
+    // staging map: 256 rows (A rows, then W rows) x 4 sixteen-byte chunks per K tile; thread t
     // moves chunk (t & 3) of rows (t >> 2) + 64 i, i = 0..NS-1 (i < NA: A rows, else W rows)
     // rows are dealt so that the 16 lanes of a store group hit rows {0, 4, 8, 12} + c: with 80-byte rows
     // those start 0, 64, 128, 192 bytes into the 256-byte bank row (rows 0..3 would wrap onto each other)
@@ -205,54 +175,27 @@ gemm_bf16_nt_kernel(const GemmP p) {
     const char *Ab = (const char *)A, *Wb = (const char *)W;
     uint32_t goff[NS];
     int loff[NS];
-    int vb[NA], vd[NA], vh[NA], vw[NA];
 #pragma unroll
     for (int i = 0; i < NS; i++) {
         const int row = srow + 64 * i;  // A rows then W rows
-        goff[i] = row < GM ? (uint32_t)min(bm0 + row, M - 1) * (uint32_t)((AMODE ? p.Cin : K) * 2) + schunk * 16
+        goff[i] = row < GM ? (uint32_t)min(bm0 + row, M - 1) * (uint32_t)(K * 2) + schunk * 16
                            : (uint32_t)min(bn0 + row - GM, N - 1) * (uint32_t)(K * 2) + schunk * 16;
         loff[i] = row * LROW + schunk * 16;
-        if (AMODE == 1 && i < NA) token_to_voxel(min(bm0 + row, M - 1), p.R, vb[i < NA ? i : 0], vd[i < NA ? i : 0], vh[i < NA ? i : 0], vw[i < NA ? i : 0]);
     }
     const int ktiles = K / GK;               // K is a multiple of 32 (checked by the callers)
-    const int kpt = AMODE ? p.Cin / GK : 1;  // K tiles per filter tap
     // (staging registers are named scalars, not an array: an indexed private array ends up in scratch)
-    const uint4 z4 = make_uint4(0, 0, 0, 0);
-    uint4 st0 = z4, st1 = z4, st2 = z4, st3 = z4, st4 = z4, st5 = z4, st6 = z4, st7 = z4;
-    uint32_t noff[NA];
-#pragma unroll
-    for (int i = 0; i < NA; i++) noff[i] = 0;
-    // pass i of the staging map: from A (dense row or the current tap's neighbour row) or from W
-#define L2D_GSRC(i) ((i) < NA ? (AMODE == 1 ? Ab + (noff[(i) < NA ? (i) : 0] + kcb) : Ab + (goff[i] + kb)) : Wb + (goff[i] + kb))
-    auto gload = [&](int kt) {
+    static_assert(NS == 4 && NA == 2, "the four staging passes below");
+    const uint4 z4 = make_uint4(0, 0, 0, 0);   // (the initialisers stay: without them the staging registers come out allocated in another order)
+    uint4 st0 = z4, st1 = z4, st2 = z4, st3 = z4;
+    auto gload = [&](int kt) {   // passes 0, 1: A rows; 2, 3: W rows
         const uint32_t kb = (uint32_t)kt * (GK * 2);
-        uint32_t kcb = 0;
-        if (AMODE == 1) {
-            const int tap = kt / kpt, kc = kt - tap * kpt;
-            if (kc == 0) {  // a new filter tap: resolve this thread's neighbour rows once for its kpt K tiles
-                const int dz = tap / 9 - 1, dy = (tap / 3) % 3 - 1, dx = tap % 3 - 1;
-#pragma unroll
-                for (int i = 0; i < NA; i++) {
-                    const int nd = vd[i] + dz, nh = vh[i] + dy, nw = vw[i] + dx;
-                    const bool in = (unsigned)nd < (unsigned)p.R && (unsigned)nh < (unsigned)p.R && (unsigned)nw < (unsigned)p.R;
-                    // outside the volume: a row of zeros the caller keeps next to the activations (no branch)
-                    noff[i] = (in ? (uint32_t)voxel_to_token(vb[i], nd, nh, nw, p.R) * (uint32_t)(p.Cin * 2) : p.zero_off) + schunk * 16;
-                }
-            }
-            kcb = (uint32_t)kc * (GK * 2);
-        }
-        st0 = *(const uint4 *)L2D_GSRC(0); st1 = *(const uint4 *)L2D_GSRC(1);
-        st2 = *(const uint4 *)L2D_GSRC(2); st3 = *(const uint4 *)L2D_GSRC(3);
-        if (NS > 4) { st4 = *(const uint4 *)L2D_GSRC(NS > 4 ? 4 : 0); st5 = *(const uint4 *)L2D_GSRC(NS > 5 ? 5 : 0); }
-        if (NS > 6) { st6 = *(const uint4 *)L2D_GSRC(NS > 6 ? 6 : 0); st7 = *(const uint4 *)L2D_GSRC(NS > 7 ? 7 : 0); }
+        st0 = *(const uint4 *)(Ab + (goff[0] + kb)); st1 = *(const uint4 *)(Ab + (goff[1] + kb));
+        st2 = *(const uint4 *)(Wb + (goff[2] + kb)); st3 = *(const uint4 *)(Wb + (goff[3] + kb));
     };
-#undef L2D_GSRC
     auto lstore = [&](int buf) {
         unsigned char *l = &lds[buf][0];
         *(uint4 *)(l + loff[0]) = st0; *(uint4 *)(l + loff[1]) = st1;
         *(uint4 *)(l + loff[2]) = st2; *(uint4 *)(l + loff[3]) = st3;
-        if (NS > 4) { *(uint4 *)(l + loff[NS > 4 ? 4 : 0]) = st4; *(uint4 *)(l + loff[NS > 5 ? 5 : 0]) = st5; }
-        if (NS > 6) { *(uint4 *)(l + loff[NS > 6 ? 6 : 0]) = st6; *(uint4 *)(l + loff[NS > 7 ? 7 : 0]) = st7; }
     };
 
     f32x16 acc[MI][NJ];
@@ -299,7 +242,6 @@ gemm_bf16_nt_kernel(const GemmP p) {
     // 16-byte row-contiguous loads of the residual and 16-byte stores.
     float *ep = (float *)&lds[0][0] + wave * (32 * 68);  // 32 rows x (64 + 4 pad) floats per wave
     unsigned long long *rowbase = (unsigned long long *)((float *)&lds[0][0] + 4 * (32 * 68)) + wave * 32;  // EPI 5
-    float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);          // EPI 7: this thread's share of the tile's column sums
 #pragma unroll
     for (int ij = 0; ij < MI * (NJ / 2); ij++) {
         const int i = ij / (NJ / 2), jh = ij % (NJ / 2);  // 32 rows x 64 columns of the wave tile per trip
@@ -320,33 +262,14 @@ gemm_bf16_nt_kernel(const GemmP p) {
         for (int q = 0; q < 8; q++) {
             const int idx = q * 64 + lane, lr = idx >> 4, c4 = (idx & 15) * 4;
             const int row = bm0 + wm + i * 32 + lr, col = bn0 + wn + jh * 64 + c4;
-            if (row < M && col < N) {
-                if (EPI == 7 && NJ == 2) {
-                    float4 st;
-                    gemm_epilogue<EPI>(p, *(const float4 *)(ep + lr * 68 + c4), row, col, N, 0ull, &st);
-                    cs.x += st.x; cs.y += st.y; cs.z += st.z; cs.w += st.w;
-                } else {
-                    gemm_epilogue<EPI>(p, *(const float4 *)(ep + lr * 68 + c4), row, col, N, EPI == 5 ? rowbase[lr] : 0ull);
-                }
-            }
+            if (row < M && col < N)
+                gemm_epilogue<EPI>(p, *(const float4 *)(ep + lr * 68 + c4), row, col, N, EPI == 5 ? rowbase[lr] : 0ull);
         }
-    }
-    // EPI 7: the bias gradient of the layer in front is the column sum of what was just stored.  A thread holds four columns of
-    // 16 of the wave's 64 rows; the four lane groups add up with two shuffles, the two waves of a column half through LDS, and the
-    // workgroup leaves one row of per-tile sums (a separate pass over C would read it all again: 134 MB per block of LaRa's encoder)
-    if (EPI == 7 && NJ == 2 && p.colsum) {
-        cs.x += __shfl_xor(cs.x, 16); cs.y += __shfl_xor(cs.y, 16); cs.z += __shfl_xor(cs.z, 16); cs.w += __shfl_xor(cs.w, 16);
-        cs.x += __shfl_xor(cs.x, 32); cs.y += __shfl_xor(cs.y, 32); cs.z += __shfl_xor(cs.z, 32); cs.w += __shfl_xor(cs.w, 32);
-        __syncthreads();
-        float *cb = (float *)&lds[0][0];      // [2 row halves][GN]
-        if (lane < 16) *(float4 *)(cb + (wave >> 1) * GN + wn + lane * 4) = cs;
-        __syncthreads();
-        if (tid < GN && bn0 + tid < N) p.colsum[(size_t)rt_ * N + bn0 + tid] = cb[tid] + cb[GN + tid];
     }
 }
 
 // ---- the same GEMM family on a 256 x 256 tile with an LDS-DMA ring ------------------------------------
-// Same operands, AMODE and EPI as gemm_bf16_nt_kernel, restructured around what limited that kernel
+// Same operands and EPI as gemm_bf16_nt_kernel (gemm_ring2_kernel: plus AMODE 1), restructured around what limited that kernel
 // (DESIGN.md section 3.4): register staging put as many LDS cycles into ds_write_b128 (13 cycles per
 // wave instruction) as into fragment reads, and the 3x3x3 convolution re-read its gathered operand
 // through L2 once per 128 output columns.  Here
@@ -499,6 +422,7 @@ __device__ __forceinline__ void ring_epilogue_lnbwd(const GemmP &p, f32x16 (&acc
 template <int AMODE, int EPI>
 __global__ void __launch_bounds__(512)
 gemm_ring_kernel(const GemmP p) {
+    static_assert(AMODE == 0 && EPI != 9, "dense A only: the convolution (AMODE 1; EPI 4, 9) runs on gemm_ring2_kernel");
     extern __shared__ __attribute__((aligned(16))) unsigned char ring[];  // RING * RTILE bytes
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int M = p.M, N = p.N, K = p.K, Cin = AMODE ? p.Cin : 0;
@@ -512,6 +436,8 @@ gemm_ring_kernel(const GemmP p) {
     // staging: wave w moves pieces {2w, 2w+1} of the A panel and of the W panel; piece i = rows 16 i ..
     // 16 i + 15, lane L lands in row 16 i + L/4, physical chunk L & 3, and must therefore FETCH the
     // logical chunk (L & 3) ^ ((row >> 2) & 3)
+    // (The AMODE 1 lines of this block are dead under the static_assert above.  They stay: without them the compiler allocates this
+    // kernel's fragment registers in another order, and refactors of this header are held to identical device code.)
     int srow[2];
     uint32_t woff[2], noff[2];
     int vb[2], vd[2], vh[2], vw[2];
@@ -645,7 +571,7 @@ gemm_ring_kernel(const GemmP p) {
     }
     __syncthreads();
 
-    ring_epilogue<EPI == 9 ? 1 : EPI>(p, acc, ring, wave, lane, bm0, bn0, wr, wc);   // (EPI 9 exists on gemm_ring2_kernel only)
+    ring_epilogue<EPI>(p, acc, ring, wave, lane, bm0, bn0, wr, wc);
 }
 
 // ---- the ring kernel, finely interleaved --------------------------------------------------------------
@@ -674,7 +600,8 @@ gemm_ring_kernel(const GemmP p) {
 // epilogue and waits -- parity-green, 485 us against 400: the W panel then travels once per 128 rows, 6 pieces per wave and K tile
 // instead of 4, and the pieces are what this loop pays for.  The block's MLP products (K = 256 / 512, HBM-bound at 94-104 us) on this
 // kernel: 99-102 us, no gain over gemm_bf16_nt_kernel's four workgroups per CU.
-// Needs K % 128 == 0 (and Cin % 128 == 0 for the convolution); launch_gemm_ring falls back to gemm_ring_kernel otherwise.
+// Needs K % 128 == 0 (and Cin % 128 == 0 for the convolution); launch_gemm_ring falls back to gemm_ring_kernel for a dense
+// product otherwise and has nothing for such a convolution (LaRa's has 256 channels).
 template <int AMODE, int EPI>
 __global__ void __launch_bounds__(512)
 gemm_ring2_kernel(const GemmP p) {
@@ -855,23 +782,25 @@ gemm_ring2_kernel(const GemmP p) {
     else ring_epilogue<EPI == 9 ? 1 : EPI>(p, acc, ring, wave, lane, bm0, bn0, wr, wc);
 }
 
-// host-side launch of the ring kernel (dynamic LDS above the 64 KB default needs the attribute once)
+// host-side launch of the ring kernels (dynamic LDS above the 64 KB default needs the attribute once)
 template <int AMODE, int EPI>
 static inline hipError_t launch_gemm_ring(const GemmP &p, hipStream_t s) {
-    static const hipError_t attr = hipFuncSetAttribute((const void *)gemm_ring_kernel<AMODE, EPI>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, RING * RTILE);
-    if (attr != hipSuccess) return attr;
+    const dim3 grid((p.M + RT - 1) / RT, (p.N + RT - 1) / RT);
     // EPI 9's row sums need a tile that holds WHOLE rows of the LayerNorm, its saved statistics and its outputs
     if (EPI == 9 && (p.N != RT || !p.lnx || !p.stats || !p.colsum || !p.C2 || !p.gamma)) return hipErrorInvalidValue;
     if (p.K % 128 == 0 && (!AMODE || p.Cin % 128 == 0)) {
         static const hipError_t attr2 = hipFuncSetAttribute((const void *)gemm_ring2_kernel<AMODE, EPI>,
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, RING * RTILE);
         if (attr2 != hipSuccess) return attr2;
-        return L2D_LAUNCH_ERR(s, (gemm_ring2_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512), RING * RTILE, p);
+        return L2D_LAUNCH_ERR(s, (gemm_ring2_kernel<AMODE, EPI>), grid, dim3(512), RING * RTILE, p);
     }
-    if (EPI == 9) return hipErrorInvalidValue;   // (the fused LayerNorm backward needs gemm_ring2_kernel's shapes: callers check ring2_shape)
-    return L2D_LAUNCH_ERR(s, (gemm_ring_kernel<AMODE, EPI>), dim3((p.M + RT - 1) / RT, (p.N + RT - 1) / RT), dim3(512), RING * RTILE, p);
+    if constexpr (AMODE == 0) {   // a dense product whose K is only a multiple of 32
+        static const hipError_t attr = hipFuncSetAttribute((const void *)gemm_ring_kernel<AMODE, EPI>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, RING * RTILE);
+        if (attr != hipSuccess) return attr;
+        return L2D_LAUNCH_ERR(s, (gemm_ring_kernel<AMODE, EPI>), grid, dim3(512), RING * RTILE, p);
+    }
+    return hipErrorInvalidValue;   // a convolution that is not of gemm_ring2_kernel's shape: nothing is built for it
 }
-static inline bool ring2_shape(const GemmP &p, const int amode) { return p.K % 128 == 0 && (!amode || p.Cin % 128 == 0); }
 
 }  // namespace

@@ -34,36 +34,26 @@
 
 namespace {
 
-#ifndef MF_TIMING
-#define MF_TIMING 0                        // timing-only builds (results invalid; tools/build_variant.sh -DMF_TIMING=n): 1 = no epilogue, 8 = no weight stream,
-#endif                                     // 2 = no products (weight stream + MFMAs), 4 = no phase 0
-// NW = waves per workgroup: 8 (128 token rows, one workgroup per CU) or 4 (64 rows, 69 KB of LDS: TWO workgroups per CU, whose
-// memory phases -- the tile's rows in, the results out -- run under the other one's products; the weights then travel L2 -> LDS twice
-// as often, 1 GB per layer at LaRa's size).
-#ifndef MF_NW
-#define MF_NW 8
-#endif
+// Eight waves per workgroup: 128 token rows, one workgroup per CU.  (Four waves on 64 rows, 69 KB of LDS, two workgroups per CU
+// whose memory phases run under each other's products, measured 256.8 us against 174.3: the weights then travel L2 -> LDS twice
+// as often.  Holding back every other first-round workgroup to put the chip's halves out of phase: 170.1 - 186.9 against 171.6.
+// Those, and the timing-only builds that left out one phase at a time: profiles/r06_mlp_fused_phases.txt.)
+constexpr int MF_WAVES = 8;
 constexpr int MF_SLOT = 16384;             // bytes per weight slot
 constexpr int MF_CONST = 5 * 1024;         // b1 (512) | b2 (256) | ln3 gamma (256) | ln3 beta (256) floats
-#ifndef MF_SLOTS0
-#define MF_SLOTS0 4        // ring slots of the inference instantiation
-#endif
-#ifndef MF_SLOTS1
-#define MF_SLOTS1 4        // ... of the training forward and the backward (z chunk resident)
-#endif
-template <int NW, int MODE = 1> struct MfCfg {
-    static constexpr int TM = 16 * NW;                     // token rows per workgroup
+template <int MODE> struct MfCfg {
+    static constexpr int TM = 16 * MF_WAVES;                  // token rows per workgroup
     // (Ring depth, measured on one box, inference / training forward + backward products: 4 slots 171.6 / 455 + 145 us, 5 and 3
     // slots 179.5 / 460 + 153, 6 and 4: 182.8 / 458 + 147, 7 and 5: 183.4 / 456 + 148 -- more bytes in flight do not speed the
-    // weight stream up; -DMF_SLOTS0 / -DMF_SLOTS1 for A/B builds.)
-    static constexpr int SLOTS = NW == 8 ? (MODE == 0 ? MF_SLOTS0 : MF_SLOTS1) : 3;          // ring
+    // weight stream up.)
+    static constexpr int SLOTS = 4;                        // ring
     static constexpr int AHEAD = SLOTS - 2;                // slots in flight behind the one being multiplied (see the loop)
-    static constexpr int PW = 16 / NW;                     // one-KB pieces of a slot per wave
+    static constexpr int PW = 16 / MF_WAVES;                  // one-KB pieces of a slot per wave
     static constexpr int HC = TM * 256;                    // the hidden chunk: [4 panels of 32 units][TM tokens][64 B]
     static constexpr int ZC = MODE == 0 ? 0 : TM * 256;    // the chunk's pre-activations z, same layout (training forward: out; backward: in)
     static constexpr int LDS = HC + ZC + SLOTS * MF_SLOT + MF_CONST;   // (phase 0's TM x 512 B of normalised rows and the
                                                                        // epilogue's bounce tiles alias the chunk + ring region)
-    static_assert(HC + SLOTS * MF_SLOT >= TM * 512 && HC + SLOTS * MF_SLOT >= NW * 8704 + 2048, "phase 0 / the epilogue alias chunk + ring");
+    static_assert(HC + SLOTS * MF_SLOT >= TM * 512 && HC + SLOTS * MF_SLOT >= MF_WAVES * 8704 + 2048, "phase 0 / the epilogue alias chunk + ring");
     static_assert(LDS <= 163840, "one workgroup's LDS");
 };
 
@@ -78,28 +68,46 @@ struct MlpP {
     unsigned short *xn2, *z, *h;      // TRAIN: bf16 [M, 256], [M, 512], [M, 512]
     float eps;
     int M;
-    // MODE 2 (the backward of the same chain, see mlp_fused_kernel): w1 = W2^T [512, 256], w2 = W1^T [256, 512]; x1, ln2_w, eps, z as
-    // above (z is READ); h = dz out (bf16 [M, 512])
+    // MODE 3 (the backward's products, see mlp_fused_kernel): w1 = W2^T [512, 256], w2 = W1^T [256, 512]; z as above (READ);
+    // h = dz out (bf16 [M, 512])
     const unsigned short *gin;        // bf16 [M, 256]: the gradient of x2 (what norm3's backward left)
-    float *g;                         // fp32 [M, 256] in / out: the residual stream's gradient; out = g + norm2's backward
-    unsigned short *gout;             // bf16 [M, 256] out: the same, rounded
-    float *part_ln;                   // [row tiles][3][256]: per-tile column sums of dy xhat, dy, out (dgamma, dbeta of norm2, -)
+    float *g;                         // (no reader since MODE 2 left; stays, with part_ln: the kernels' argument offsets would move)
+    unsigned short *gout;             // bf16 [M, 256] out: dy, the gradient of norm2's output
+    float *part_ln;
     float *part_b1;                   // [row tiles][512]: per-tile column sums of dz (the bias gradient of fc1)
 };
 
-// MODE 0: inference forward; 1: training forward (TRAIN); 2: the BACKWARD of the same chain, which has the same shape --
+// MODE 0: inference forward; 1: training forward (TRAIN); 3: the products of the BACKWARD of the same chain, which has the same shape --
 //     dz = (g2 . W2) * gelu'(z)            <-> fc1 with W2^T as its weight, the activation a product with gelu'(z) read from HBM
 //     dy = dz . W1   (rounded to bf16)      <-> fc2 with W1^T as its weight
-//     g  = g + norm2_backward(dy; x1)       <-> the epilogue
-// (network.py:94 backwards; rounds 2-5: two products, 175 us, + a LayerNorm backward pass, 98 us, per layer.)  Phase 0 copies the bf16
-// gradient rows into the fragment layout (no LayerNorm); the chunk's dz leaves through LDS for the weight gradient of fc1, its
-// per-tile column sums (fc1's bias gradient) are taken on the way; the epilogue re-deals the tile so that a wave owns WHOLE rows
-// (64 rows x 256 floats at a time through LDS) and runs ln_bwd_kernel's arithmetic on them, operation for operation.
+// (network.py:94 backwards; rounds 2-5: two products, 175 us per layer.)  Phase 0 copies the bf16 gradient rows into the fragment
+// layout (no LayerNorm); the chunk's dz leaves through LDS for the weight gradient of fc1, its per-tile column sums (fc1's bias
+// gradient) are taken on the way; dy leaves row-contiguous through LDS.  (MODE 2 was the same with norm2's backward in the epilogue,
+// a wave owning whole rows: measured slower than the pass of its own, profiles/r06_mlp_fused_phases.txt; the number stays retired.)
+
+// 0.5 x (1 + erf(x / sqrt 2)) with erf from Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7) on v_exp / v_rcp
+__device__ __forceinline__ float gelu_erf_grad(const float x) {  // Phi(x) + x phi(x)
+    const float z = fabsf(x) * 0.70710678f;
+    const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
+    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+    const float ex = __expf(-z * z);
+    const float cdf = 0.5f * (1.0f + copysignf(1.0f - poly * ex, x));
+    return cdf + x * ex * 0.3989422804f;
+}
+__device__ __forceinline__ float gelu_erf(const float x) {      // erf GELU (nn.GELU's default)
+    const float z = fabsf(x) * 0.70710678f;
+    const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
+    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+    const float erf_abs = 1.0f - poly * __expf(-z * z);
+    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
+}
+
 template <int MODE, int NW>
 __global__ void __launch_bounds__(64 * NW)
 mlp_fused_kernel(const MlpP p) {
+    static_assert((MODE == 0 || MODE == 1 || MODE == 3) && NW == MF_WAVES, "the instantiations that exist");
     constexpr bool TRAIN = MODE == 1;
-    using Cfg = MfCfg<NW, MODE>;
+    using Cfg = MfCfg<MODE>;
     constexpr int TM = Cfg::TM, PANEL = TM * 64, MF_SLOTS = Cfg::SLOTS, MF_AHEAD = Cfg::AHEAD, PW = Cfg::PW, MF_HC = Cfg::HC;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char *const hc = lds;                       // hidden chunk
@@ -115,14 +123,6 @@ mlp_fused_kernel(const MlpP p) {
     // fc2 wave tile: tokens wr * 64 .. + 64, outputs wc * 64 .. + 64
     const int wr = wave >> 2, wc = wave & 3;
 
-#ifdef MF_STAGGER
-    // Stagger: the workgroups of a round run their phases in lock-step -- every CU reads its rows at the same time, then every CU
-    // streams the weights from L2, then every CU writes -- so each shared resource is idle two thirds of the time.  Holding back every
-    // other workgroup of the FIRST round by about half a tile's time puts the two halves of the chip out of phase for the rest of the
-    // launch (a tile takes the same time everywhere, so the offset persists).
-    if (blockIdx.x < 256 && (blockIdx.x & 1))
-        for (int i = 0; i < MF_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-#endif
     // ---- the weight stream: slot n of a tile = (chunk c = n / 8, k = n % 8): k < 4: W1 rows c*128 .. +128, channels 64 k .. +64 as
     //      two 32-channel sub-tiles [2][128 rows][64 B]; k >= 4: W2 rows 0 .. 256, hidden units c*128 + 32 (k-4) .. +32 as [256 rows][64 B].
     //      A slot is 16 one-KB pieces (16 rows x 64 B, lane L -> row L / 4, physical chunk L & 3 = logical chunk ^ ((row >> 2) & 3));
@@ -148,7 +148,6 @@ mlp_fused_kernel(const MlpP p) {
 #define MF_DMA(base, voff, ldsaddr) \
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"((uint32_t)(ldsaddr)), "v"((uint32_t)(voff)), "s"(base) : "memory")
     auto issue = [&](const int n) {      // this wave's pieces of slot n (n < 32)
-        if (MF_TIMING & 8) return;       // (timing-only: no weight stream -- the products run on whatever the ring holds)
         const int c = n >> 3, k = n & 7;
         const uint32_t dst = ring_a + (n % MF_SLOTS) * MF_SLOT;
 #pragma unroll
@@ -159,14 +158,12 @@ mlp_fused_kernel(const MlpP p) {
     };
 
     // ---- phase 0: norm2 of the tile's rows -> bf16 -> LDS [8 panels of 32 channels][128 tokens][64 B] (aliases chunk + ring)
-    if (MODE >= 2) {
-        if (MODE == 2 && tid < 64) ((float4 *)cst)[tid] = ((const float4 *)p.ln2_w)[tid];      // gamma of norm2
-    } else
+    if (MODE != 3)
     for (int t = tid; t < 320; t += 64 * NW) {      // the constants: b1 | b2 | gamma3 | beta3
         const float *src = t < 128 ? p.b1 + t * 4 : t < 192 ? p.b2 + (t - 128) * 4 : t < 256 ? p.ln3_w + (t - 192) * 4 : p.ln3_b + (t - 256) * 4;
         ((float4 *)cst)[t] = *(const float4 *)src;
     }
-    if (MODE >= 2) {
+    if (MODE == 3) {
         uint2 v[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) v[i] = ((const uint2 *)(p.gin + (size_t)min(bm0 + wave * 16 + i, M - 1) * 256))[lane];
@@ -175,7 +172,7 @@ mlp_fused_kernel(const MlpP p) {
             const int tok = wave * 16 + i;
             *(uint2 *)(lds + (lane >> 3) * PANEL + tok * 64 + ((((lane & 7) >> 1) ^ ((tok >> 2) & 3)) << 4) + (lane & 1) * 8) = v[i];
         }
-    } else if (!(MF_TIMING & 4)) {
+    } else {
         const float4 g = ((const float4 *)p.ln2_w)[lane], be = ((const float4 *)p.ln2_b)[lane];
         float4 v[16];
 #pragma unroll
@@ -222,7 +219,7 @@ mlp_fused_kernel(const MlpP p) {
 #pragma unroll
             for (int e = 0; e < 16; e++) acc2[i][j][e] = 0.f;
     f32x16 acc1[2];
-    float *const csum = cst + 256;                 // MODE 2, 3: [NW waves][128] column sums of the chunk's dz
+    float *const csum = cst + 256;                 // MODE 3: [NW waves][128] column sums of the chunk's dz
     (void)csum; (void)zc;
 
     // fragment offsets inside a slot / the chunk: row * 64 + ((K step's chunk pair 2 s + kh) ^ ((row >> 2) & 3)) * 16
@@ -239,7 +236,6 @@ mlp_fused_kernel(const MlpP p) {
     // reading that one before it arrived at barrier n - 1, which this wave has passed -- hence SLOTS >= AHEAD + 2), wait for this
     // wave's pieces of slot n (counted: the 2 AHEAD younger pieces stay in flight; on gfx9 vector memory operations retire in issue
     // order, so younger STORES in the queue only make the wait conservative), barrier, multiply.
-    if (!(MF_TIMING & 2)) {
 #pragma unroll
     for (int n = 0; n < MF_AHEAD; n++) issue(n);
 #pragma unroll 1
@@ -261,7 +257,7 @@ mlp_fused_kernel(const MlpP p) {
                 static_assert(kMaxYounger <= 12, "add cases below");
                 // (the backward's z pieces are requested at k == 0 behind that trip's slot and are needed at k == 3: with AHEAD <= 3 every
                 // piece the k == 3 wait leaves outstanding is younger than they are)
-                static_assert(MODE < 2 || MF_AHEAD <= 3, "the z chunk's pieces would be among the outstanding ones at k == 3");
+                static_assert(MODE != 3 || MF_AHEAD <= 3, "the z chunk's pieces would be among the outstanding ones at k == 3");
                 switch (younger) {
                 case 0: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
                 case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
@@ -273,7 +269,7 @@ mlp_fused_kernel(const MlpP p) {
                 }
             }
             const unsigned char *slot = ring + (n % MF_SLOTS) * MF_SLOT;
-            if (MODE >= 2 && k == 0) {
+            if (MODE == 3 && k == 0) {
                 // the chunk's pre-activations z [TM tokens x 128 units] into LDS, in the chunk buffer's layout, by DMA: 4 TM / 16 one-KB
                 // pieces (16 tokens x 32 units each), 16-byte row-contiguous reads (the accumulator layout's own 8-byte gathers used a
                 // quarter of every 64-byte sector they touched).  Needed at k == 3; the pieces are older than the weight slots that
@@ -288,7 +284,7 @@ mlp_fused_kernel(const MlpP p) {
                     MF_DMA((const char *)p.z, off, zc_a + piece * 1024);
                 }
             }
-            if (MODE >= 2 && k == 5 && tid < 128) {      // fc1's bias gradient of the chunk: the eight waves' column sums (see k == 4)
+            if (MODE == 3 && k == 5 && tid < 128) {      // fc1's bias gradient of the chunk: the eight waves' column sums (see k == 4)
                 float t = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; w++) t += csum[w * 128 + tid];
@@ -316,7 +312,7 @@ mlp_fused_kernel(const MlpP p) {
                         for (int eg = 0; eg < 4; eg++) {
                             const int u0 = wh * 64 + 32 * i + 8 * eg + 4 * kh;
                             uint2 hh;
-                            if (MODE >= 2) {      // dz = (g2 . W2) * gelu'(z)
+                            if (MODE == 3) {      // dz = (g2 . W2) * gelu'(z)
                                 const uint2 zz = *(const uint2 *)(zc + (2 * wh + i) * PANEL + tok * 64 + ((eg ^ ((tok >> 2) & 3)) << 4) + kh * 8);
                                 hh.x = f2bf2(acc1[i][4 * eg] * gelu_erf_grad(bf2f((unsigned short)zz.x)),
                                              acc1[i][4 * eg + 1] * gelu_erf_grad(bf2f((unsigned short)(zz.x >> 16))));
@@ -337,8 +333,8 @@ mlp_fused_kernel(const MlpP p) {
                         }
                 }
             } else {
-                if (k == 4 && (TRAIN || MODE >= 2)) {
-                    // (the barrier of this slot published the chunk) h / dz out, row-contiguous: 128 tokens x 256 bytes.  MODE 2: the
+                if (k == 4 && (TRAIN || MODE == 3)) {
+                    // (the barrier of this slot published the chunk) h / dz out, row-contiguous: 128 tokens x 256 bytes.  MODE 3: the
                     // column sums of what is stored (fc1's bias gradient) on the way: a thread's pieces all belong to columns
                     // 8 (tid & 15) .. + 8; its four tokens, then the wave's four lanes of a column group, then (k == 5) the waves
                     float cs8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -351,7 +347,7 @@ mlp_fused_kernel(const MlpP p) {
                             if (TRAIN)
                                 *(uint4 *)(p.z + (size_t)(bm0 + tok) * 512 + c * 128 + c16 * 8) =
                                     *(const uint4 *)(zc + (c16 >> 2) * PANEL + tok * 64 + (((c16 & 3) ^ ((tok >> 2) & 3)) << 4));
-                            if (MODE >= 2) {
+                            if (MODE == 3) {
                                 cs8[0] += __uint_as_float(v.x << 16); cs8[1] += __uint_as_float(v.x & 0xffff0000u);
                                 cs8[2] += __uint_as_float(v.y << 16); cs8[3] += __uint_as_float(v.y & 0xffff0000u);
                                 cs8[4] += __uint_as_float(v.z << 16); cs8[5] += __uint_as_float(v.z & 0xffff0000u);
@@ -359,7 +355,7 @@ mlp_fused_kernel(const MlpP p) {
                             }
                         }
                     }
-                    if (MODE >= 2) {
+                    if (MODE == 3) {
 #pragma unroll
                         for (int q = 0; q < 8; q++) { cs8[q] += __shfl_xor(cs8[q], 16, 64); cs8[q] += __shfl_xor(cs8[q], 32, 64); }
                         if (lane < 16) {
@@ -382,16 +378,11 @@ mlp_fused_kernel(const MlpP p) {
             }
         }
     }
-    }
     __syncthreads();      // every fragment read is done: chunk + ring become the bounce tiles
-    if (MF_TIMING & 1) {
-        if (acc2[0][0][0] == 123.456f) p.x2[0] = acc2[0][0][0] + acc2[0][1][1] + acc2[1][0][2] + acc2[1][1][3];
-        return;
-    }
 
     if (MODE == 3) {
         // ---- the backward's products alone: dy = bf16(acc2) to HBM (p.gout), row-contiguous through LDS; norm2's backward stays a
-        //      pass of its own (ln_bwd_kernel: many small workgroups at HBM speed, where the fused epilogue below serialises its
+        //      pass of its own (ln_bwd_kernel: many small workgroups at HBM speed, where a fused epilogue serialised its
         //      0.47 GB behind the products of ONE workgroup per CU)
         unsigned short *bounce = (unsigned short *)lds;      // [64][256] bf16
 #pragma unroll
@@ -412,81 +403,7 @@ mlp_fused_kernel(const MlpP p) {
         }
         return;
     }
-    if (MODE == 2) {
-        // ---- epilogue of the backward: dy = bf16(acc2); g <- g + norm2's backward (ln_bwd_kernel's arithmetic); a wave owns whole rows.
-        //      Half i of the tile = the rows wr * 64 + 32 i + (0 .. 31) of both wave rows: 64 rows x 256 floats through LDS,
-        //      wave w then takes bounce rows 8 w .. 8 w + 7.
-        float *bounce = (float *)lds;                       // [64][256]
-        const float4 gam = ((const float4 *)cst)[lane];
-        float pg[4] = {0.f, 0.f, 0.f, 0.f}, pb[4] = {0.f, 0.f, 0.f, 0.f}, po[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            float4 xv[8], kv[8];
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                const int lrow = wave * 8 + t, row = min(bm0 + (lrow >> 5) * 64 + i * 32 + (lrow & 31), M - 1);
-                xv[t] = ((const float4 *)(p.x1 + (size_t)row * 256))[lane];
-                kv[t] = ((const float4 *)(p.g + (size_t)row * 256))[lane];
-            }
-            __syncthreads();      // (i == 1: the rows of half 0 have been read)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int e = 0; e < 16; e++)
-                    bounce[(wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh) * 256 + wc * 64 + j * 32 + r] = bf2f(f2bf(acc2[i][j][e]));
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                const int lrow = wave * 8 + t, row = bm0 + (lrow >> 5) * 64 + i * 32 + (lrow & 31);
-                const float4 v = xv[t], k = kv[t], d = ((const float4 *)(bounce + lrow * 256))[lane];
-                float s = v.x + v.y + v.z + v.w;
-// (kept open-coded: through wave_sum this unit's device code comes out different)
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                const float mean = s * (1.0f / 256.0f);
-                const float c0 = v.x - mean, c1 = v.y - mean, c2 = v.z - mean, c3 = v.w - mean;
-                float q = c0 * c0 + c1 * c1 + c2 * c2 + c3 * c3;
-// (kept open-coded: through wave_sum this unit's device code comes out different)
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-                const float rstd = 1.0f / sqrtf(q * (1.0f / 256.0f) + p.eps);
-                const float h0 = c0 * rstd, h1 = c1 * rstd, h2 = c2 * rstd, h3 = c3 * rstd;
-                const float a0 = d.x * gam.x, a1 = d.y * gam.y, a2 = d.z * gam.z, a3 = d.w * gam.w;
-                float sa = a0 + a1 + a2 + a3, sh = a0 * h0 + a1 * h1 + a2 * h2 + a3 * h3;
-// (kept open-coded: through wave_sum this unit's device code comes out different)
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sh += __shfl_xor(sh, o, 64); }
-                sa *= (1.0f / 256.0f); sh *= (1.0f / 256.0f);
-                const float4 rr = make_float4(rstd * (a0 - sa - h0 * sh) + k.x, rstd * (a1 - sa - h1 * sh) + k.y,
-                                              rstd * (a2 - sa - h2 * sh) + k.z, rstd * (a3 - sa - h3 * sh) + k.w);
-                if (row < M) {
-                    ((float4 *)(p.g + (size_t)row * 256))[lane] = rr;
-                    uint2 hb;
-                    hb.x = f2bf2(rr.x, rr.y); hb.y = f2bf2(rr.z, rr.w);
-                    ((uint2 *)(p.gout + (size_t)row * 256))[lane] = hb;
-                    pg[0] += d.x * h0; pg[1] += d.y * h1; pg[2] += d.z * h2; pg[3] += d.w * h3;
-                    pb[0] += d.x; pb[1] += d.y; pb[2] += d.z; pb[3] += d.w;
-                    po[0] += rr.x; po[1] += rr.y; po[2] += rr.z; po[3] += rr.w;
-                }
-            }
-        }
-        __syncthreads();
-        float *red = (float *)lds;      // [NW][12][64]
-#pragma unroll
-        for (int c = 0; c < 4; c++) { red[(wave * 12 + c) * 64 + lane] = pg[c]; red[(wave * 12 + 4 + c) * 64 + lane] = pb[c]; red[(wave * 12 + 8 + c) * 64 + lane] = po[c]; }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int k = 0; k < 12; k++) {
-                float t = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; w++) t += red[(w * 12 + k) * 64 + lane];
-                p.part_ln[(size_t)blockIdx.x * 768 + (k >> 2) * 256 + 4 * lane + (k & 3)] = t;      // quantity k / 4, channel 4 lane + k % 4
-            }
-        }
-        return;
-    }
-    if (MODE < 2 && blockIdx.x == 0 && tid < 32) ((uint4 *)(p.xn3 + (size_t)M * 256))[tid] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && tid < 32) ((uint4 *)(p.xn3 + (size_t)M * 256))[tid] = make_uint4(0u, 0u, 0u, 0u);
     // ---- epilogue: x2 = acc2 + b2 + x1, norm3(x2).  Per wave 32 rows x 64 columns per trip through LDS (as ring_epilogue);
     //      a lane then holds four columns (c4) of rows 16 half + 4 q + lg; a row's 256 columns sit in the four waves of its wave row.
     // the residual rows this lane adds below (16 float4: the registers the fc1 operand held until the last chunk), requested in one
@@ -563,11 +480,10 @@ mlp_fused_kernel(const MlpP p) {
 
 template <int MODE>
 static inline hipError_t launch_mlp_fused(const MlpP &p, hipStream_t s) {
-    using Cfg = MfCfg<MF_NW, MODE>;
-    static_assert(MODE < 2 || MF_NW == 8, "the backward's epilogue deals 64-row halves to eight waves");
-    static const hipError_t attr = hipFuncSetAttribute((const void *)mlp_fused_kernel<MODE, MF_NW>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+    using Cfg = MfCfg<MODE>;
+    static const hipError_t attr = hipFuncSetAttribute((const void *)mlp_fused_kernel<MODE, MF_WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
     if (attr != hipSuccess) return attr;
-    return L2D_LAUNCH_ERR(s, (mlp_fused_kernel<MODE, MF_NW>), dim3((p.M + Cfg::TM - 1) / Cfg::TM), dim3(64 * MF_NW), Cfg::LDS, p);
+    return L2D_LAUNCH_ERR(s, (mlp_fused_kernel<MODE, MF_WAVES>), dim3((p.M + Cfg::TM - 1) / Cfg::TM), dim3(64 * MF_WAVES), Cfg::LDS, p);
 }
 
 }  // namespace

@@ -97,11 +97,8 @@ def main():
         return
     # what `step_with_reference_lr` leaves behind: the size class has seen D = --grown pairs per view
     b = rz._bucket(dev, scenes[0]["centers"].shape[0], args.res, args.res)
-    if hasattr(rz, "note_pair_count"):
-        for _ in range(4):
-            rz.note_pair_count(b, args.grown)
-    else:
-        rz._hwm[b] = args.grown
+    for _ in range(4):
+        rz.note_pair_count(b, args.grown)
     out["grown_capacity"] = rz.binning_capacity(scenes[0]["centers"].shape[0], args.res, args.res, dev)
     phase("grown")
     # ... and many calls later (a history that decays gives the capacity back)

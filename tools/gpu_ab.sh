@@ -1,5 +1,6 @@
 #!/bin/bash
-# kernel A/B on one box: tools/gpu_ab.sh "<variant> <variant> ..."   (variant `cur` = lara_amd/liblara2dgs.so, else liblara2dgs_<variant>.so)
+# kernel A/B on one box: tools/gpu_ab.sh "<variant> <variant> ..."   (variant `cur` = lara_amd/liblara2dgs.so, else liblara2dgs_<variant>.so:
+# make -C lara_amd/csrc VARIANT=<variant> EXTRA="<hipcc flags>" builds it; hipcc cross-compiles without a GPU)
 set -u
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
