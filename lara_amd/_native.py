@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare, and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in a table of its own, those of ``include/meshrender/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -202,7 +202,18 @@ def _parse_signatures(text):
     return table
 
 
+# include/meshrender/lara_meshrender.h, in the same notation.  A table of its own: ``tests/test_abi_cpu.py`` pins the number of
+# functions the headers directly under ``include/`` declare, and ``SIGNATURES`` with it; ``tests/test_meshrender.py`` holds this
+# table to its header with the same comparison.
+MESHRENDER_SIGNATURES = """
+l lara_meshrender_workspace_bytes(i*5)
+i lara_meshrender_section_offsets(i*5 p)
+i lara_meshrender_views(i*5 p*6 f p i p*7 s)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
+_SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 
@@ -221,7 +232,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lara_amd/csrc`. "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    for name, (restype, argtypes, _) in _SIGS.items():
+    for name, (restype, argtypes, _) in _ALL_SIGS.items():
         fn = getattr(lib, name)         # (a row without a symbol behind it fails here, not at the first call)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.lara2dgs_abi_version() != ABI_VERSION:
@@ -247,7 +258,7 @@ def call(name: str, device, *args):
     None as NULL; ints (raw addresses among them), floats, struct instances and host arrays go as they are; the device's
     current stream is appended where the prototype ends in ``void *stream``.  Nothing is copied, cast or made contiguous."""
     lib = load_library()
-    _, argtypes, has_stream = _SIGS[name]
+    _, argtypes, has_stream = _ALL_SIGS[name]
     with torch.cuda.device(device) if device is not None else contextlib.nullcontext():
         a = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
         if has_stream:
@@ -262,8 +273,8 @@ def call(name: str, device, *args):
 def query(name: str, *args, error=None) -> int:
     """A ``*_bytes`` / ``*_floats`` / ``*_blocks`` / ``*_rows`` query (host code).  A negative answer raises like a failed
     call, or raises ``error`` where the caller has a better message for sizes the library refuses."""
-    if len(args) != len(_SIGS[name][1]):
-        raise TypeError(f"lara_amd: {name} takes {len(_SIGS[name][1])} arguments, got {len(args)}")
+    if len(args) != len(_ALL_SIGS[name][1]):
+        raise TypeError(f"lara_amd: {name} takes {len(_ALL_SIGS[name][1])} arguments, got {len(args)}")
     n = int(getattr(load_library(), name)(*args))
     if n < 0:
         if error is not None:

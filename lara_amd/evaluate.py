@@ -305,6 +305,15 @@ def render_turntable(renderer, gs_params, cams, chunk=8, bg=None):
     return frames, normals
 
 
+def render_mesh_turntable(mesh, cams, chunk=8):
+    """evaluation.py:150-155 (``infer.mesh_video_frames > 0``) without Mitsuba: the extracted mesh -- a (vertices, triangles[,
+    colors]) tuple on the device, as ``MeshExtractor.extract`` returns it -- seen from ``cams`` through the z-buffer rasteriser
+    of `lara_amd.meshrender`, ``chunk`` cameras at a time.  Returns the device uint8 tensor [N, H, W, 3]; the frames register
+    pixel for pixel with ``render_turntable``'s for the same cameras."""
+    from .meshrender import render_mesh_views
+    return render_mesh_views(cams, mesh[0], mesh[1], mesh[2] if len(mesh) > 2 else None, chunk=chunk)["frames"]
+
+
 # ---------------------------------------------------------------------------------------------------------- accumulation
 
 class Evaluator:
