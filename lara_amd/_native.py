@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in a table of its own, those of ``include/meshrender/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/`` and ``include/meshmetrics/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -211,9 +211,21 @@ i lara_meshrender_section_offsets(i*5 p)
 i lara_meshrender_views(i*5 p*6 f p i p*7 s)
 """
 
+# include/meshmetrics/lara_meshmetrics.h, likewise; ``tests/test_meshmetrics.py`` holds this table to its header.
+MESHMETRICS_SIGNATURES = """
+l lara_meshmetrics_sample_workspace_bytes(i)
+i lara_meshmetrics_sample_surface(i i p p i i p*6 s)
+i lara_meshmetrics_grid_resolution(i)
+l lara_meshmetrics_nearest_workspace_bytes(i i)
+i lara_meshmetrics_nearest(i i p*6 s)
+l lara_meshmetrics_reduce_workspace_bytes(i)
+i lara_meshmetrics_reduce(i i p*4 i p*3 s)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER}
+_SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

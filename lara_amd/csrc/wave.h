@@ -41,6 +41,17 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum_xor(v); }
 __device__ __forceinline__ double wave_sum(double v) { return wave_sum_xor(v); }
 __device__ __forceinline__ int wave_sum(int v) { return wave_sum_xor(v); }
 
+// wave-wide inclusive prefix sum over the lanes (Hillis-Steele on __shfl_up); lane = the caller's lane id, 0..63
+template <class T>
+__device__ __forceinline__ T wave_inclusive_scan(T v, const int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
 // x moved across lanes by one DPP control (lanes the control or the row mask leaves out read 0): the step of the DPP reductions
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_move(float x) {

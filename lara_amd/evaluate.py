@@ -328,6 +328,7 @@ class Evaluator:
         self.lpips = dict(lpips or {})
         self.names, self.depth_accs = [], []
         self.psnrs, self.ssims, self.lpips_vggs, self.lpips_alexs = [], [], [], []
+        self.geometry = []          # [(name, scores)] of add_geometry; empty: the JSON is the reference's
 
     def add_scores(self, name, psnr=None, ssim=None, depth_acc=None, lpips_vgg=None, lpips_alex=None):
         """One scene's numbers (evaluation.py:92-95, :111, :113)."""
@@ -364,6 +365,30 @@ class Evaluator:
             self.add_scores(name, s["psnr"], s["ssim"], s["depth_acc"], lp.get("vgg"), lp.get("alex"))
         return scores
 
+    def add_geometry(self, name, scores):
+        """One scene's geometry scores: the dict `lara_amd.meshmetrics.surface_scores` returns (the extracted mesh against the
+        ground truth).  Scenes scored here need not be the scenes of ``add``; their names go under ``geometry_name``."""
+        keep = {k: scores[k] for k in self.GEOMETRY_SCALARS + self.GEOMETRY_LISTS}
+        keep["thresholds"] = [float(t) for t in scores["thresholds"]]
+        if self.geometry and keep["thresholds"] != self.geometry[0][1]["thresholds"]:
+            raise ValueError("lara_amd.evaluate: the scenes of one Evaluator share their geometry thresholds")
+        self.geometry.append((name, keep))
+
+    GEOMETRY_SCALARS = ("accuracy", "completeness", "chamfer", "chamfer_sq", "normal_consistency")
+    GEOMETRY_LISTS = ("precision", "recall", "fscore")          # one entry per threshold
+
+    def _geometry_summary(self):
+        """Per-scene lists and their means, as the image scores are written: a scalar key holds one number per scene, a
+        per-threshold key one list per scene; ``<key>_mean`` the mean over scenes (None where a scene has None)."""
+        out = {"geometry_name": [n for n, _ in self.geometry], "geometry_thresholds": list(self.geometry[0][1]["thresholds"])}
+        for k in self.GEOMETRY_SCALARS:
+            vals = [None if s[k] is None else float(s[k]) for _, s in self.geometry]
+            out[k], out[k + "_mean"] = vals, self._mean(vals)
+        for k in self.GEOMETRY_LISTS:
+            vals = [[float(x) for x in s[k]] for _, s in self.geometry]
+            out[k], out[k + "_mean"] = vals, [sum(c) / len(c) for c in zip(*vals)]
+        return out
+
     @staticmethod
     def _mean(values):
         return None if any(v is None for v in values) else sum(values) / len(values)
@@ -372,16 +397,19 @@ class Evaluator:
         """The dictionary evaluation.py:167-172 dumps ('depth_acc' ends up holding the MEAN: the reference's update overwrites
         the per-scene list under the same key), or None when no scene had image scores (:164)."""
         if not self.psnrs:
-            return None
+            return self._geometry_summary() if self.geometry else None
         if self.eval_depth and self.depth_accs:
             cols = list(zip(*self.depth_accs))
             mean_depth = [sum(c) / len(c) for c in cols]
         else:
             mean_depth = 0.0
-        return {"name": list(self.names), "psnr": list(self.psnrs), "ssim": list(self.ssims), "lpips_vgg": list(self.lpips_vggs),
-                "lpips_alex": list(self.lpips_alexs), "depth_acc": mean_depth, "psnr_mean": self._mean(self.psnrs),
-                "ssim_mean": self._mean(self.ssims), "lpips_vgg_mean": self._mean(self.lpips_vggs),
-                "lpips_alex_mean": self._mean(self.lpips_alexs)}
+        out = {"name": list(self.names), "psnr": list(self.psnrs), "ssim": list(self.ssims), "lpips_vgg": list(self.lpips_vggs),
+               "lpips_alex": list(self.lpips_alexs), "depth_acc": mean_depth, "psnr_mean": self._mean(self.psnrs),
+               "ssim_mean": self._mean(self.ssims), "lpips_vgg_mean": self._mean(self.lpips_vggs),
+               "lpips_alex_mean": self._mean(self.lpips_alexs)}
+        if self.geometry:          # (behind the reference's keys, and only when add_geometry was called)
+            out.update(self._geometry_summary())
+        return out
 
     def write(self, metric_path):
         """evaluation.py:164-176; returns the dictionary written (None, and no file, when there is nothing to write)."""
