@@ -44,8 +44,9 @@ int lara_loss_terms_backward(int32_t B, int32_t V, int32_t H, int32_t W, const f
  * The MS-SSIM term (lightning/loss.py:15, :42-45: `0.5 * (1 - MS_SSIM(data_range=1.0, size_average=True, channel=3)(img, tar))`),
  * forward and backward, on the images where they lie.  `pytorch_msssim` is a third-party dependency absent from /root/reference
  * and from this image (version not pinned by the reference): the algorithm is restated from its published form in
- * oracle/msssim_ref.py (five scales, 11-tap sigma-1.5 Gaussian 'valid' filters, K = (0.01, 0.03), 2 x 2 average pooling with odd
- * sides padded) -- PARITY UNPINNED by the reference; the kernels are held to that restatement.
+ * lara_amd/loss.py: ms_ssim and, in float64 and scale by scale, in tests/loss_restate.py (five scales, 11-tap sigma-1.5 Gaussian
+ * 'valid' filters, K = (0.01, 0.03), 2 x 2 average pooling with odd sides padded) -- PARITY UNPINNED by the reference; the kernels
+ * are held to those restatements.
  *
  * An image batch is addressed through a view: value(n, c, y, x) = p[n sN + c sC + y sY + (x / Wv) sV + (x % Wv) sX] (element
  * strides), which covers the renderer's side-by-side output [B, H, V*W, 3] (sN = H V W 3, sC = 1, sY = V W 3, sV = W 3, sX = 3,
