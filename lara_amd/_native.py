@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/`` and ``include/meshmetrics/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/`` and ``include/meshsimplify/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -222,10 +222,27 @@ l lara_meshmetrics_reduce_workspace_bytes(i)
 i lara_meshmetrics_reduce(i i p*4 i p*3 s)
 """
 
+# include/meshsimplify/lara_meshsimplify.h, likewise; ``tests/test_meshsimplify.py`` holds this table to its header.
+MESHSIMPLIFY_SIGNATURES = """
+l lara_meshsimplify_cells_workspace_bytes(l)
+i lara_meshsimplify_cells(l p f p*5 s)
+i lara_meshsimplify_clusters(l p*5 s)
+l lara_meshsimplify_triangles_workspace_bytes(l)
+i lara_meshsimplify_triangles(l*3 p*8 s)
+i lara_meshsimplify_corner_keys(l l p*5 s)
+i lara_meshsimplify_bucket_count(l l p p s)
+l lara_meshsimplify_bucket_workspace_bytes(l l)
+i lara_meshsimplify_bucket_fill(l l p*4 s)
+i lara_meshsimplify_sums(l*3 p*7 i p*3 s)
+i lara_meshsimplify_solve(l l i p*4 f p*4 s)
+i lara_meshsimplify_vertex_map(l l p*4 s)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS}
+_SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

@@ -237,16 +237,22 @@ class MeshExtractor:
 
     @torch.no_grad()
     def extract(self, save_mesh_path, dataset_name, voxel_size=2 / 256, sdf_trunc=0.08, alpha_thres=0.08, depth_trunc=10,
-                sample=None, fov=None, device='cuda', cams=None, chunk=8):
+                sample=None, fov=None, device='cuda', cams=None, chunk=8, *, simplify_voxel=None, simplify_target=None,
+                simplify_contraction="quadric"):
         """tools/meshExtractor.py:51-135: render the views, fuse them into a block-sparse TSDF volume (Open3D's
         ``ScalableTSDFVolume`` semantics, lara_amd.tsdf), marching cubes, ``clean_mesh`` (crop to the box, the 10 largest
         clusters), ``write_obj(save_mesh_path)``.  ``cams``: the views (the reference's ``MiniCam``s or
         ``lara_amd.cameras.Camera``s); None = the reference's ``uni_mesh_path(16, dataset_name, sample, fov)``, imported
         from LaRa's own ``tools`` package at call time.  Returns (vertices, triangles, vertex_colors) of the written mesh
-        (the reference returns None)."""
+        (the reference returns None).  ``simplify_voxel`` (a cell size) or ``simplify_target`` (a triangle budget), one of
+        them at most: the cleaned mesh goes through ``lara_amd.meshsimplify`` (``simplify_vertex_clustering`` / ``simplify_to``
+        with ``simplify_contraction``) before it is written, and ``last_simplify_info`` holds its ``info``; with both None
+        nothing changes."""
         from .batch import build_rays, fov_to_ixt
         from .renderer import Renderer
         from .tsdf import TSDFVolume
+        if simplify_voxel is not None and simplify_target is not None:
+            raise ValueError("lara_amd.mesh.MeshExtractor: give simplify_voxel or simplify_target, not both")
         if cams is None:
             from tools.gen_video_path import uni_mesh_path          # LaRa's module (the reference's camera path)
             cams = uni_mesh_path(16, dataset_name, sample, fov)
@@ -303,6 +309,15 @@ class MeshExtractor:
         self._mark("clean_mesh")
         self.last_info = info
         self.raw_mesh = (verts, tris, cols)
+        self.last_simplify_info = None
+        if simplify_voxel is not None or simplify_target is not None:
+            from . import meshsimplify
+            if simplify_voxel is not None:
+                v, t, c, sinfo = meshsimplify.simplify_vertex_clustering(v, t, c, simplify_voxel, simplify_contraction)
+            else:
+                v, t, c, sinfo = meshsimplify.simplify_to(v, t, c, simplify_target, simplify_contraction)
+            self.last_simplify_info = sinfo
+            self._mark("simplify")
         write_obj(save_mesh_path, v, t, c)
         self._mark("write_obj")
         return v, t, c
