@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/`` and ``include/meshsimplify/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/`` and ``include/depthsurface/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -238,11 +238,24 @@ i lara_meshsimplify_solve(l l i p*4 f p*4 s)
 i lara_meshsimplify_vertex_map(l l p*4 s)
 """
 
+# include/depthsurface/lara_depthsurface.h, likewise; ``tests/test_depthsurface.py`` holds this table to its header.
+DEPTHSURFACE_SIGNATURES = """
+l lara_depthsurface_backproject_workspace_bytes(i*3)
+i lara_depthsurface_backproject_count(i*3 p p i i f p p s)
+i lara_depthsurface_backproject_emit(i*3 p p i i f p p i p f p*4 s)
+l lara_depthsurface_thin_workspace_bytes(i i)
+i lara_depthsurface_thin(i p p f i p*5 s)
+i lara_depthsurface_observe(i p i*3 p p i f p p f i p s)
+l lara_depthsurface_reduce_workspace_bytes(i)
+i lara_depthsurface_reduce(i i p*5 i p*3 s)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
 _SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY}
+_SIGS_DEPTHSURFACE = _parse_signatures(DEPTHSURFACE_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 
