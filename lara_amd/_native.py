@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/`` and ``include/depthsurface/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/`` and ``include/meshio/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -250,12 +250,25 @@ l lara_depthsurface_reduce_workspace_bytes(i)
 i lara_depthsurface_reduce(i i p*5 i p*3 s)
 """
 
+# include/meshio/lara_meshio.h, likewise; ``tests/test_meshio.py`` holds this table to its header.
+MESHIO_SIGNATURES = """
+l lara_meshio_obj_workspace_bytes(l l)
+i lara_meshio_obj_lengths(l p p l p i p s)
+i lara_meshio_obj_emit(l p p l p i p p s)
+l lara_meshio_ply_body_bytes(l l i i)
+l lara_meshio_ply_workspace_bytes()
+i lara_meshio_ply_pack(l p*3 l p i p p s)
+i lara_meshio_format_f32_host(l p*3)
+i lara_meshio_format_u32_host(l p*3)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
 _SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
 _SIGS_DEPTHSURFACE = _parse_signatures(DEPTHSURFACE_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE}
+_SIGS_MESHIO = _parse_signatures(MESHIO_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

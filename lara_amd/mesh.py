@@ -238,7 +238,7 @@ class MeshExtractor:
     @torch.no_grad()
     def extract(self, save_mesh_path, dataset_name, voxel_size=2 / 256, sdf_trunc=0.08, alpha_thres=0.08, depth_trunc=10,
                 sample=None, fov=None, device='cuda', cams=None, chunk=8, *, simplify_voxel=None, simplify_target=None,
-                simplify_contraction="quadric"):
+                simplify_contraction="quadric", writer="host"):
         """tools/meshExtractor.py:51-135: render the views, fuse them into a block-sparse TSDF volume (Open3D's
         ``ScalableTSDFVolume`` semantics, lara_amd.tsdf), marching cubes, ``clean_mesh`` (crop to the box, the 10 largest
         clusters), ``write_obj(save_mesh_path)``.  ``cams``: the views (the reference's ``MiniCam``s or
@@ -247,12 +247,16 @@ class MeshExtractor:
         (the reference returns None).  ``simplify_voxel`` (a cell size) or ``simplify_target`` (a triangle budget), one of
         them at most: the cleaned mesh goes through ``lara_amd.meshsimplify`` (``simplify_vertex_clustering`` / ``simplify_to``
         with ``simplify_contraction``) before it is written, and ``last_simplify_info`` holds its ``info``; with both None
-        nothing changes."""
+        nothing changes.  ``writer``: "host" (the default) writes through ``write_obj``; "device" through
+        ``lara_amd.meshio.write_mesh``, which builds the file's bytes on the device and takes the format from the path's extension
+        (``.obj``: the same bytes; ``.ply``: binary PLY)."""
         from .batch import build_rays, fov_to_ixt
         from .renderer import Renderer
         from .tsdf import TSDFVolume
         if simplify_voxel is not None and simplify_target is not None:
             raise ValueError("lara_amd.mesh.MeshExtractor: give simplify_voxel or simplify_target, not both")
+        if writer not in ("host", "device"):
+            raise ValueError('lara_amd.mesh.MeshExtractor: writer is "host" or "device"')
         if cams is None:
             from tools.gen_video_path import uni_mesh_path          # LaRa's module (the reference's camera path)
             cams = uni_mesh_path(16, dataset_name, sample, fov)
@@ -318,6 +322,10 @@ class MeshExtractor:
                 v, t, c, sinfo = meshsimplify.simplify_to(v, t, c, simplify_target, simplify_contraction)
             self.last_simplify_info = sinfo
             self._mark("simplify")
-        write_obj(save_mesh_path, v, t, c)
+        if writer == "device":
+            from . import meshio
+            meshio.write_mesh(save_mesh_path, v, t, c)
+        else:
+            write_obj(save_mesh_path, v, t, c)
         self._mark("write_obj")
         return v, t, c
