@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/`` and ``include/meshio/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/`` and ``include/meshdist/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -262,13 +262,26 @@ i lara_meshio_format_f32_host(l p*3)
 i lara_meshio_format_u32_host(l p*3)
 """
 
+# include/meshdist/lara_meshdist.h, likewise; ``tests/test_meshdist.py`` holds this table to its header.
+MESHDIST_SIGNATURES = """
+i lara_meshdist_grid_resolution(i)
+l lara_meshdist_grid_bytes(i)
+i lara_meshdist_build(i i p*3 s)
+l lara_meshdist_query_workspace_bytes(i)
+i lara_meshdist_query(i p*7 s)
+i lara_meshdist_face_normals(i i p*3 s)
+i lara_meshdist_point_triangle_host(l p*4)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
 _SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
 _SIGS_DEPTHSURFACE = _parse_signatures(DEPTHSURFACE_SIGNATURES)
 _SIGS_MESHIO = _parse_signatures(MESHIO_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO}
+_SIGS_MESHDIST = _parse_signatures(MESHDIST_SIGNATURES)
+_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
+             **_SIGS_MESHDIST}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

@@ -198,7 +198,8 @@ def _reduce(dev, dist, index, M, keep, nq, nt, thr, n_thr, row):
 
 @torch.no_grad()
 def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetrics.THRESHOLDS, voxel=None, tau=None, stride=1,
-                 depth_max=None, normals="depth", jump=None, background_is_free=True, seed=0, return_samples=False):
+                 depth_max=None, normals="depth", jump=None, background_is_free=True, seed=0, return_samples=False,
+                 distance="point"):
     """The geometry scores of ``pred`` -- a mesh (vertices, triangles[, ...]), ``n`` points sampled from it, or a point set taken
     as it is -- against the surface the depth maps show: ``backproject`` (then ``thin`` when ``voxel`` is given).  Accuracy and
     precision run over the OBSERVED samples of ``pred`` only (``observe`` with ``tau``, by default the largest threshold: a sample
@@ -206,7 +207,15 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
     samples; normal consistency over the pairs where both normals are non-zero.  Returns the dict of
     ``meshmetrics.surface_scores`` (``Evaluator.add_geometry`` takes it), plus n_pred_observed, n_pred_unobserved, n_gt_raw, n_gt,
     normal_pairs, tau, voxel.  With no observed sample accuracy and precision are None and fscore is 0.
-    Host reads: N, N' when thinning, the two rows, and the sampler's own."""
+    Host reads: N, N' when thinning, the two rows, and the sampler's own.
+
+    ``distance``: "point" is the above.  "triangle", for a ``pred`` that is a mesh: completeness and recall measure every
+    ground-truth point against the predicted mesh's TRIANGLES (`lara_amd.meshdist`), exactly, and the normal of that direction is
+    the closest face's; the ground truth is a point cloud, so accuracy and precision stay sample-to-point, bit for bit.  The dict
+    gains ``"distance": "triangle"``; ``samples`` then holds faces of ``pred`` in i_gt.  A ``pred`` given as points is measured as
+    with "point"."""
+    if distance not in ("point", "triangle"):
+        raise ValueError(f"lara_amd.depthsurface: distance must be 'point' or 'triangle', got {distance!r}")
     thresholds = [float(t) for t in thresholds]
     if len(thresholds) > MAX_THRESHOLDS:
         raise ValueError(f"lara_amd.depthsurface: at most {MAX_THRESHOLDS} thresholds")
@@ -216,7 +225,11 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
         if not thresholds:
             raise ValueError("lara_amd.depthsurface: tau defaults to the largest threshold; give one of them")
         tau = max(thresholds)
-    P, Pn = meshmetrics._surface(pred, n, seed, dev)
+    if distance == "triangle":
+        from . import meshdist
+        P, Pn, pred_grid = meshdist._side(pred, n, seed, dev)
+    else:
+        (P, Pn), pred_grid = meshmetrics._surface(pred, n, seed, dev), None
     G, Gn, _ = backproject(depth, mask, ixt, c2w, stride=stride, depth_max=depth_max, normals=normals, jump=jump)
     n_gt_raw = G.shape[0]
     if voxel is not None:
@@ -226,18 +239,23 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
     seen = observe(P, depth, mask, ixt, c2w, tau, background_is_free, depth_max=depth_max)
     keep = (seen != 0).to(torch.uint8)
     d_p, i_p, f_p = meshmetrics.nearest(P, G, return_fallbacks=True)
-    d_g, i_g, f_g = meshmetrics.nearest(G, P, return_fallbacks=True)
+    if pred_grid is None:
+        (d_g, i_g, f_g), Tn, m_g = meshmetrics.nearest(G, P, return_fallbacks=True), Pn, P.shape[0]
+    else:
+        d_g, i_g, Tn, m_g, f_g = meshdist.distances_to(G, P, Pn, pred_grid)
     with_normals = Pn is not None and Gn is not None
     rows = torch.empty(2 * ROW + 2, dtype=torch.float64, device=dev)
     thr = host_array("f", thresholds)
     nq, nt = (Pn, Gn) if with_normals else (None, None)
     _reduce(dev, d_p, i_p, G.shape[0], keep, nq, nt, thr, len(thresholds), rows[:ROW])
-    _reduce(dev, d_g, i_g, P.shape[0], None, nt, nq, thr, len(thresholds), rows[ROW:2 * ROW])
+    _reduce(dev, d_g, i_g, m_g, None, nt, Tn if with_normals else None, thr, len(thresholds), rows[ROW:2 * ROW])
     rows[2 * ROW:] = torch.stack([f_p[0], f_g[0]]).double()
     host = rows.cpu().numpy()          # the one host read of the scores
     out = scores_from_rows(host[:ROW], host[ROW:2 * ROW], thresholds, with_normals, n_pred=P.shape[0])
     out.update(fallbacks=int(host[2 * ROW] + host[2 * ROW + 1]), n_gt_raw=int(n_gt_raw), tau=float(tau),
                voxel=None if voxel is None else float(voxel))
+    if distance == "triangle":
+        out["distance"] = "triangle"
     if return_samples:
         out["samples"] = (P, Pn, G, Gn, d_p, i_p, d_g, i_g, seen)
     return out

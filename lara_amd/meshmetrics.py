@@ -11,7 +11,8 @@ csrc/meshmetrics.hip); opt-in like every module here.
                         grid's build order is not;
   * ``surface_scores``  both of the above in both directions, one reduction pass per direction, one host read.
 
-Point-to-point distances between samples (not point-to-triangle); no alignment.  No CPU path: tensors must live on the GPU.
+Point-to-point distances between samples by default; ``surface_scores(..., distance="triangle")`` measures against the other
+mesh's triangles instead (`lara_amd.meshdist`).  No alignment.  No CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -105,7 +106,7 @@ def _surface(x, n, seed, dev):
 
 
 @torch.no_grad()
-def surface_scores(pred, gt, n=100000, thresholds=THRESHOLDS, seed=0, *, return_samples=False, device=None):
+def surface_scores(pred, gt, n=100000, thresholds=THRESHOLDS, seed=0, *, return_samples=False, device=None, distance="point"):
     """The geometry scores of ``pred`` against ``gt``.  Each is a mesh -- (vertices, triangles[, ...]): what `lara_amd.mesh`
     returns and what ``mesh.read_obj`` reads, taken as they are, ``n`` points sampled from each -- or a point set -- points [N,3],
     (points,) or (points, normals).  Returns a dict of Python floats:
@@ -116,7 +117,16 @@ def surface_scores(pred, gt, n=100000, thresholds=THRESHOLDS, seed=0, *, return_
       None when a side has no normals), n_pred, n_gt, fallbacks (queries of either direction the brute-force kernel resolved).
 
     One host read (the two reduction rows), plus one per sampled mesh.  ``return_samples``: also ``samples``, the device tensors
-    scored (pred_points, pred_normals, gt_points, gt_normals, d_pred, i_pred, d_gt, i_gt)."""
+    scored (pred_points, pred_normals, gt_points, gt_normals, d_pred, i_pred, d_gt, i_gt).
+
+    ``distance``: "point" measures every sample against the other side's SAMPLES (what the text above describes); "triangle"
+    measures it against the other mesh's triangles, exactly: ``lara_amd.meshdist.mesh_scores``, same arguments, same dict plus
+    ``"distance": "triangle"``."""
+    if distance == "triangle":
+        from . import meshdist
+        return meshdist.mesh_scores(pred, gt, n, thresholds, seed, return_samples=return_samples, device=device)
+    if distance != "point":
+        raise ValueError(f"lara_amd.meshmetrics: distance must be 'point' or 'triangle', got {distance!r}")
     thresholds = [float(t) for t in thresholds]
     if len(thresholds) > MAX_THRESHOLDS:
         raise ValueError(f"lara_amd.meshmetrics: at most {MAX_THRESHOLDS} thresholds")
