@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/`` and ``include/meshdist/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/`` and ``include/meshalign/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -64,7 +64,7 @@ STRUCTS = {"lara2dgs_view": View, "lara2dgs_state_layout": StateLayout, "lara2dg
            "lara_lpips_layer": LpipsLayer, "lara_lpips_net": LpipsNet, "lara_rows_item": RowsItem, "lara_vit_dims": VitDims}
 
 # One row per declared function: `<return> <name>(<parameters>)`.  Returns: i = int / int32_t, l = int64_t, z = const char *.
-# Parameters: i = int32_t / int, l = int64_t, f = float, p = any pointer (device memory, or a host array where the header says
+# Parameters: i = int32_t / int, l = int64_t, f = float, d = double, p = any pointer (device memory, or a host array where the header says
 # so), s = the trailing `void *stream`, a struct's name = a pointer to that struct (an instance is passed by reference, an
 # array of them as it is); `x*N` repeats x N times.
 SIGNATURES = """
@@ -176,7 +176,7 @@ i lara_vit_backward(VitDims p*5 s)
 """
 
 _RETURNS = {"i": ctypes.c_int, "l": _i64, "z": ctypes.c_char_p}
-_PARAMS = {"i": _i32, "l": _i64, "f": _f32, "p": _vp, "s": _vp,
+_PARAMS = {"i": _i32, "l": _i64, "f": _f32, "d": ctypes.c_double, "p": _vp, "s": _vp,
            **{cls.__name__: ctypes.POINTER(cls) for cls in STRUCTS.values()}}
 
 
@@ -273,6 +273,13 @@ i lara_meshdist_face_normals(i i p*3 s)
 i lara_meshdist_point_triangle_host(l p*4)
 """
 
+# include/meshalign/lara_meshalign.h, likewise; ``tests/test_meshalign.py`` holds this table to its header.
+MESHALIGN_SIGNATURES = """
+i lara_meshalign_transform(i p*3 d p p s)
+l lara_meshalign_accumulate_workspace_bytes(i)
+i lara_meshalign_accumulate(i*3 p*6 f p*3 s)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -280,8 +287,9 @@ _SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
 _SIGS_DEPTHSURFACE = _parse_signatures(DEPTHSURFACE_SIGNATURES)
 _SIGS_MESHIO = _parse_signatures(MESHIO_SIGNATURES)
 _SIGS_MESHDIST = _parse_signatures(MESHDIST_SIGNATURES)
+_SIGS_MESHALIGN = _parse_signatures(MESHALIGN_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST}
+             **_SIGS_MESHDIST, **_SIGS_MESHALIGN}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

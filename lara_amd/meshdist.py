@@ -11,7 +11,8 @@ csrc/meshdist.hip, csrc/tridist.h); opt-in like every module here.
   * ``mesh_scores``     ``meshmetrics.surface_scores`` with every sample measured against the OTHER MESH'S TRIANGLES instead of
                         its samples: a mesh against itself scores 0 up to the rounding of its samples.
 
-No alignment.  No CPU path: tensors must live on the GPU.
+The two surfaces are scored where they are: `lara_amd.meshalign` registers them first (ICP; ``aligned_scores``, which searches
+through the ``TriangleGrid`` of this module).  No CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 

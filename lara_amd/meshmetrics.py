@@ -12,7 +12,8 @@ csrc/meshmetrics.hip); opt-in like every module here.
   * ``surface_scores``  both of the above in both directions, one reduction pass per direction, one host read.
 
 Point-to-point distances between samples by default; ``surface_scores(..., distance="triangle")`` measures against the other
-mesh's triangles instead (`lara_amd.meshdist`).  No alignment.  No CPU path: tensors must live on the GPU.
+mesh's triangles instead (`lara_amd.meshdist`).  The two surfaces are scored where they are: `lara_amd.meshalign` registers them
+first (ICP; ``aligned_scores``).  No CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
