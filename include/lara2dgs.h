@@ -70,7 +70,16 @@ typedef struct lara2dgs_view {
     int32_t prefiltered;    /* bit 0: as the reference passes it (unused by LaRa, ignored); bit 1 (opt-in, not in the
                              * reference): cull surfels whose opacity is below 1/255 -- alpha = min(0.99, opacity * G)
                              * can then never pass the 1/255 test, so images and gradients are unchanged while such
-                             * surfels leave the binning, sort and composite (their radii read 0) */
+                             * surfels leave the binning, sort and composite (their radii read 0); bit 2 (opt-in, not in
+                             * the reference): "tight tiles" -- a surfel is binned into the tiles that `cullbox` (below)
+                             * meets instead of all tiles of its 3-sigma square: tile tx keeps it iff min x <= 16 tx + 15
+                             * and max x >= 16 tx, likewise in y; the empty box gives no tile, the unbounded box and a box
+                             * with a NaN bound the whole square.  The pairs that go are pairs the composite drops while
+                             * staging, so the same (pixel, surfel) pairs blend; `point_list` / `ranges` / D shrink, `radii`
+                             * stay the 3-sigma radii (a surfel with radii > 0 may own no pair), geom and cullbox are
+                             * unchanged.  A subset call must carry the bits of its coarse call.  Every earlier
+                             * caller passes this bit as zero and is served as before: LARA2DGS_ABI_VERSION stays (it
+                             * changes when a caller built against the older header would be served wrongly) */
     int32_t debug;
     int32_t forward_only;   /* 1: no backward will follow (inference): see "forward-only calls" above */
     int64_t capacity;       /* max (tile, surfel) pairs the state/scratch buffers were sized for */

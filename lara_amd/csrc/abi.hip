@@ -61,6 +61,7 @@ bool make_view(const lara2dgs_view *view, ViewDev &v) {
     if (v.gx > 65535 || v.gy > 65535) return false;
     v.scale_modifier = view->scale_modifier;
     v.cull_transparent = (view->prefiltered >> 1) & 1;
+    v.tight_tiles = (view->prefiltered >> 2) & 1;
     v.cap = (unsigned)view->capacity;
     v.fwd_only = view->forward_only != 0;
     v.counts_out = view->counts_out;

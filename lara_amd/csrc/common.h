@@ -28,6 +28,7 @@ struct ViewDev {
     unsigned cap;  // capacity in (tile, surfel) pairs
     unsigned dbg;  // LARA2DGS_DEBUG_FLAGS (perf experiments only; 0 in production)
     int cull_transparent;  // opt-in: surfels with opacity < 1/255 are culled in preprocess (lara2dgs_view.prefiltered bit 1)
+    int tight_tiles;       // opt-in: a surfel is binned into the tiles its cull box meets, not its whole 3-sigma square (prefiltered bit 2)
     int fwd_only;          // lara2dgs_view.forward_only: nothing is kept for a backward
     const float *bg, *viewmatrix, *projmatrix, *campos;
     uint32_t *counts_out;  // host-visible uint32[4] of view 0 (view z: + 4 z), or null: lara2dgs_view.counts_out

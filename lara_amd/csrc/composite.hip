@@ -32,6 +32,7 @@
 // preprocess_bwd gathers a surfel's rows.  The reference issues one atomic per (pixel, surfel,
 // component).
 #include "common.h"
+#include "tilebox.h"
 #include "wave.h"
 
 namespace {
@@ -62,11 +63,10 @@ __device__ __forceinline__ uint32_t stage_entry(const float4 *__restrict__ geom,
     uint32_t mask_lo = 0, mask_hi = 0, rectpack = 0;
     int gx0 = 0, gx1 = -1, gy0 = 0, gy1 = -1;
     if (valid) {
-        // block gx covers pixels X0+2gx, X0+2gx+1: overlap <=> minx <= X0+2gx+1 and maxx >= X0+2gx
-        gx0 = (int)ceilf(fminf(fmaxf((cb.x - X0 - 1.f) * 0.5f, 0.f), 8.f));
-        gx1 = (int)floorf(fminf(fmaxf((cb.y - X0) * 0.5f, -1.f), 7.f));
-        gy0 = (int)ceilf(fminf(fmaxf((cb.z - Y0 - 1.f) * 0.5f, 0.f), 8.f));
-        gy1 = (int)floorf(fminf(fmaxf((cb.w - Y0) * 0.5f, -1.f), 7.f));
+        // block gx covers pixels X0+2gx, X0+2gx+1: overlap <=> minx <= X0+2gx+1 and maxx >= X0+2gx (tilebox.h: the test the
+        // preprocess's tight binning applies to whole tiles)
+        l2d_box_cells<2>(cb.x, cb.y, X0, 8.f, gx0, gx1);
+        l2d_box_cells<2>(cb.z, cb.w, Y0, 8.f, gy0, gy1);
     }
     if (gx0 <= gx1 && gy0 <= gy1) {  // the 80-byte record is only fetched for surfels the tile can see
         const float4 *g = geom + (size_t)id * 5;

@@ -8,6 +8,9 @@
 // Replaces the reference's (absent) `preprocessCUDA` forward/backward; behaviour restated from the
 // published 2DGS rasteriser, call-site contract at lightning/renderer_2dgs.py:209-218.
 #include "common.h"
+#include "tilebox.h"
+
+static_assert(TILE == 16, "tilebox.h's l2d_tight_rect cuts to 16-pixel tiles");
 
 namespace {
 
@@ -245,8 +248,12 @@ surfel_forward(const ViewDev &v, const int idx, const float *__restrict__ means3
     g[4] = make_float4(rgb[0], rgb[1], rgb[2], __uint_as_float(clamp_bits));
     radii[idx] = max_radius;
     depth_out = p_view[2];
-    return make_ushort4((unsigned short)rx0, (unsigned short)ry0, (unsigned short)rx1,
-                        (unsigned short)ry1);
+    int qx0 = rx0, qy0 = ry0, qx1 = rx1, qy1 = ry1;
+    // opt-in (not in the reference): only the tiles the cull box meets -- the pairs the composite's staging drops anyway.  A
+    // surfel left without a tile keeps its record and radius, owns no pair and gets zero gradients.
+    if (v.tight_tiles) l2d_tight_rect(cb.x, cb.y, cb.z, cb.w, v.gx, v.gy, qx0, qy0, qx1, qy1);
+    return make_ushort4((unsigned short)qx0, (unsigned short)qy0, (unsigned short)qx1,
+                        (unsigned short)qy1);
 }
 
 // forward kernel: one thread per surfel + binning pass 1 (per-tile population count).  Consecutive

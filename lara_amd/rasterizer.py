@@ -47,6 +47,20 @@ def load_library():
 _cull_transparent = os.environ.get("LARA2DGS_CULL_TRANSPARENT", "0") == "1"
 
 
+_TIGHT_TILES_BIT = 4     # lara2dgs_view.prefiltered bit 2 (include/lara2dgs.h)
+
+
+def _flag_bits(rs, tight_tiles: bool) -> int:
+    """`lara2dgs_view.prefiltered` of a call: the reference's flag, the process-wide `cull_transparent` opt-in, and the call's
+    `tight_tiles` keyword -- opt-in, not in the reference: a surfel is binned into the tiles its cull box (the conservative pixel
+    box of alpha >= 1/255 the preprocess computes for the composite) meets, not into its whole 3-sigma square.  The pairs that go
+    are pairs the composite drops while staging: the same (pixel, surfel) pairs blend, the maps move by an ulp on a handful of
+    pixels (list positions shift) and the gradients by summation order; `point_list`, `ranges` and D shrink (0.70 of D at LaRa's
+    init statistics), `radii` stay the 3-sigma radii.  Off for the drop-in operator, whose lists are the reference's;
+    `lara_amd.renderer.Renderer` turns it on."""
+    return int(bool(rs.prefiltered)) | (2 if _cull_transparent else 0) | (_TIGHT_TILES_BIT if tight_tiles else 0)
+
+
 def set_cull_transparent(on: bool) -> bool:
     """Opt-in, not in the reference (default off, or LARA2DGS_CULL_TRANSPARENT=1): surfels whose opacity is below
     1/255 are culled in the preprocess.  alpha = min(0.99, opacity * G) <= opacity and the composite skips every
@@ -90,7 +104,7 @@ def _sizing_P(P: int) -> int:
 #     outputs.  No consumer ever reads a poisoned image (rounds 1-4 raised on overflow; round 5 repaired lazily and leaked NaN
 #     to whatever ran in between: VERDICT r5 missing #4).  What this costs: the host cannot run more than one forward ahead of the
 #     device (measured: DESIGN.md section 3.1);
-#   * size class ("bucket") = (device, quantised surfel count, H, W); `_hist` keeps the pair counts of the class's last
+#   * size class ("bucket") = (device, quantised surfel count, H, W[, "tight_tiles"]); `_hist` keeps the pair counts of the class's last
 #     `_HISTORY` calls -- a WINDOW, not a high-water mark: one transient spike (a training run whose surfels grow, then an
 #     evaluation in the same process) does not pin 16 Mi-pair buffers for the life of the process (round 5 did);
 #   * capacity of the next call = max(LARA2DGS_DUP_FACTOR * surfels, 2 * the window's maximum), rounded up to the grid
@@ -103,8 +117,10 @@ _hist = {}     # bucket -> deque of the largest D (over the views) of each of it
 _reruns = 0    # forwards repeated at a larger capacity since the process started (tests, bench)
 
 
-def _bucket(device: torch.device, P: int, H: int, W: int):
-    return (device.index, _sizing_P(P), int(H), int(W))
+def _bucket(device: torch.device, P: int, H: int, W: int, tight_tiles: bool = False):
+    """(Tight-tiles calls of a size produce ~0.7 of the pairs of its loose calls: a class -- a capacity history -- of their own.)"""
+    b = (device.index, _sizing_P(P), int(H), int(W))
+    return b + ("tight_tiles",) if tight_tiles else b
 
 
 def _cap_grid(n: int) -> int:
@@ -281,7 +297,7 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-def _make_view(rs: GaussianRasterizationSettings, P: int, M: int, cap: int, device):
+def _make_view(rs: GaussianRasterizationSettings, P: int, M: int, cap: int, device, tight_tiles=False):
     bg = _prep(rs.bg, "bg", device)
     vm = _prep(rs.viewmatrix, "viewmatrix", device)
     pm = _prep(rs.projmatrix, "projmatrix", device)
@@ -292,7 +308,7 @@ def _make_view(rs: GaussianRasterizationSettings, P: int, M: int, cap: int, devi
         raise RuntimeError("lara_amd: bg[3], viewmatrix[4,4], projmatrix[4,4], campos[3] expected")
     v = _View(P, int(rs.sh_degree), M, int(rs.image_height), int(rs.image_width),
               float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
-              int(bool(rs.prefiltered)) | (2 if _cull_transparent else 0), int(bool(rs.debug)), 0, cap,
+              _flag_bits(rs, tight_tiles), int(bool(rs.debug)), 0, cap,
               bg.data_ptr(), vm.data_ptr(), pm.data_ptr(), cp.data_ptr(), None)
     return v, (bg, vm, pm, cp)
 
@@ -335,26 +351,24 @@ def _needs_state(*tensors) -> bool:
 # ---------------------------------------------------------------------------------------------
 # the operator: the n views of a scene in one call; one view is the case n = 1
 # ---------------------------------------------------------------------------------------------
-def _views_array(settings, P, M, cap, device, prefiltered_bits=None):
+def _views_array(settings, P, M, cap, device, tight_tiles=False):
     arr = (_View * len(settings))()
     keep = []
     for i, rs in enumerate(settings):
-        v, k = _make_view(rs, P, M, cap, device)
-        if prefiltered_bits is not None:
-            v.prefiltered = prefiltered_bits
+        v, k = _make_view(rs, P, M, cap, device, tight_tiles)
         arr[i] = v
         keep.extend(k)
     return arr, keep
 
 
 def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, forward_only=False,
-                        subset=None, batched=True):
+                        subset=None, batched=True, tight_tiles=False):
     """Validate, allocate, enqueue the forward of the n views of a scene in one library call; returns once its pair count is
     known and it fits (see the workspace policy).  `state` holds the n per-view states at stride `sb`.  `forward_only`: nothing
     is kept for a backward and the returned `state` is the short one.  `subset` = (state, state stride, capacity, surfel count
     of an earlier call with the same cameras, ascending row indices of this call's surfels in that call's): the lists are
     filtered out of the earlier call's instead of scattered and sorted again (`lara2dgs_forward_views_subset`).
-    `batched=False` (one view): the outputs come without the leading view dimension."""
+    `batched=False` (one view): the outputs come without the leading view dimension.  `tight_tiles`: see `_flag_bits`."""
     lib = load_library()
     rs0 = settings[0]
     n = len(settings)
@@ -368,7 +382,7 @@ def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotation
     H, W = int(rs0.image_height), int(rs0.image_width)
     fo = int(bool(forward_only))
     with torch.cuda.device(device):
-        views, keep = _views_array(settings, P, M, 0, device)
+        views, keep = _views_array(settings, P, M, 0, device, tight_tiles)
         lead = (n,) if batched else ()
         color = torch.empty(lead + (3, H, W), dtype=torch.float32, device=device)
         allmap = torch.empty(lead + (7, H, W), dtype=torch.float32, device=device)
@@ -402,9 +416,9 @@ def _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotation
                        "lara2dgs_forward_views_subset")
             return state, (lambda: state.view(n, sb)[:, :64].contiguous().view(torch.int32)), (sb, qb)
 
-        state, cap, (sb, qb), D = _run_forward(_bucket(device, P, H, W), n, enqueue, any(rs.debug for rs in settings))
+        state, cap, (sb, qb), D = _run_forward(_bucket(device, P, H, W, tight_tiles), n, enqueue, any(rs.debug for rs in settings))
     return dict(color=color, radii=radii, allmap=allmap, state=state, cap=cap, strides=(sb, qb), D=D, M=M, keep=keep,
-                inputs=(means3D_c, sh_c, col_c, sc_c, rot_c, tm_c))
+                prefiltered_bits=int(views[0].prefiltered), inputs=(means3D_c, sh_c, col_c, sc_c, rot_c, tm_c))
 
 
 class _RasterizeViews(torch.autograd.Function):
@@ -415,17 +429,16 @@ class _RasterizeViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=None,
-                batched=True):
+                batched=True, tight_tiles=False):
         settings = tuple(settings)
-        rs0 = settings[0]
         r = _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, subset=subset,
-                                batched=batched)
+                                batched=batched, tight_tiles=tight_tiles)
         color, radii, allmap, M, keep = r["color"], r["radii"], r["allmap"], r["M"], r["keep"]
         means3D_c, sh_c, col_c, sc_c, rot_c, tm_c = r["inputs"]
         ctx.state, ctx.cap, ctx.strides, ctx.D = r["state"], r["cap"], r["strides"], r["D"]
         ctx.settings = settings
         ctx.M = M
-        ctx.prefiltered_bits = int(bool(rs0.prefiltered)) | (2 if _cull_transparent else 0)
+        ctx.prefiltered_bits = r["prefiltered_bits"]      # (cull_transparent, tight_tiles: the backward's views carry the forward's)
         ctx.flags = (sh_c is not None, col_c is not None, sc_c is not None, tm_c is not None)
         ctx.shapes = (sh.shape if sh_c is not None else None, opacities.shape)
         empty = means3D_c.new_empty(0)
@@ -483,11 +496,11 @@ class _RasterizeViews(torch.autograd.Function):
         return (sec(G.means3D, 3, (P, 3)), sec(G.means2D, 3, (P, 3)) if ctx.needs_input_grad[1] else None, g_sh,
                 sec(G.colors, 3, (P, 3)) if has_col else None, g_opac,
                 sec(G.scales, 2, (P, 2)) if has_sr else None, sec(G.rotations, 4, (P, 4)) if has_sr else None,
-                sec(G.transmat, 9, (P, 9)) if has_tm else None, None, None, None)
+                sec(G.transmat, 9, (P, 9)) if has_tm else None, None, None, None, None)
 
 
 def rasterize_gaussians_views(settings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None, subset_of=None):
+                              rotations=None, cov3D_precomp=None, subset_of=None, tight_tiles=False):
     """All views of a scene in one call: ``settings`` is a sequence of GaussianRasterizationSettings (one per camera,
     same image size / sh_degree); returns ``(color [n,3,H,W], radii [n,P], allmap [n,7,H,W])``.  Same results per view
     as ``GaussianRasterizer(settings[i])(...)``; the gradients are the sums over the views.
@@ -496,7 +509,11 @@ def rasterize_gaussians_views(settings, means3D, means2D, opacities, shs=None, c
     int64) of the surfels an EARLIER grad-mode call of this function rendered from the same cameras -- ``color`` is that call's
     colour output -- with the same means, scales, rotations and opacities.  The per-tile lists are then filtered out of the earlier
     call's instead of scattered and sorted again; every output is the same bit for bit.  Ignored (the full path runs) when the
-    earlier call kept no state (``no_grad``) or this one keeps none."""
+    earlier call kept no state (``no_grad``) or this one keeps none.
+
+    ``tight_tiles`` (opt-in, default off; ``lara_amd.renderer.Renderer`` sets it): bin every surfel into the tiles its cull box
+    meets instead of its 3-sigma square (`_flag_bits`).  A ``subset_of`` call must carry the flags of the call it names: the
+    filtered lists and this call's own per-tile counts agree only under one binning rule."""
     if len(settings) == 0:
         raise RuntimeError("lara_amd: rasterize_gaussians_views needs at least one view")
     if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
@@ -508,7 +525,8 @@ def rasterize_gaussians_views(settings, means3D, means2D, opacities, shs=None, c
         _as_f32(t) for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp))
     if not _needs_state(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp):
         # inference (evaluation.py:129 / tools/meshExtractor.py:85 run under no_grad): a forward-only call, no autograd node
-        r = _forward_views_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, tuple(settings), True)
+        r = _forward_views_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, tuple(settings), True,
+                                tight_tiles=tight_tiles)
         return r["color"], r["radii"], r["allmap"]
     subset = None
     if subset_of is not None:
@@ -520,9 +538,13 @@ def rasterize_gaussians_views(settings, means3D, means2D, opacities, shs=None, c
                         (b.image_height, b.image_width, b.tanfovx, b.tanfovy, float(b.scale_modifier)) or \
                         a.viewmatrix.data_ptr() != b.viewmatrix.data_ptr() or a.projmatrix.data_ptr() != b.projmatrix.data_ptr():
                     raise RuntimeError("lara_amd: `subset_of` names a call with other cameras")
+            if node.prefiltered_bits != _flag_bits(settings[0], tight_tiles):
+                raise RuntimeError("lara_amd: `subset_of` names a call made with other flags (prefiltered / cull_transparent / "
+                                   f"tight_tiles bits {node.prefiltered_bits}, this call's {_flag_bits(settings[0], tight_tiles)}): "
+                                   "its lists were binned under another rule than this call's counts")
             subset = (node.state, node.strides[0], node.cap, node.saved_tensors[0].shape[0], idx.contiguous())
     return _RasterizeViews.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                 tuple(settings), subset)
+                                 tuple(settings), subset, True, bool(tight_tiles))
 
 
 def _as_f32(t):
@@ -530,7 +552,7 @@ def _as_f32(t):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                        cov3Ds_precomp, raster_settings):
+                        cov3Ds_precomp, raster_settings, tight_tiles=False):
     # fp32 is the rasteriser's arithmetic (as the reference's); bf16 / fp16 / fp64 inputs are cast here, through
     # autograd (SURVEY.md section 8b asks for custom_fwd(cast_inputs=float32): torch's custom_fwd cannot rebuild the
     # settings NamedTuple it would recurse into, and the node holds no autocast-sensitive torch op -- only raw-pointer
@@ -540,10 +562,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     if not _needs_state(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
         # inference (evaluation.py:129 / tools/meshExtractor.py:85 run under no_grad): a forward-only call, no autograd node
         r = _forward_views_impl(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, (raster_settings,), True,
-                                batched=False)
+                                batched=False, tight_tiles=tight_tiles)
         return r["color"], r["radii"], r["allmap"]
     return _RasterizeViews.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                 (raster_settings,), None, False)
+                                 (raster_settings,), None, False, bool(tight_tiles))
 
 
 class GaussianRasterizer(nn.Module):
@@ -620,12 +642,12 @@ def state_views(state: torch.Tensor, P: int, H: int, W: int, cap: int, forward_o
 
 
 def forward_with_state(raster_settings, means3D, opacities, shs=None, colors_precomp=None,
-                       scales=None, rotations=None, cov3D_precomp=None, forward_only=False) -> dict:
+                       scales=None, rotations=None, cov3D_precomp=None, forward_only=False, tight_tiles=False) -> dict:
     """One forward returning its ``state`` too: ``dict(color, radii, allmap, state, cap, D, views, ...)`` -- the training-mode
     forward's full state, or (``forward_only``) the short one of an inference call."""
     with torch.no_grad():
         r = _forward_views_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, (raster_settings,),
-                                forward_only, batched=False)
+                                forward_only, batched=False, tight_tiles=tight_tiles)
     P = means3D.shape[0]
     r["views"] = state_views(r["state"], P, int(raster_settings.image_height),      # (the layout is the real P's; the buffer is sized for _sizing_P)
                              int(raster_settings.image_width), r["cap"], forward_only)

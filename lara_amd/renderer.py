@@ -18,12 +18,13 @@ working.  No CPU path: tensors must live on the GPU.
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 from torch import nn
 
 from ._native import call, require_device
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_views
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, rasterize_gaussians_views
 
 
 class _SurfaceMaps(torch.autograd.Function):
@@ -174,10 +175,17 @@ def surface_maps(color, allmap, rays, rot, depth_ratio=0.0):
 
 
 class Renderer(nn.Module):
-    """Same constructor and ``render_img`` as the reference ``Renderer`` (renderer_2dgs.py:91-268)."""
+    """Same constructor and ``render_img`` as the reference ``Renderer`` (renderer_2dgs.py:91-268).
 
-    def __init__(self, sh_degree=3, white_background=True, radius=1):
+    ``tight_tiles`` (not in the reference): ``render_img`` and ``render_views`` bin every surfel into the tiles its cull box meets
+    instead of its whole 3-sigma square (`rasterizer._flag_bits`: the same pixels blend the same surfels, the per-tile lists
+    lose the ~30 % of their entries that could never reach alpha 1/255 in their tile).  ``None`` reads
+    ``LARA2DGS_TIGHT_TILES`` (default "1": on; "0" gives the reference's lists, for an A/B in one process tree).  The drop-in
+    object of ``set_rasterizer`` stays on the reference's lists either way."""
+
+    def __init__(self, sh_degree=3, white_background=True, radius=1, tight_tiles=None):
         super().__init__()
+        self.tight_tiles = (os.environ.get("LARA2DGS_TIGHT_TILES", "1") == "1") if tight_tiles is None else bool(tight_tiles)
         self.sh_degree, self.white_background, self.radius = sh_degree, white_background, radius
         self.scaling_activation, self.opacity_activation = torch.exp, torch.sigmoid
         self.rotation_activation = torch.nn.functional.normalize
@@ -256,13 +264,14 @@ class Renderer(nn.Module):
 
     def render_img(self, cam, rays, centers, shs, opacity, scales, rotations, device, cov3D_precomp=None, prex='',
                    depth_ratio=0.0):
-        rasterizer = self.set_rasterizer(cam, device=device)
+        settings = self._settings(cam, device=device)
         opacity, scales, rotations = self._activated(opacity, scales, rotations)
         # the reference builds a fresh zero tensor that requires grad per view (renderer_2dgs.py:194-205) to read
         # screen-space gradients it no longer returns (:264-266 are commented out): one shared constant does here
         screenspace_points = self._zero_means2D(centers)
-        rendered_image, radii, allmap = rasterizer(means3D=centers, means2D=screenspace_points, shs=shs, opacities=opacity,
-                                                   scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        # (the operator behind `set_rasterizer`'s object, called with this renderer's binning rule)
+        rendered_image, radii, allmap = rasterize_gaussians(centers, screenspace_points, shs, None, opacity, scales, rotations,
+                                                            cov3D_precomp, settings, tight_tiles=self.tight_tiles)
         if rays is None:
             return rendered_image.clamp(0, 1)
         rot = cam.world_view_transform[:3, :3].T          # renderer_2dgs.py:231
@@ -292,7 +301,7 @@ class Renderer(nn.Module):
         opacity, scales, rotations = self._activated(opacity, scales, rotations)
         color, radii, allmap = rasterize_gaussians_views(settings, centers, self._zero_means2D(centers), opacity, shs=shs,
                                                          scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
-                                                         subset_of=subset_of)
+                                                         subset_of=subset_of, tight_tiles=self.tight_tiles)
         if raster_out is not None:
             raster_out.append((color, radii, allmap))
         if concat and rays is not None:
