@@ -189,16 +189,21 @@ def _device(device, *sides):
     return dev
 
 
+def _check_search(search):
+    if search not in ("grid", "bvh"):
+        raise ValueError(f"lara_amd.meshalign: search must be 'grid' or 'bvh', got {search!r}")
+
+
 class _Target:
     """The search side of a registration: a mesh (one ``TriangleGrid``, built once: closest points and face normals) or a point
     set (``meshmetrics.nearest``; its normals where given)."""
 
-    def __init__(self, target, n, seed, dev, need_points):
+    def __init__(self, target, n, seed, dev, need_points, search="grid"):
         mesh = _mesh_parts(target)
         self.grid = None
         if mesh is not None:
             from . import meshdist
-            self.grid = meshdist.TriangleGrid(mesh[0].to(dev, torch.float32), mesh[1].to(dev))
+            self.grid = meshdist.search_structure(search)(mesh[0].to(dev, torch.float32), mesh[1].to(dev))
             self.normals = self.grid.face_normals
             self.reference = self.grid.vertices                                          # what the origin is taken from
             self.points = meshmetrics._surface(target, n, seed, dev)[0] if need_points else None      # (area-weighted: the PCA start)
@@ -254,7 +259,7 @@ def pca_candidates(mean_s, cov_s, mean_t, cov_t):
 
 @torch.no_grad()
 def icp(source, target, *, max_dist, estimation="plane", with_scale=False, init=None, max_iter=50, rel_fitness=1e-6, rel_rmse=1e-6,
-        n=100000, seed=0, device=None):
+        n=100000, seed=0, device=None, search="grid"):
     """Register ``source`` onto ``target``.  Each is a mesh -- (vertices, triangles[, ...]), ``n`` points sampled from a source
     mesh -- or a point set -- points, (points,) or (points, normals) --, told apart as ``meshmetrics.surface_scores`` does.
 
@@ -272,7 +277,11 @@ def icp(source, target, *, max_dist, estimation="plane", with_scale=False, init=
     the kept pairs), iterations (solves done), converged, history (fitness, inlier_rmse and fallbacks of the start and after
     every iteration), fallbacks (queries the brute-force kernels resolved, all searches).  One host read per iteration, one for the
     start, one for the origin (the target's centroid, subtracted inside the reduction so that meshes far from the origin keep
-    their digits), plus the samplers' own and one for "centroid" / "pca"."""
+    their digits), plus the samplers' own and one for "centroid" / "pca".
+
+    ``search``: what a mesh target is searched with: "grid" (``meshdist.TriangleGrid``) or "bvh" (``meshbvh.TriangleBVH``: the
+    same correspondences bit for bit, hence the same result, and no query falls back to brute force however far off the start)."""
+    _check_search(search)
     if estimation not in ("plane", "point"):
         raise ValueError(f"lara_amd.meshalign: estimation must be 'plane' or 'point', got {estimation!r}")
     if with_scale and estimation != "point":
@@ -284,7 +293,7 @@ def icp(source, target, *, max_dist, estimation="plane", with_scale=False, init=
         raise ValueError(f"lara_amd.meshalign: init must be None, 'centroid', 'pca' or a 4x4, got {init!r}")
     dev = _device(device, source, target)
     S = meshmetrics._surface(source, n, seed, dev)[0]
-    tgt = _Target(target, n, seed, dev, need_points=start in ("centroid", "pca"))
+    tgt = _Target(target, n, seed, dev, need_points=start in ("centroid", "pca"), search=search)
     if S.shape[0] == 0:
         raise ValueError("lara_amd.meshalign: a surface without points")
     plane = estimation == "plane"
@@ -349,6 +358,7 @@ def align_mesh(pred, gt, **icp_kw):
     (vertices' on the device, triangles, the registration dict)."""
     if _mesh_parts(pred) is None:
         raise ValueError("lara_amd.meshalign: align_mesh moves a mesh (vertices, triangles)")
+    _check_search(icp_kw.get("search", "grid"))
     dev = _device(icp_kw.pop("device", None), pred, gt)
     reg = icp(pred, gt, device=dev, **icp_kw)
     return transform_points(torch.as_tensor(pred[0]).to(dev, torch.float32), reg["transformation"]), pred[1], reg
@@ -357,8 +367,14 @@ def align_mesh(pred, gt, **icp_kw):
 @torch.no_grad()
 def aligned_scores(pred, gt, n=100000, thresholds=meshmetrics.THRESHOLDS, seed=0, distance="point", **icp_kw):
     """``meshmetrics.surface_scores`` of ``pred`` after ``align_mesh`` has moved it onto ``gt``: that dict (``distance`` as
-    there: "point" or "triangle") plus ``"alignment"``, the registration.  ``Evaluator.add_geometry`` takes it as it is."""
+    there: "point" or "triangle") plus ``"alignment"``, the registration.  ``Evaluator.add_geometry`` takes it as it is.
+    ``search="bvh"`` (among ``icp_kw``) also reaches the "triangle" scores: ``meshdist.mesh_scores(..., search="bvh")``."""
+    search = icp_kw.get("search", "grid")
     V, F, reg = align_mesh(pred, gt, n=n, seed=seed, **icp_kw)
-    out = meshmetrics.surface_scores((V, F), gt, n, thresholds, seed, distance=distance, device=V.device)
+    if search != "grid" and distance == "triangle":
+        from . import meshdist
+        out = meshdist.mesh_scores((V, F), gt, n, thresholds, seed, device=V.device, search=search)
+    else:
+        out = meshmetrics.surface_scores((V, F), gt, n, thresholds, seed, distance=distance, device=V.device)
     out["alignment"] = reg
     return out

@@ -84,20 +84,31 @@ class TriangleGrid:
         return (dist, face) + ((closest,) if return_closest else ()) + ((fallbacks,) if return_fallbacks else ())
 
 
+def search_structure(search):
+    """The class behind ``search``: "grid" -> ``TriangleGrid``, "bvh" -> ``meshbvh.TriangleBVH`` (imported here, on that route
+    only); any other value is refused."""
+    if search == "grid":
+        return TriangleGrid
+    if search == "bvh":
+        from . import meshbvh
+        return meshbvh.TriangleBVH
+    raise ValueError(f"lara_amd.meshdist: search must be 'grid' or 'bvh', got {search!r}")
+
+
 @torch.no_grad()
-def point_to_mesh(points, vertices, triangles, return_closest=False, return_fallbacks=False):
-    """``TriangleGrid(vertices, triangles).query(points, ...)``."""
-    return TriangleGrid(vertices, triangles).query(points, return_closest, return_fallbacks)
+def point_to_mesh(points, vertices, triangles, return_closest=False, return_fallbacks=False, *, search="grid"):
+    """``TriangleGrid(vertices, triangles).query(points, ...)``; ``search="bvh"``: ``meshbvh.TriangleBVH`` instead, the same bits."""
+    return search_structure(search)(vertices, triangles).query(points, return_closest, return_fallbacks)
 
 
-def _side(x, n, seed, dev):
+def _side(x, n, seed, dev, structure=TriangleGrid):
     """(points, normals or None, grid or None) of one side, told apart as ``meshmetrics._surface`` does: a mesh -- an integer
-    second entry -- is sampled AND gets a grid over its triangles; a point set is taken as it is."""
+    second entry -- is sampled AND gets a grid (``structure``) over its triangles; a point set is taken as it is."""
     points, normals = meshmetrics._surface(x, n, seed, dev)
     second = None if isinstance(x, (torch.Tensor, np.ndarray)) or len(x) < 2 or x[1] is None else torch.as_tensor(x[1])
     if second is None or second.dtype.is_floating_point:
         return points, normals, None
-    return points, normals, TriangleGrid(torch.as_tensor(x[0]).to(dev, torch.float32), second.to(dev))
+    return points, normals, structure(torch.as_tensor(x[0]).to(dev, torch.float32), second.to(dev))
 
 
 def distances_to(points, target_points, target_normals, target_grid):
@@ -111,13 +122,15 @@ def distances_to(points, target_points, target_normals, target_grid):
 
 
 @torch.no_grad()
-def mesh_scores(pred, gt, n=100000, thresholds=meshmetrics.THRESHOLDS, seed=0, *, return_samples=False, device=None):
+def mesh_scores(pred, gt, n=100000, thresholds=meshmetrics.THRESHOLDS, seed=0, *, return_samples=False, device=None, search="grid"):
     """``meshmetrics.surface_scores`` with exact distances: ``n`` points are sampled from each mesh as there, and every sample is
     measured against the other mesh's TRIANGLES; normal consistency is |n_sample . n_closest_face|.  A side given as a bare point
     set has no triangles: the other side's samples are measured against its points, as ``surface_scores`` does.  Returns its dict
     (``Evaluator.add_geometry`` takes it) plus ``"distance": "triangle"``.  One host read (the two reduction rows), plus one per
     sampled mesh.  ``return_samples``: also ``samples``, the device tensors scored (pred_points, pred_normals, gt_points,
-    gt_normals, d_pred, face_pred, d_gt, face_gt) -- an index is a face of the other side where that side is a mesh."""
+    gt_normals, d_pred, face_pred, d_gt, face_gt) -- an index is a face of the other side where that side is a mesh.
+    ``search``: "grid" (``TriangleGrid``) or "bvh" (``meshbvh.TriangleBVH``: the same distances and faces, no fallbacks)."""
+    structure = search_structure(search)
     thresholds = [float(t) for t in thresholds]
     if len(thresholds) > meshmetrics.MAX_THRESHOLDS:
         raise ValueError(f"lara_amd.meshdist: at most {meshmetrics.MAX_THRESHOLDS} thresholds")
@@ -127,8 +140,8 @@ def mesh_scores(pred, gt, n=100000, thresholds=meshmetrics.THRESHOLDS, seed=0, *
         device = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
     dev = torch.device(device)
     require_device(dev)
-    P, Pn, Pg = _side(pred, n, seed, dev)
-    G, Gn, Gg = _side(gt, n, seed, dev)
+    P, Pn, Pg = _side(pred, n, seed, dev, structure)
+    G, Gn, Gg = _side(gt, n, seed, dev, structure)
     if P.shape[0] == 0 or G.shape[0] == 0:
         raise ValueError("lara_amd.meshdist: a surface without points")
     d_p, i_p, nt_p, m_p, f_p = distances_to(P, G, Gn, Gg)
