@@ -21,12 +21,16 @@
  *           opacity [M,K] -- i.e. the reference's [B, voxels*K, c] tensors, which are the same memory.
  * backward: gradients of the five outputs (any may be NULL = zero) + x + the offset OUTPUT -> dx [M,80] fp32, and the
  *           bf16 factor matrices the parameter gradients are products of, M_pad = lara_coarse_decoder_padded_rows(M) rows each
- *           (rows >= M of the dz matrices are written as zeros):
+ *           (rows >= M of the dz matrices are written as zeros; rows >= M of xb, h1, h2 are recomputed from row M - 1 -- finite whenever
+ *           x is -- with their column of ones: in the products they only ever meet the zero rows of dz):
  *               xb, h1, h2 [M_pad,88]: 80 features, then a column of ones and 7 of zeros
- *               dz1, dz2 [M_pad,80];  dz3 [M_pad,48]  (columns >= 22 K zero)
+ *               dz1, dz2 [M_pad,80];  dz3 [M_pad,48]  (columns >= K (10 + sh_dim) zero)
  *               G1 = dz1^T xb,  G2 = dz2^T h1,  G3 = dz3^T h2   [80|80|48, 88]     (lara_gemm_tn_bf16, lara_groupattn.h)
  *               dW_l = G_l[:, :80] (G3: rows < 22 K),  db_l = G_l[:, 80] -- the column of ones makes the bias gradient (the
  *               column sums of dz) part of the same product: no separate reduction, no atomics, reproducible.
+ * Alignment: x, dx, the five outputs, their gradients, offset_out and the six factor matrices must be 16-byte aligned (the
+ * kernels move them as float4 / four bf16 at a time; every row block they address is then a multiple of 16 bytes from the
+ * base).  Any fresh allocation of the HIP runtime or of PyTorch is.
  * Only the reference's sizes are built: 80 features, hidden 80, K * (10 + sh_dim) <= 48.
  * Returns 0 or a negative LARA2DGS_E_* code; work is enqueued on `stream`, no host synchronisation.
  */
