@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/`` and ``include/meshbvh/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/`` and ``include/meshray/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -290,6 +290,16 @@ i lara_meshbvh_query(i p*5 s)
 i lara_meshbvh_box_bound_host(l p*3)
 """
 
+# include/meshray/lara_meshray.h, likewise; ``tests/test_meshray.py`` holds this table to its header.
+MESHRAY_SIGNATURES = """
+i lara_meshray_cast(i p*8 s)
+i lara_meshray_cast_other_order(i p*8 s)
+i lara_meshray_occluded(i p*6 s)
+i lara_meshray_visible(i p p i p f p p s)
+i lara_meshray_raytri_host(l p*8)
+i lara_meshray_box_entry_host(l p*6)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -299,8 +309,9 @@ _SIGS_MESHIO = _parse_signatures(MESHIO_SIGNATURES)
 _SIGS_MESHDIST = _parse_signatures(MESHDIST_SIGNATURES)
 _SIGS_MESHALIGN = _parse_signatures(MESHALIGN_SIGNATURES)
 _SIGS_MESHBVH = _parse_signatures(MESHBVH_SIGNATURES)
+_SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH}
+             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

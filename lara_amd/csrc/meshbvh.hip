@@ -15,61 +15,14 @@
 #include "unigrid.h"
 #include "tridist.h"
 #include "boxbound.h"
-#include "../../include/meshbvh/lara_meshbvh.h"
+#include "meshbvh_layout.h"      // MbLayout, MbHeader, mb_layout, mb_load, mb_load_box: shared with meshray.hip
 
 #include <cmath>
 
 namespace {
 
-constexpr int MB_LEVELS = LARA_MESHBVH_MAX_LEVELS;
 constexpr int64_t MB_MAX_TRIANGLES = 1ll << 26, MB_MAX_POINTS = 1ll << 30;
 constexpr unsigned long long MB_ID_MASK = (1ull << 26) - 1ull, MB_INVALID = 1ull << 62;
-
-// byte offsets into the caller's buffer and slot counts: functions of T alone
-struct MbLayout {
-    int64_t keys, rec, part, total, steps;      // steps: all stored slots, the walk's cap
-    int64_t box[MB_LEVELS];
-    int n[MB_LEVELS];
-    int levels;
-};
-
-struct MbHeader {
-    int count[LARA_MESHBVH_HEADER_INTS];      // LARA_MESHBVH_HDR_*
-    float lo[3], inv[3];                      // the cell rule
-    MbLayout L;
-};
-static_assert(sizeof(MbHeader) <= 256, "the header's slot");
-
-MbLayout mb_layout(const int64_t T) {
-    MbLayout w = {};
-    int64_t o = 256;
-    w.keys = o;  o = align_up(o + T * 8, 256);
-    w.rec = o;   o = align_up(o + T * 48, 256);
-    w.part = o;  o = align_up(o + MM_BOUNDS_BLOCKS * 6 * 4, 256);
-    int64_t n = (T + 7) / 8;
-    for (int k = 0; k < MB_LEVELS; k++) {
-        const int64_t padded = (n + 7) / 8 * 8;
-        w.box[k] = o;  o = align_up(o + padded * 24, 256);
-        w.n[k] = (int)n;
-        w.steps += padded;
-        w.levels = k + 1;
-        if (n == 1) break;
-        n = (n + 7) / 8;
-    }
-    w.total = o;
-    return w;
-}
-
-struct MbRec { float p[3][3]; int id; };
-__device__ __forceinline__ MbRec mb_load(const float4 *__restrict__ rec, const int i) {
-    const float4 a = rec[3 * (size_t)i], b = rec[3 * (size_t)i + 1], c = rec[3 * (size_t)i + 2];
-    MbRec r;
-    r.p[0][0] = a.x; r.p[0][1] = a.y; r.p[0][2] = a.z;
-    r.p[1][0] = a.w; r.p[1][1] = b.x; r.p[1][2] = b.y;
-    r.p[2][0] = b.z; r.p[2][1] = b.w; r.p[2][2] = c.x;
-    r.id = __float_as_int(c.y);
-    return r;
-}
 
 // the three vertices of triangle i; false: an index outside [0, Nv) or a coordinate that is not finite (p is then zero)
 __device__ __forceinline__ bool mb_fetch(const int Nv, const float *__restrict__ v, const int *__restrict__ t, const long long i,
@@ -217,11 +170,6 @@ __device__ __forceinline__ void mb_store_box(float2 *__restrict__ box, const siz
     box[3 * j] = make_float2(lo[0], lo[1]);
     box[3 * j + 1] = make_float2(lo[2], hi[0]);
     box[3 * j + 2] = make_float2(hi[1], hi[2]);
-}
-__device__ __forceinline__ void mb_load_box(const float2 *__restrict__ box, const size_t j, float lo[3], float hi[3]) {
-    const float2 a = box[3 * j], b = box[3 * j + 1], c = box[3 * j + 2];
-    lo[0] = a.x; lo[1] = a.y; lo[2] = b.x;
-    hi[0] = b.y; hi[1] = c.x; hi[2] = c.y;
 }
 
 // level 0: slot j = the box of the valid records 8 j .. 8 j + 7; `padded` slots are written

@@ -11,7 +11,8 @@ csrc/depthsurface.hip); opt-in like every module here.  LaRa's evaluation sets s
                       prediction only -- the depth maps say nothing about the underside or the inside of the visible shell.
 
 A depth is a view-space z (what ``output['depth_fine']`` holds); pixel (y, x) looks through (x + 0.5, y + 0.5).  Point-to-point
-distances; no alignment; the prediction's own geometry does not occlude.  No CPU path: tensors must live on the GPU (the cameras, a
+distances; no alignment; the prediction's own geometry occludes only where asked (``observe(occluder=...)``,
+``depth_scores(self_occlusion=True)``: `lara_amd.meshray`).  No CPU path: tensors must live on the GPU (the cameras, a
 few floats per view, are read and inverted on the host).
 """
 from __future__ import annotations
@@ -157,10 +158,15 @@ def thin(points, normals, voxel, *, max_cells=MAX_CELLS, return_dropped=False):
 
 
 @torch.no_grad()
-def observe(points, depth, mask, ixt, c2w, tau, background_is_free=True, *, depth_max=None):
+def observe(points, depth, mask, ixt, c2w, tau, background_is_free=True, *, depth_max=None, occluder=None, occluder_faces=None,
+            shrink=2.0 ** -10):
     """``seen`` [N] int64: bit v is set when view v observed the point -- it projects inside the image in front of the camera and
     lies no further than ``tau`` behind the depth there; on a pixel without valid depth (masked background) it counts as observed
-    iff ``background_is_free``.  A non-finite point has ``seen`` = 0.  No host read."""
+    iff ``background_is_free``.  A non-finite point has ``seen`` = 0.  No host read.
+
+    ``occluder``: a ``meshbvh.TriangleBVH``; a view then also has to SEE the point past that mesh -- no triangle of it (but
+    ``occluder_faces[i]``, the one point i lies on) meets the segment from the camera centre to the point before its last
+    ``shrink`` (``meshray.visibility``).  None: the bits of before."""
     D, M, mbytes, V, H, W = _maps(depth, mask)
     dev = D.device
     P = points.detach().to(dev, torch.float32).contiguous()
@@ -175,6 +181,10 @@ def observe(points, depth, mask, ixt, c2w, tau, background_is_free=True, *, dept
     seen = torch.empty(P.shape[0], dtype=torch.int64, device=dev)
     call("lara_depthsurface_observe", dev, P.shape[0], P, V, H, W, D, M, mbytes, _limit(depth_max, "depth_max"),
          torch.from_numpy(k).to(dev), torch.from_numpy(pose).to(dev), tau, 1 if background_is_free else 0, seen)
+    if occluder is not None:
+        from . import meshray
+        eyes = torch.as_tensor(c2w).detach().to(dev, torch.float32)[:, :3, 3]
+        seen &= meshray.visibility(occluder, P, eyes, occluder_faces, shrink)
     return seen
 
 
@@ -199,7 +209,7 @@ def _reduce(dev, dist, index, M, keep, nq, nt, thr, n_thr, row):
 @torch.no_grad()
 def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetrics.THRESHOLDS, voxel=None, tau=None, stride=1,
                  depth_max=None, normals="depth", jump=None, background_is_free=True, seed=0, return_samples=False,
-                 distance="point"):
+                 distance="point", self_occlusion=False):
     """The geometry scores of ``pred`` -- a mesh (vertices, triangles[, ...]), ``n`` points sampled from it, or a point set taken
     as it is -- against the surface the depth maps show: ``backproject`` (then ``thin`` when ``voxel`` is given).  Accuracy and
     precision run over the OBSERVED samples of ``pred`` only (``observe`` with ``tau``, by default the largest threshold: a sample
@@ -213,9 +223,16 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
     ground-truth point against the predicted mesh's TRIANGLES (`lara_amd.meshdist`), exactly, and the normal of that direction is
     the closest face's; the ground truth is a point cloud, so accuracy and precision stay sample-to-point, bit for bit.  The dict
     gains ``"distance": "triangle"``; ``samples`` then holds faces of ``pred`` in i_gt.  A ``pred`` given as points is measured as
-    with "point"."""
+    with "point".
+
+    ``self_occlusion``, for a ``pred`` that is a mesh (a point set raises ValueError): a sample also has to be visible past the
+    prediction's OWN triangles from a view that observed it (`lara_amd.meshbvh`, `lara_amd.meshray`; the sample's own face is
+    ignored): an inner layer less than ``tau`` behind the seen shell no longer counts.  The samples are the same points.  The dict
+    gains ``n_pred_self_occluded``: observed by the depth rule, hidden by the mesh."""
     if distance not in ("point", "triangle"):
         raise ValueError(f"lara_amd.depthsurface: distance must be 'point' or 'triangle', got {distance!r}")
+    if self_occlusion and not _is_mesh(pred):
+        raise ValueError("lara_amd.depthsurface: self_occlusion needs a prediction that is a mesh (vertices, triangles)")
     thresholds = [float(t) for t in thresholds]
     if len(thresholds) > MAX_THRESHOLDS:
         raise ValueError(f"lara_amd.depthsurface: at most {MAX_THRESHOLDS} thresholds")
@@ -225,6 +242,7 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
         if not thresholds:
             raise ValueError("lara_amd.depthsurface: tau defaults to the largest threshold; give one of them")
         tau = max(thresholds)
+    occluder = _own_mesh(pred, dev) if self_occlusion else None
     if distance == "triangle":
         from . import meshdist
         P, Pn, pred_grid = meshdist._side(pred, n, seed, dev)
@@ -237,6 +255,13 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
     if P.shape[0] == 0 or G.shape[0] == 0:
         raise ValueError("lara_amd.depthsurface: a surface without points")
     seen = observe(P, depth, mask, ixt, c2w, tau, background_is_free, depth_max=depth_max)
+    hidden = None
+    if occluder is not None:
+        from . import meshray
+        bvh, faces = occluder
+        by_depth = seen != 0
+        seen = seen & meshray.visibility(bvh, P, torch.as_tensor(c2w).detach().to(dev, torch.float32)[:, :3, 3], faces(n, seed))
+        hidden = (by_depth & (seen == 0)).sum()
     keep = (seen != 0).to(torch.uint8)
     d_p, i_p, f_p = meshmetrics.nearest(P, G, return_fallbacks=True)
     if pred_grid is None:
@@ -244,21 +269,39 @@ def depth_scores(pred, depth, mask, ixt, c2w, *, n=100000, thresholds=meshmetric
     else:
         d_g, i_g, Tn, m_g, f_g = meshdist.distances_to(G, P, Pn, pred_grid)
     with_normals = Pn is not None and Gn is not None
-    rows = torch.empty(2 * ROW + 2, dtype=torch.float64, device=dev)
+    extra = [] if hidden is None else [hidden.to(f_p.dtype)]
+    rows = torch.empty(2 * ROW + 2 + len(extra), dtype=torch.float64, device=dev)
     thr = host_array("f", thresholds)
     nq, nt = (Pn, Gn) if with_normals else (None, None)
     _reduce(dev, d_p, i_p, G.shape[0], keep, nq, nt, thr, len(thresholds), rows[:ROW])
     _reduce(dev, d_g, i_g, m_g, None, nt, Tn if with_normals else None, thr, len(thresholds), rows[ROW:2 * ROW])
-    rows[2 * ROW:] = torch.stack([f_p[0], f_g[0]]).double()
+    rows[2 * ROW:] = torch.stack([f_p[0], f_g[0]] + extra).double()
     host = rows.cpu().numpy()          # the one host read of the scores
     out = scores_from_rows(host[:ROW], host[ROW:2 * ROW], thresholds, with_normals, n_pred=P.shape[0])
     out.update(fallbacks=int(host[2 * ROW] + host[2 * ROW + 1]), n_gt_raw=int(n_gt_raw), tau=float(tau),
                voxel=None if voxel is None else float(voxel))
     if distance == "triangle":
         out["distance"] = "triangle"
+    if hidden is not None:
+        out["n_pred_self_occluded"] = int(host[2 * ROW + 2])
     if return_samples:
         out["samples"] = (P, Pn, G, Gn, d_p, i_p, d_g, i_g, seen)
     return out
+
+
+def _is_mesh(pred):
+    """Told apart as ``meshmetrics._surface`` does: a mesh has an integer second entry."""
+    if isinstance(pred, (torch.Tensor, np.ndarray)) or len(pred) < 2 or pred[1] is None:
+        return False
+    return not torch.as_tensor(pred[1]).dtype.is_floating_point
+
+
+def _own_mesh(pred, dev):
+    """(the ``TriangleBVH`` of the mesh ``pred``, a function (n, seed) -> the faces ``meshmetrics.sample_surface`` draws its
+    samples from)."""
+    from . import meshbvh
+    V, F = torch.as_tensor(pred[0]).to(dev, torch.float32), torch.as_tensor(pred[1]).to(dev)
+    return meshbvh.TriangleBVH(V, F), lambda n, seed: meshmetrics.sample_surface(V, F, n, seed)[2]
 
 
 def scores_from_rows(row_pred, row_gt, thresholds, with_normals, n_pred=None):
