@@ -392,6 +392,14 @@ def require_device(t):
         raise RuntimeError("lara_amd: tensors must live on an MI355X (HIP) device; there is no CPU path")
 
 
+def rows3(x, device, what: str, module: str) -> torch.Tensor:
+    """``x`` as the [N,3] fp32 contiguous tensor on ``device`` a kernel takes (detached); any other shape raises."""
+    x = x.detach().to(device, torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise RuntimeError(f"lara_amd.{module}: expected {what} [N,3]")
+    return x
+
+
 def host_array(kind: str, values):
     """A host array a 'p' parameter takes: ``kind`` 'i' int32, 'l' int64, 'f' float, 'd' double, 'p' device addresses (of
     tensors); ``values`` the elements, or a length for a zeroed output array."""
@@ -427,6 +435,21 @@ def alloc_bytes(n: int, device: torch.device) -> torch.Tensor:
     whole.fill_(255)
     _guards.append((whole, n))
     return whole[_GUARD:_GUARD + n]
+
+
+class StreamWorkspace:
+    """One module's workspace: a byte tensor per (device index, current stream), grown on demand.  Two calls on one stream
+    share it in stream order; a module whose call runs another module's call while it holds its own keeps an instance of its own."""
+
+    def __init__(self):
+        self._buffers = {}
+
+    def __call__(self, dev, nbytes):
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        ws = self._buffers.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._buffers[key] = alloc_bytes(nbytes, dev)
+        return ws
 
 
 def check_poison_guards() -> list:

@@ -10,11 +10,12 @@
 //                                                          lo and max cell by integer atomics on ordered images of the floats, the
 //                                                          winners by an integer atomicMin per cell word
 //   ds_observe_kernel                                      one thread per sample, the views' twenty floats in LDS, a depth gather per view
-//   ds_reduce_kernel / ds_reduce_finish                    csrc/meshmetrics.hip's reduction with a keep mask and counted normal pairs
+//   ds_reduce_kernel / ds_reduce_finish                    csrc/meshmetrics.hip's reduction with a keep mask and counted normal pairs (rowsum.h)
 // Every hand-off between workgroups is a launch boundary.  The only atomics are integer min / max / add; no result depends on their
 // order.  Built with -ffp-contract=off.
 #include "common.h"
 #include "wave.h"
+#include "rowsum.h"
 #include "../../include/depthsurface/lara_depthsurface.h"
 
 #include <cmath>
@@ -376,9 +377,7 @@ __global__ void __launch_bounds__(256)
 ds_reduce_kernel(const int N, const int M, const float *__restrict__ dist, const int *__restrict__ index, const unsigned char *__restrict__ keep,
                  const float *__restrict__ nq, const float *__restrict__ nt, const DsThr thr, double *__restrict__ part,
                  unsigned *__restrict__ cnt) {
-    __shared__ double red[DS_RQ][4];
-    __shared__ int redc[DS_RC][4];
-    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
     double s[DS_RQ] = {0.0, 0.0, 0.0};
     int c[DS_RC];
 #pragma unroll
@@ -399,56 +398,14 @@ ds_reduce_kernel(const int N, const int M, const float *__restrict__ dist, const
 #pragma unroll
         for (int k = 0; k < LARA_DEPTHSURFACE_MAX_THRESHOLDS; k++) c[2 + k] = (k < thr.n && d <= thr.v[k]) ? 1 : 0;
     }
-#pragma unroll
-    for (int k = 0; k < DS_RQ; k++) {
-        s[k] = wave_sum(s[k]);
-        if (lane == 0) red[k][wave] = s[k];
-    }
-#pragma unroll
-    for (int k = 0; k < DS_RC; k++) {
-        c[k] = wave_sum(c[k]);
-        if (lane == 0) redc[k][wave] = c[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < DS_RQ) {
-        const int k = threadIdx.x;
-        part[(size_t)blockIdx.x * DS_RQ + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    }
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + DS_RC) {
-        const int k = threadIdx.x - 64;
-        cnt[(size_t)blockIdx.x * DS_RC + k] = (unsigned)(((redc[k][0] + redc[k][1]) + redc[k][2]) + redc[k][3]);
-    }
+    rowsum_block(s, c, part, cnt);
 }
 
+// row: the sums -> [1 .. 3]; kept -> [0], pairs -> [4], threshold k -> [5 + k]
 __global__ void __launch_bounds__(256)
 ds_reduce_finish(const int blocks, const double *__restrict__ part, const unsigned *__restrict__ cnt, double *__restrict__ row) {
-    __shared__ double red[256];
-    __shared__ unsigned long long redc[256];
-    const int tid = threadIdx.x;
-    for (int q = 0; q < DS_RQ; q++) {
-        double s = 0.0;
-        for (int k = tid; k < blocks; k += 256) s += part[(size_t)k * DS_RQ + q];
-        red[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) red[tid] += red[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[1 + q] = red[0];
-        __syncthreads();
-    }
-    for (int q = 0; q < DS_RC; q++) {
-        unsigned long long s = 0;
-        for (int k = tid; k < blocks; k += 256) s += cnt[(size_t)k * DS_RC + q];
-        redc[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) redc[tid] += redc[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[q == 0 ? 0 : 3 + q] = (double)redc[0];      // kept -> [0], pairs -> [4], threshold k -> [5 + k]
-        __syncthreads();
-    }
+    rowsum_finish<DS_RQ, DS_RC>(blocks, part, cnt, [&](const int q, const double v) { row[1 + q] = v; },
+                                [&](const int q, const double v) { row[q == 0 ? 0 : 3 + q] = v; });
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------

@@ -5,10 +5,12 @@
 //   ma_transform_kernel     one thread per row: points and (optionally) normals, in double, one rounding to fp32
 //   ma_accumulate_kernel    one pair per lane; every one of the 46 sums is butterflied as soon as its term exists, so a lane never
 //                           holds the row: the live state is p, q, n, J (18 doubles), not 46 sums
-//   ma_accumulate_finish    one workgroup: the partials in a fixed order, the counts as integers
+//   ma_accumulate_finish    one workgroup: the partials in a fixed order, the counts as integers (rowsum.h, like the wave and
+//                           workgroup steps of ma_accumulate_kernel)
 // Every hand-off between workgroups is a launch boundary.  No atomics.  Built with -ffp-contract=off.
 #include "common.h"
 #include "wave.h"
+#include "rowsum.h"
 #include "../../include/meshalign/lara_meshalign.h"
 
 #include <cmath>
@@ -45,7 +47,7 @@ ma_accumulate_kernel(const int N, const int M, const int K, const float *__restr
                      unsigned *__restrict__ cnt) {
     __shared__ double red[MA_SUMS][4];
     __shared__ int redc[2][4];
-    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
     bool keep = false, has_n = false;
     double p[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0}, n[3] = {0.0, 0.0, 0.0};
     if (i < N) {
@@ -69,10 +71,7 @@ ma_accumulate_kernel(const int N, const int M, const int K, const float *__restr
         }
     }
     // a term of row entry `entry`: +0 from a lane that does not contribute, the butterfly, the wave's slot
-    const auto emit = [&](const int entry, const bool on, const double term) {
-        const double s = wave_sum(on ? term : 0.0);
-        if (lane == 0) red[entry - 1][wave] = s;
-    };
+    const auto emit = [&](const int entry, const bool on, const double term) { rowsum_wave(red[entry - 1], on ? term : 0.0); };
     const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
     emit(1, keep, (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 #pragma unroll
@@ -94,48 +93,16 @@ ma_accumulate_kernel(const int N, const int M, const int K, const float *__restr
 #pragma unroll
     for (int a = 0; a < 6; a++) emit(40 + a, has_n, J[a] * r);
     emit(46, has_n, r * r);
-    const int ck = wave_sum(keep ? 1 : 0), cn = wave_sum(has_n ? 1 : 0);
-    if (lane == 0) { redc[0][wave] = ck; redc[1][wave] = cn; }
-    __syncthreads();
-    if (threadIdx.x < MA_SUMS) {
-        const int k = threadIdx.x;
-        part[(size_t)blockIdx.x * MA_SUMS + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    }
-    if (threadIdx.x >= 64 && threadIdx.x < 66) {
-        const int k = threadIdx.x - 64;
-        cnt[(size_t)blockIdx.x * 2 + k] = (unsigned)(((redc[k][0] + redc[k][1]) + redc[k][2]) + redc[k][3]);
-    }
+    rowsum_wave(redc[0], keep ? 1 : 0);
+    rowsum_wave(redc[1], has_n ? 1 : 0);
+    rowsum_block_partial(red, redc, part, cnt);
 }
 
+// row: the sums -> [1 .. 46]; pairs kept -> [0], kept pairs with a normal -> [47]
 __global__ void __launch_bounds__(256)
 ma_accumulate_finish(const int blocks, const double *__restrict__ part, const unsigned *__restrict__ cnt, double *__restrict__ row) {
-    __shared__ double red[256];
-    __shared__ unsigned long long redc[256];
-    const int tid = threadIdx.x;
-    for (int q = 0; q < MA_SUMS; q++) {
-        double s = 0.0;
-        for (int k = tid; k < blocks; k += 256) s += part[(size_t)k * MA_SUMS + q];
-        red[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) red[tid] += red[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[1 + q] = red[0];
-        __syncthreads();
-    }
-    for (int q = 0; q < 2; q++) {
-        unsigned long long s = 0;
-        for (int k = tid; k < blocks; k += 256) s += cnt[(size_t)k * 2 + q];
-        redc[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) redc[tid] += redc[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[q == 0 ? 0 : LARA_MESHALIGN_ROW - 1] = (double)redc[0];
-        __syncthreads();
-    }
+    rowsum_finish<MA_SUMS, 2>(blocks, part, cnt, [&](const int q, const double v) { row[1 + q] = v; },
+                              [&](const int q, const double v) { row[q == 0 ? 0 : LARA_MESHALIGN_ROW - 1] = v; });
 }
 
 int64_t ma_part_bytes(const int64_t blocks) { return align_up(blocks * MA_SUMS * 8 + 8, 256); }

@@ -1,7 +1,8 @@
 // meshbvh.hip -- exact point-to-triangle distances at any distance on gfx950: a bounding-volume hierarchy over a mesh's triangles,
 // Morton-sorted records under an implicit complete 8-ary tree of boxes, and a stackless walk that prunes with the margined bound of
 // boxbound.h.  Interface, the key and box rules, the margin and the tie rule in include/meshbvh/lara_meshbvh.h; the distance is
-// tridist.h's, the function meshdist.hip runs, so the two searches return the same bits.
+// tridist.h's, and the validity rule, the record, the tie rule and the result write are trimesh.h's, the functions meshdist.hip runs,
+// so the two searches return the same bits.
 //
 //   mb_bounds_kernel                        the box of the valid triangles (partials per workgroup); the bad and the valid count
 //   mb_header_kernel                        the partials -> lo, inv of the cell rule; T, the levels and the layout
@@ -15,7 +16,7 @@
 #include "unigrid.h"
 #include "tridist.h"
 #include "boxbound.h"
-#include "meshbvh_layout.h"      // MbLayout, MbHeader, mb_layout, mb_load, mb_load_box: shared with meshray.hip
+#include "meshbvh_layout.h"      // MbLayout, MbHeader, mb_layout, mb_load_box: shared with meshray.hip
 
 #include <cmath>
 
@@ -24,80 +25,28 @@ namespace {
 constexpr int64_t MB_MAX_TRIANGLES = 1ll << 26, MB_MAX_POINTS = 1ll << 30;
 constexpr unsigned long long MB_ID_MASK = (1ull << 26) - 1ull, MB_INVALID = 1ull << 62;
 
-// the three vertices of triangle i; false: an index outside [0, Nv) or a coordinate that is not finite (p is then zero)
-__device__ __forceinline__ bool mb_fetch(const int Nv, const float *__restrict__ v, const int *__restrict__ t, const long long i,
-                                         float p[3][3]) {
-    const int id[3] = {t[3 * i], t[3 * i + 1], t[3 * i + 2]};
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; k++) ok = ok && id[k] >= 0 && id[k] < Nv;
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            p[k][j] = v[3 * (size_t)(ok ? id[k] : 0) + j];
-            ok = ok && fabsf(p[k][j]) < INFINITY;
-        }
-    if (!ok) {
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) p[k][j] = 0.0f;
-    }
-    return ok;
-}
-
 // part[block][6] = min x y z, max x y z of the valid triangles the workgroup strides over; the two counters
 __global__ void __launch_bounds__(256)
 mb_bounds_kernel(const int Nv, const int T, const float *__restrict__ v, const int *__restrict__ t, float *__restrict__ part,
                  int *__restrict__ count) {
-    __shared__ float red[6][4];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     int bad = 0, valid = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < T; i += (long long)gridDim.x * 256) {
         float p[3][3];
-        if (!mb_fetch(Nv, v, t, i, p)) { bad++; continue; }
+        if (!tri_fetch(Nv, v, t, i, p)) { bad++; continue; }
         valid++;
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                lo[j] = fminf(lo[j], p[k][j]);
-                hi[j] = fmaxf(hi[j], p[k][j]);
-            }
+        box_grow(lo, hi, p);
     }
     if (bad) atomicAdd(&count[LARA_MESHBVH_HDR_BAD], bad);
     if (valid) atomicAdd(&count[LARA_MESHBVH_HDR_VALID], valid);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        lo[j] = mm_wave_min(lo[j]);
-        hi[j] = mm_wave_max(hi[j]);
-        if (lane == 0) { red[j][wave] = lo[j]; red[3 + j][wave] = hi[j]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int j = threadIdx.x;
-        const float a = red[j][0], b = red[j][1], c = red[j][2], d = red[j][3];
-        part[blockIdx.x * 6 + j] = j < 3 ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
-    }
+    box_block_partial(lo, hi, part);
 }
 
 // one wave: the box of all partials -> lo, inv of the cell rule; T, the levels and the layout
 __global__ void __launch_bounds__(64)
 mb_header_kernel(const int blocks, const float *__restrict__ part, const int T, const MbLayout L, MbHeader *__restrict__ hdr) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = threadIdx.x; b < blocks; b += 64)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            lo[j] = fminf(lo[j], part[b * 6 + j]);
-            hi[j] = fmaxf(hi[j], part[b * 6 + 3 + j]);
-        }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        lo[j] = mm_wave_min(lo[j]);
-        hi[j] = mm_wave_max(hi[j]);
-    }
+    box_gather_partials(blocks, part, lo, hi);
     if (threadIdx.x != 0) return;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
@@ -137,7 +86,7 @@ mb_keys_kernel(const int Nv, const int T, const float *__restrict__ v, const int
     if (i >= T) return;
     float p[3][3];
     unsigned long long key = MB_INVALID | (unsigned long long)i;
-    if (mb_fetch(Nv, v, t, i, p)) {
+    if (tri_fetch(Nv, v, t, i, p)) {
         const float lo[3] = {hdr->lo[0], hdr->lo[1], hdr->lo[2]}, inv[3] = {hdr->inv[0], hdr->inv[1], hdr->inv[2]};
         float c[3];
 #pragma unroll
@@ -160,10 +109,8 @@ mb_records_kernel(const int Nv, const int T, const float *__restrict__ v, const 
     const unsigned long long key = keys[j];
     const long long i = (long long)(key & MB_ID_MASK);
     float p[3][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-    const bool ok = (key >> 56) == 0ull && i < T && mb_fetch(Nv, v, t, i, p);
-    rec[3 * (size_t)j] = make_float4(p[0][0], p[0][1], p[0][2], p[1][0]);
-    rec[3 * (size_t)j + 1] = make_float4(p[1][1], p[1][2], p[2][0], p[2][1]);
-    rec[3 * (size_t)j + 2] = make_float4(p[2][2], __int_as_float(ok ? (int)i : -1), 0.0f, 0.0f);
+    const bool ok = (key >> 56) == 0ull && i < T && tri_fetch(Nv, v, t, i, p);
+    tri_store(rec, (size_t)j, p, ok ? (int)i : -1);
 }
 
 __device__ __forceinline__ void mb_store_box(float2 *__restrict__ box, const size_t j, const float lo[3], const float hi[3]) {
@@ -181,7 +128,7 @@ mb_leaf_kernel(const int T, const int padded, const float4 *__restrict__ rec, fl
     for (int k = 0; k < 8; k++) {
         const long long r = 8ll * j + k;
         if (r >= T) break;
-        const MbRec m = mb_load(rec, (int)r);
+        const TriRec m = tri_load(rec, (int)r);
         if (m.id < 0) continue;
 #pragma unroll
         for (int c = 0; c < 3; c++)
@@ -214,18 +161,16 @@ mb_level_kernel(const int n_child, const int padded, const float2 *__restrict__ 
     mb_store_box(box, (size_t)j, lo, hi);
 }
 
-struct MbBest { double d2; int id, pos; };
-
-// the eight records of leaf `leaf`
-__device__ __forceinline__ void mb_leaf(MbBest &best, const float q[3], const float4 *__restrict__ rec, const int T, const int leaf) {
+// the eight records of leaf `leaf`; pos = the record of the candidate
+__device__ __forceinline__ void mb_leaf(Nearest<double> &best, int &pos, const float q[3], const float4 *__restrict__ rec, const int T,
+                                        const int leaf) {
     for (int k = 0; k < 8; k++) {
         const long long r = 8ll * leaf + k;
         if (r >= T) break;
-        const MbRec m = mb_load(rec, (int)r);
+        const TriRec m = tri_load(rec, (int)r);
         if (m.id < 0) continue;
         double c[3];
-        const double d2 = lara_tridist(q, m.p[0], m.p[1], m.p[2], c);
-        if (d2 < best.d2 || (d2 == best.d2 && m.id < best.id)) { best.d2 = d2; best.id = m.id; best.pos = (int)r; }
+        if (best.take(lara_tridist(q, m.p[0], m.p[1], m.p[2], c), m.id)) pos = (int)r;
     }
 }
 
@@ -239,7 +184,8 @@ mb_query_kernel(const int N, const float *__restrict__ q, const char *__restrict
     const int top = hdr->L.levels - 1;
     const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
     const float qf[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
-    MbBest best{INFINITY, MM_NONE, 0};
+    Nearest<double> best{INFINITY, NEAREST_NONE};
+    int pos = 0;      // the candidate's record: the records are in sorted order, not by id
     const bool finite = fabsf(qf[0]) < INFINITY && fabsf(qf[1]) < INFINITY && fabsf(qf[2]) < INFINITY;
     if (finite && n_valid > 0 && top >= 0 && top < MB_LEVELS) {
         // the seed: the first valid key not below the query's own code, and the leaf it lies in
@@ -251,7 +197,7 @@ mb_query_kernel(const int N, const float *__restrict__ q, const char *__restrict
             const int mid = a + ((b - a) >> 1);
             if (keys[mid] < want) a = mid + 1; else b = mid;
         }
-        mb_leaf(best, qf, rec, T, min(a, n_valid - 1) >> 3);
+        mb_leaf(best, pos, qf, rec, T, min(a, n_valid - 1) >> 3);
         // the walk
         const long long steps = hdr->L.steps;
         int level = top, idx = 0;
@@ -263,24 +209,14 @@ mb_query_kernel(const int N, const float *__restrict__ q, const char *__restrict
             const double bound = lara_boxbound(qf, blo, bhi);
             if (bound < (double)INFINITY && !(bound > best.d2)) {
                 if (level > 0) { level--; idx <<= 3; continue; }
-                mb_leaf(best, qf, rec, T, idx);
+                mb_leaf(best, pos, qf, rec, T, idx);
             }
             idx++;
             while (level < top && (idx & 7) == 0) { idx >>= 3; level++; }
             if (level == top) break;
         }
     }
-    const bool none = best.id == MM_NONE;
-    dist[i] = none ? INFINITY : (float)sqrt(best.d2);
-    face[i] = none ? -1 : best.id;
-    if (!closest) return;
-    double c[3] = {NAN, NAN, NAN};
-    if (!none) {
-        const MbRec m = mb_load(rec, best.pos);
-        lara_tridist(qf, m.p[0], m.p[1], m.p[2], c);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) closest[3 * (size_t)i + j] = (float)c[j];
+    tri_write_result(i, qf, best, rec, pos, dist, face, closest);
 }
 
 }  // namespace

@@ -1,8 +1,9 @@
 // meshbvh_layout.h -- the buffer lara_meshbvh_build writes, as the units that walk it see it (meshbvh.hip, meshray.hip): the layout
-// as a function of T, the header's slot, and the loads of a 48-byte record and a 24-byte box.  Format and sizes in
-// include/meshbvh/lara_meshbvh.h.  Include after common.h and unigrid.h.
+// as a function of T, the header's slot, and the load of a 24-byte box; the 48-byte record (TriRec, tri_load) is trimesh.h's.
+// Format and sizes in include/meshbvh/lara_meshbvh.h.  Include after common.h and unigrid.h.
 #pragma once
 
+#include "trimesh.h"
 #include "../../include/meshbvh/lara_meshbvh.h"
 
 namespace {
@@ -42,17 +43,6 @@ MbLayout mb_layout(const int64_t T) {
     }
     w.total = o;
     return w;
-}
-
-struct MbRec { float p[3][3]; int id; };
-__device__ __forceinline__ MbRec mb_load(const float4 *__restrict__ rec, const int i) {
-    const float4 a = rec[3 * (size_t)i], b = rec[3 * (size_t)i + 1], c = rec[3 * (size_t)i + 2];
-    MbRec r;
-    r.p[0][0] = a.x; r.p[0][1] = a.y; r.p[0][2] = a.z;
-    r.p[1][0] = a.w; r.p[1][1] = b.x; r.p[1][2] = b.y;
-    r.p[2][0] = b.z; r.p[2][1] = b.w; r.p[2][2] = c.x;
-    r.id = __float_as_int(c.y);
-    return r;
 }
 
 __device__ __forceinline__ void mb_load_box(const float2 *__restrict__ box, const size_t j, float lo[3], float hi[3]) {

@@ -1,13 +1,14 @@
 // meshdist.hip -- exact point-to-triangle distances on gfx950: a uniform grid over a mesh's triangles, the ring search of
 // meshmetrics.hip carried over from points to triangles, and a brute-force kernel for the queries the rings do not settle.
-// Interface, the grid rule, the cover argument and the tie rule in include/meshdist/lara_meshdist.h; the distance itself in tridist.h.
+// Interface, the grid rule, the cover argument and the tie rule in include/meshdist/lara_meshdist.h; the distance itself in tridist.h;
+// the record, the validity rule, the box reduction, the candidate and the result write in trimesh.h, shared with meshbvh.hip.
 //
 //   md_pack_kernel                          48-byte records {p0, p1, p2, id or -1}; the box of the valid triangles; the bad count
 //   mm_bounds_finish (unigrid.h)            the box -> the grid record
 //   md_count_kernel                         per triangle: the cells its box overlaps -> integer atomic histogram, or the large flag
 //   mm_scan (unigrid.h)                     the cells' ends; the large triangles' positions (an ordered compaction)
 //   md_scatter_kernel / md_finish_kernel    cursor scatter of the triangle ids; the large list; the header's counts
-//   md_query_kernel                         one thread per query: the large list, then Chebyshev rings until the bound accepts
+//   md_query_kernel                         one thread per query: the large list, then mm_rings (unigrid.h) until the bound accepts
 //   md_brute_kernel                         a workgroup per listed query: all records, tiled through LDS
 //   md_normals_kernel                       unit face normals
 // Every hand-off between workgroups is a launch boundary.  The only atomics are integer ones (histogram, cursors, list length, bad
@@ -54,76 +55,25 @@ MdLayout md_layout(const int64_t T) {
     return w;
 }
 
-struct MdRec { float p[3][3]; int id; };
-__device__ __forceinline__ MdRec md_unpack(const float4 a, const float4 b, const float4 c) {
-    MdRec r;
-    r.p[0][0] = a.x; r.p[0][1] = a.y; r.p[0][2] = a.z;
-    r.p[1][0] = a.w; r.p[1][1] = b.x; r.p[1][2] = b.y;
-    r.p[2][0] = b.z; r.p[2][1] = b.w; r.p[2][2] = c.x;
-    r.id = __float_as_int(c.y);
-    return r;
-}
-__device__ __forceinline__ MdRec md_load(const float4 *__restrict__ rec, const int i) {
-    return md_unpack(rec[3 * (size_t)i], rec[3 * (size_t)i + 1], rec[3 * (size_t)i + 2]);
-}
-
-// rec[i] and part[block][6] = min x y z, max x y z of the valid triangles the workgroup strides over.  Valid: every index inside
-// [0, Nv) and every coordinate finite; the others get id = -1, zero coordinates, and are counted
+// rec[i] and part[block][6] = min x y z, max x y z of the valid triangles the workgroup strides over.  Valid: tri_fetch's rule;
+// the others get id = -1, zero coordinates, and are counted
 __global__ void __launch_bounds__(256)
 md_pack_kernel(const int Nv, const int T, const float *__restrict__ v, const int *__restrict__ t, float4 *__restrict__ rec,
                float *__restrict__ part, int *__restrict__ bad) {
-    __shared__ float red[6][4];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < T; i += (long long)gridDim.x * 256) {
-        const int id[3] = {t[3 * i], t[3 * i + 1], t[3 * i + 2]};
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < 3; k++) ok = ok && id[k] >= 0 && id[k] < Nv;
         float p[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                p[k][j] = v[3 * (size_t)(ok ? id[k] : 0) + j];
-                ok = ok && fabsf(p[k][j]) < INFINITY;
-            }
-        if (!ok) {
-            atomicAdd(bad, 1);
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) p[k][j] = 0.0f;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    lo[j] = fminf(lo[j], p[k][j]);
-                    hi[j] = fmaxf(hi[j], p[k][j]);
-                }
-        }
-        rec[3 * i] = make_float4(p[0][0], p[0][1], p[0][2], p[1][0]);
-        rec[3 * i + 1] = make_float4(p[1][1], p[1][2], p[2][0], p[2][1]);
-        rec[3 * i + 2] = make_float4(p[2][2], __int_as_float(ok ? (int)i : -1), 0.0f, 0.0f);
+        const bool ok = tri_fetch(Nv, v, t, i, p);
+        if (!ok) atomicAdd(bad, 1);
+        else box_grow(lo, hi, p);
+        tri_store(rec, (size_t)i, p, ok ? (int)i : -1);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        lo[j] = mm_wave_min(lo[j]);
-        hi[j] = mm_wave_max(hi[j]);
-        if (lane == 0) { red[j][wave] = lo[j]; red[3 + j][wave] = hi[j]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int j = threadIdx.x;
-        const float a = red[j][0], b = red[j][1], c = red[j][2], d = red[j][3];
-        part[blockIdx.x * 6 + j] = j < 3 ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
-    }
+    box_block_partial(lo, hi, part);
 }
 
 // the cells c0 .. c1 (per axis) between the cell of the box's minimum corner and the cell of its maximum corner: the cell rule is
 // monotone, so every point of the triangle falls into one of them.  true: the box spans more than MD_SPAN cells on some axis
-__device__ __forceinline__ bool md_cells(const MmGrid &g, const MdRec &r, int c0[3], int c1[3]) {
+__device__ __forceinline__ bool md_cells(const MmGrid &g, const TriRec &r, int c0[3], int c1[3]) {
     bool large = false;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -140,7 +90,7 @@ md_count_kernel(const int T, const float4 *__restrict__ rec, const MdHeader *__r
                 unsigned *__restrict__ flag) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= T) return;
-    const MdRec r = md_load(rec, i);
+    const TriRec r = tri_load(rec, i);
     unsigned f = 0u;
     if (r.id >= 0) {
         const MmGrid g = hdr->g;
@@ -167,7 +117,7 @@ md_scatter_kernel(const int T, const float4 *__restrict__ rec, const MdHeader *_
         if (pos < (unsigned)T) large[pos] = i;
         return;
     }
-    const MdRec r = md_load(rec, i);
+    const TriRec r = tri_load(rec, i);
     if (r.id < 0) return;
     const MmGrid g = hdr->g;
     int c0[3], c1[3];
@@ -191,24 +141,7 @@ __global__ void md_finish_kernel(MdHeader *__restrict__ hdr, const MdLayout L, c
     hdr->L = L;
 }
 
-struct MdBest { double d2; int id; };
-__device__ __forceinline__ void md_take(MdBest &b, const double d2, const int id) {
-    if (d2 < b.d2 || (d2 == b.d2 && id < b.id)) { b.d2 = d2; b.id = id; }
-}
-__device__ __forceinline__ double md_d2(const float q[3], const MdRec &r, double c[3]) { return lara_tridist(q, r.p[0], r.p[1], r.p[2], c); }
-
-// dist, face and the closest point of a settled query (id = MM_NONE: no candidate at all)
-__device__ __forceinline__ void md_write(const int i, const float q[3], const MdBest &best, const float4 *__restrict__ rec,
-                                         float *__restrict__ dist, int *__restrict__ face, float *__restrict__ closest) {
-    const bool none = best.id == MM_NONE;
-    dist[i] = none ? INFINITY : (float)sqrt(best.d2);
-    face[i] = none ? -1 : best.id;
-    if (!closest) return;
-    double c[3] = {NAN, NAN, NAN};
-    if (!none) md_d2(q, md_load(rec, best.id), c);
-#pragma unroll
-    for (int j = 0; j < 3; j++) closest[3 * (size_t)i + j] = (float)c[j];
-}
+__device__ __forceinline__ double md_d2(const float q[3], const TriRec &r, double c[3]) { return lara_tridist(q, r.p[0], r.p[1], r.p[2], c); }
 
 __global__ void __launch_bounds__(256)
 md_query_kernel(const int N, const float *__restrict__ q, const char *__restrict__ grid, float *__restrict__ dist,
@@ -223,49 +156,29 @@ md_query_kernel(const int N, const float *__restrict__ q, const char *__restrict
     const int *large = (const int *)(grid + hdr->L.large), *pairs = (const int *)(grid + hdr->L.pairs);
     const unsigned long long cap = (unsigned long long)T * MD_PAIRS;
     const float qf[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
-    MdBest best{INFINITY, MM_NONE};
+    Nearest<double> best{INFINITY, NEAREST_NONE};
     if (!(fabsf(qf[0]) < INFINITY && fabsf(qf[1]) < INFINITY && fabsf(qf[2]) < INFINITY)) {      // a non-finite query: no candidate
-        md_write(i, qf, best, rec, dist, face, closest);
+        tri_write_result(i, qf, best, rec, best.id, dist, face, closest);
         return;
     }
     const auto test = [&](const int id) {
         if ((unsigned)id >= (unsigned)T) return;
         double c[3];
-        md_take(best, md_d2(qf, md_load(rec, id), c), id);
+        best.take(md_d2(qf, tri_load(rec, id), c), id);
     };
     for (int j = 0; j < n_large; j++) test(large[j]);
     const float u[3] = {qf[0] - g.lo[0], qf[1] - g.lo[1], qf[2] - g.lo[2]};
-    const int c[3] = {mm_cell_axis(u[0] * g.inv_h, g.R[0]), mm_cell_axis(u[1] * g.inv_h, g.R[1]), mm_cell_axis(u[2] * g.inv_h, g.R[2])};
-    const float margin = fmaxf(fmaxf(fabsf(u[0]), fabsf(u[1])), fmaxf(fabsf(u[2]), g.ext)) * MM_MARGIN;
+    int c[3];
+    mm_locate(g, u, c);
     // the pairs of the cells c0 .. c1 of one x row are contiguous; at most 64 T of them (the guard costs nothing)
     const auto visit = [&](const int c0, const int c1) {
         const unsigned s = c0 ? end[c0 - 1] : 0u;
         const unsigned e = (unsigned)min((unsigned long long)end[c1], cap);
         for (unsigned j = s; j < e; j++) test(pairs[j]);
     };
-    bool done = false;
-    for (int r = 0; r <= MD_RMAX && !done; r++) {
-        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.R[2] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.R[1] - 1);
-        const int xa = max(c[0] - r, 0), xb = min(c[0] + r, g.R[0] - 1);
-        for (int z = z0; z <= z1; z++)
-            for (int y = y0; y <= y1; y++) {
-                const int row = (z * g.R[1] + y) * g.R[0];
-                if (z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r) visit(row + xa, row + xb);
-                else {      // (r > 0 here) the ring's two cells of an inner row
-                    if (c[0] - r >= 0) visit(row + c[0] - r, row + c[0] - r);
-                    if (c[0] + r < g.R[0]) visit(row + c[0] + r, row + c[0] + r);
-                }
-            }
-        float gap = INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            if (c[a] - r > 0) gap = fminf(gap, u[a] - (float)(c[a] - r) * g.h);
-            if (c[a] + r + 1 < g.R[a]) gap = fminf(gap, (float)(c[a] + r + 1) * g.h - u[a]);
-        }
-        const double bound = (double)fmaxf(0.0f, gap - margin);
-        done = best.d2 < bound * bound;
-    }
-    if (done) md_write(i, qf, best, rec, dist, face, closest);
+    const auto accept = [&](const float bound) { return best.d2 < (double)bound * (double)bound; };
+    // a record's position in the grid's buffer is its id
+    if (mm_rings(g, u, c, MD_RMAX, visit, accept)) tri_write_result(i, qf, best, rec, best.id, dist, face, closest);
     else list[atomicAdd(count, 1u)] = i;
 }
 
@@ -287,7 +200,7 @@ md_brute_kernel(const float *__restrict__ q, const char *__restrict__ grid, cons
     const float4 *rec = (const float4 *)(grid + hdr->L.rec);
     const int qi = list[blockIdx.x];
     const float qf[3] = {q[3 * (size_t)qi], q[3 * (size_t)qi + 1], q[3 * (size_t)qi + 2]};
-    MdBest best{INFINITY, MM_NONE};
+    Nearest<double> best{INFINITY, NEAREST_NONE};
     const long long words = 3ll * T;
     for (int base = 0; base < T; base += MD_TILE) {
         if (base) __syncthreads();
@@ -298,7 +211,7 @@ md_brute_kernel(const float *__restrict__ q, const char *__restrict__ grid, cons
         }
         __syncthreads();
         if (base + tid < T) {
-            const MdRec r = md_unpack(tile[3 * tid], tile[3 * tid + 1], tile[3 * tid + 2]);
+            const TriRec r = tri_unpack(tile[3 * tid], tile[3 * tid + 1], tile[3 * tid + 2]);
             if (r.id >= 0) {
                 double c[3];
                 const double d2 = md_d2(qf, r, c);
@@ -307,12 +220,12 @@ md_brute_kernel(const float *__restrict__ q, const char *__restrict__ grid, cons
         }
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) md_take(best, __shfl_xor(best.d2, d, 64), __shfl_xor(best.id, d, 64));
+    for (int d = 32; d > 0; d >>= 1) best.take(__shfl_xor(best.d2, d, 64), __shfl_xor(best.id, d, 64));
     if ((tid & 63) == 0) { wd[tid >> 6] = best.d2; wi[tid >> 6] = best.id; }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; w++) md_take(best, wd[w], wi[w]);
-        md_write(qi, qf, best, rec, dist, face, closest);
+        for (int w = 1; w < 4; w++) best.take(wd[w], wi[w]);
+        tri_write_result(qi, qf, best, rec, best.id, dist, face, closest);
     }
 }
 
@@ -323,7 +236,7 @@ md_normals_kernel(const int Nv, const int T, const float *__restrict__ v, const 
     if (i >= T) return;
     const int id[3] = {t[3 * (size_t)i], t[3 * (size_t)i + 1], t[3 * (size_t)i + 2]};
     double n[3] = {0.0, 0.0, 0.0};
-    if (id[0] >= 0 && id[0] < Nv && id[1] >= 0 && id[1] < Nv && id[2] >= 0 && id[2] < Nv) {
+    if (id[0] >= 0 && id[0] < Nv && id[1] >= 0 && id[1] < Nv && id[2] >= 0 && id[2] < Nv) {      // (not tri_fetch's rule: indices only)
         double p[3][3];
 #pragma unroll
         for (int k = 0; k < 3; k++)

@@ -8,14 +8,15 @@
 //   mm_sample_kernel                        one thread per sample: binary search in the prefix, hashed barycentrics, in double
 //   mm_bounds_partial / mm_bounds_finish    the targets' box -> the grid record (the finish and the cell rule: unigrid.h)
 //   mm_hist_kernel / mm_scatter_kernel      integer atomic histogram over the cells; cursor scatter of {x, y, z, index} records
-//   mm_query_kernel                         one thread per query: Chebyshev rings until the bound accepts, else onto the list
+//   mm_query_kernel                         one thread per query: mm_rings (unigrid.h) until the bound accepts, else onto the list
 //   mm_brute_kernel                         a workgroup per listed query: all targets, tiled through LDS (coalesced loads of the
 //                                           [M][3] layout, stride-3 LDS reads)
-//   mm_reduce_kernel / mm_reduce_finish     per-workgroup partials, added in a fixed order
+//   mm_reduce_kernel / mm_reduce_finish     per-workgroup partials, added in a fixed order (rowsum.h)
 // Every hand-off between workgroups is a launch boundary.  The only atomics are integer ones (histogram, cursors, list length); no
 // result depends on their order.  Built with -ffp-contract=off.
 #include "common.h"
 #include "unigrid.h"
+#include "rowsum.h"
 #include "../../include/meshmetrics/lara_meshmetrics.h"
 
 #include <cmath>
@@ -34,7 +35,7 @@ struct MmTri { double p[3][3]; bool ok; };
 __device__ __forceinline__ MmTri mm_load_tri(const float *__restrict__ v, const int *__restrict__ t, const int i, const int Nv) {
     MmTri r;
     const int a = t[3 * (size_t)i], b = t[3 * (size_t)i + 1], c = t[3 * (size_t)i + 2];
-    r.ok = a >= 0 && a < Nv && b >= 0 && b < Nv && c >= 0 && c < Nv;
+    r.ok = a >= 0 && a < Nv && b >= 0 && b < Nv && c >= 0 && c < Nv;      // (not tri_fetch's rule: indices only)
     const int id[3] = {r.ok ? a : 0, r.ok ? b : 0, r.ok ? c : 0};
 #pragma unroll
     for (int k = 0; k < 3; k++)
@@ -138,7 +139,6 @@ mm_sample_kernel(const int Nv, const int T, const float *__restrict__ v, const i
 // part[block][6] = min x y z, max x y z of the targets the workgroup strides over (fminf / fmaxf skip a NaN)
 __global__ void __launch_bounds__(256)
 mm_bounds_partial(const int M, const float *__restrict__ t, float *__restrict__ part) {
-    __shared__ float red[6][4];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256)
 #pragma unroll
@@ -147,19 +147,7 @@ mm_bounds_partial(const int M, const float *__restrict__ t, float *__restrict__ 
             lo[j] = fminf(lo[j], x);
             hi[j] = fmaxf(hi[j], x);
         }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        lo[j] = mm_wave_min(lo[j]);
-        hi[j] = mm_wave_max(hi[j]);
-        if (lane == 0) { red[j][wave] = lo[j]; red[3 + j][wave] = hi[j]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int j = threadIdx.x;
-        const float a = red[j][0], b = red[j][1], c = red[j][2], d = red[j][3];
-        part[blockIdx.x * 6 + j] = j < 3 ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
-    }
+    box_block_partial(lo, hi, part);
 }
 
 __device__ __forceinline__ int mm_cell(const MmGrid &g, const float x, const float y, const float z) {
@@ -191,10 +179,6 @@ mm_scatter_kernel(const int M, const float *__restrict__ t, const MmGrid *__rest
     if (pos < (unsigned)M) rec[pos] = make_float4(x, y, z, __int_as_float(i));
 }
 
-struct MmBest { float d2; int idx; };
-__device__ __forceinline__ void mm_take(MmBest &b, const float d2, const int idx) {
-    if (d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) { b.d2 = d2; b.idx = idx; }
-}
 __device__ __forceinline__ float mm_d2(const float qx, const float qy, const float qz, const float tx, const float ty, const float tz) {
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
     return (dx * dx + dy * dy) + dz * dz;
@@ -209,42 +193,21 @@ mm_query_kernel(const int N, const int M, const float *__restrict__ q, const MmG
     const MmGrid g = *grid;
     const float qx = q[3 * (size_t)i], qy = q[3 * (size_t)i + 1], qz = q[3 * (size_t)i + 2];
     const float u[3] = {qx - g.lo[0], qy - g.lo[1], qz - g.lo[2]};
-    const int c[3] = {mm_cell_axis(u[0] * g.inv_h, g.R[0]), mm_cell_axis(u[1] * g.inv_h, g.R[1]), mm_cell_axis(u[2] * g.inv_h, g.R[2])};
-    const float margin = fmaxf(fmaxf(fabsf(u[0]), fabsf(u[1])), fmaxf(fabsf(u[2]), g.ext)) * MM_MARGIN;
-    MmBest best{INFINITY, MM_NONE};
+    int c[3];
+    mm_locate(g, u, c);
+    Nearest<float> best{INFINITY, NEAREST_NONE};
     // the records of the cells c0 .. c1 of one x row are contiguous; at most M of them (the guard costs nothing)
     const auto visit = [&](const int c0, const int c1) {
         const unsigned s = c0 ? end[c0 - 1] : 0u, e = min(end[c1], (unsigned)M);
         for (unsigned j = s; j < e; j++) {
             const float4 t = rec[j];
-            mm_take(best, mm_d2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
+            best.take(mm_d2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
         }
     };
-    bool done = false;
-    for (int r = 0; r <= MM_RMAX && !done; r++) {
-        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.R[2] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.R[1] - 1);
-        const int xa = max(c[0] - r, 0), xb = min(c[0] + r, g.R[0] - 1);
-        for (int z = z0; z <= z1; z++)
-            for (int y = y0; y <= y1; y++) {
-                const int row = (z * g.R[1] + y) * g.R[0];
-                if (z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r) visit(row + xa, row + xb);
-                else {      // (r > 0 here) the ring's two cells of an inner row
-                    if (c[0] - r >= 0) visit(row + c[0] - r, row + c[0] - r);
-                    if (c[0] + r < g.R[0]) visit(row + c[0] + r, row + c[0] + r);
-                }
-            }
-        float gap = INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            if (c[a] - r > 0) gap = fminf(gap, u[a] - (float)(c[a] - r) * g.h);
-            if (c[a] + r + 1 < g.R[a]) gap = fminf(gap, (float)(c[a] + r + 1) * g.h - u[a]);
-        }
-        const float bound = fmaxf(0.0f, gap - margin);
-        done = best.d2 < bound * bound;
-    }
-    if (done) {
+    const auto accept = [&](const float bound) { return best.d2 < bound * bound; };
+    if (mm_rings(g, u, c, MM_RMAX, visit, accept)) {
         dist[i] = sqrtf(best.d2);
-        index[i] = best.idx;
+        index[i] = best.id;
     } else {
         list[atomicAdd(count, 1u)] = i;
     }
@@ -265,7 +228,7 @@ mm_brute_kernel(const int M, const float *__restrict__ q, const float *__restric
     if (blockIdx.x >= n_listed) return;
     const int qi = list[blockIdx.x];
     const float qx = q[3 * (size_t)qi], qy = q[3 * (size_t)qi + 1], qz = q[3 * (size_t)qi + 2];
-    MmBest best{INFINITY, MM_NONE};
+    Nearest<float> best{INFINITY, NEAREST_NONE};
     const long long floats = 3ll * M;
     for (int base = 0; base < M; base += MM_TILE) {
         if (base) __syncthreads();
@@ -280,18 +243,18 @@ mm_brute_kernel(const int M, const float *__restrict__ q, const float *__restric
             const int j = tid + 256 * m;
             if (base + j < M) {
                 const float d2 = mm_d2(qx, qy, qz, tile[3 * j], tile[3 * j + 1], tile[3 * j + 2]);
-                if (d2 < best.d2) { best.d2 = d2; best.idx = base + j; }
+                if (d2 < best.d2) { best.d2 = d2; best.id = base + j; }
             }
         }
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) mm_take(best, __shfl_xor(best.d2, d, 64), __shfl_xor(best.idx, d, 64));
-    if ((tid & 63) == 0) { wd[tid >> 6] = best.d2; wi[tid >> 6] = best.idx; }
+    for (int d = 32; d > 0; d >>= 1) best.take(__shfl_xor(best.d2, d, 64), __shfl_xor(best.id, d, 64));
+    if ((tid & 63) == 0) { wd[tid >> 6] = best.d2; wi[tid >> 6] = best.id; }
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; w++) mm_take(best, wd[w], wi[w]);
+        for (int w = 1; w < 4; w++) best.take(wd[w], wi[w]);
         dist[qi] = sqrtf(best.d2);
-        index[qi] = best.idx == MM_NONE ? -1 : best.idx;
+        index[qi] = best.id == NEAREST_NONE ? -1 : best.id;
     }
 }
 
@@ -303,9 +266,7 @@ struct MmThr { int n; float v[LARA_MESHMETRICS_MAX_THRESHOLDS]; };
 __global__ void __launch_bounds__(256)
 mm_reduce_kernel(const int N, const int M, const float *__restrict__ dist, const int *__restrict__ index, const float *__restrict__ nq,
                  const float *__restrict__ nt, const MmThr thr, double *__restrict__ part, unsigned *__restrict__ cnt) {
-    __shared__ double red[MM_RQ][4];
-    __shared__ int redc[LARA_MESHMETRICS_MAX_THRESHOLDS][4];
-    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
     double s[MM_RQ] = {0.0, 0.0, 0.0};
     int below[LARA_MESHMETRICS_MAX_THRESHOLDS];
 #pragma unroll
@@ -324,58 +285,16 @@ mm_reduce_kernel(const int N, const int M, const float *__restrict__ dist, const
 #pragma unroll
         for (int k = 0; k < LARA_MESHMETRICS_MAX_THRESHOLDS; k++) below[k] = (k < thr.n && d <= thr.v[k]) ? 1 : 0;
     }
-#pragma unroll
-    for (int k = 0; k < MM_RQ; k++) {
-        s[k] = wave_sum(s[k]);
-        if (lane == 0) red[k][wave] = s[k];
-    }
-#pragma unroll
-    for (int k = 0; k < LARA_MESHMETRICS_MAX_THRESHOLDS; k++) {
-        below[k] = wave_sum(below[k]);
-        if (lane == 0) redc[k][wave] = below[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < MM_RQ) {
-        const int k = threadIdx.x;
-        part[(size_t)blockIdx.x * MM_RQ + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-    }
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + LARA_MESHMETRICS_MAX_THRESHOLDS) {
-        const int k = threadIdx.x - 64;
-        cnt[(size_t)blockIdx.x * LARA_MESHMETRICS_MAX_THRESHOLDS + k] = (unsigned)(((redc[k][0] + redc[k][1]) + redc[k][2]) + redc[k][3]);
-    }
+    rowsum_block(s, below, part, cnt);
 }
 
+// row = N, the three sums, the counts per threshold
 __global__ void __launch_bounds__(256)
 mm_reduce_finish(const int N, const int blocks, const double *__restrict__ part, const unsigned *__restrict__ cnt,
                  double *__restrict__ row) {
-    __shared__ double red[256];
-    __shared__ unsigned long long redc[256];
-    const int tid = threadIdx.x;
-    for (int q = 0; q < MM_RQ; q++) {
-        double s = 0.0;
-        for (int k = tid; k < blocks; k += 256) s += part[(size_t)k * MM_RQ + q];
-        red[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) red[tid] += red[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[1 + q] = red[0];
-        __syncthreads();
-    }
-    for (int q = 0; q < LARA_MESHMETRICS_MAX_THRESHOLDS; q++) {
-        unsigned long long s = 0;
-        for (int k = tid; k < blocks; k += 256) s += cnt[(size_t)k * LARA_MESHMETRICS_MAX_THRESHOLDS + q];
-        redc[tid] = s;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) {
-            if (tid < d) redc[tid] += redc[tid + d];
-            __syncthreads();
-        }
-        if (tid == 0) row[4 + q] = (double)redc[0];
-        __syncthreads();
-    }
-    if (tid == 0) row[0] = (double)N;
+    rowsum_finish<MM_RQ, LARA_MESHMETRICS_MAX_THRESHOLDS>(blocks, part, cnt, [&](const int q, const double v) { row[1 + q] = v; },
+                                                          [&](const int q, const double v) { row[4 + q] = v; });
+    if (threadIdx.x == 0) row[0] = (double)N;
 }
 
 // ---- workspace layouts ----------------------------------------------------------------------------------------------------------

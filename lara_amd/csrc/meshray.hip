@@ -1,7 +1,7 @@
 // meshray.hip -- ray queries on the triangle hierarchy of meshbvh.hip on gfx950: the first triangle a ray meets, whether it meets
-// any, and which of E eyes see a point.  A second walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h), with the
-// ray-triangle function of raytri.h per record and the margined entry parameter of raybox.h per box.  Interface, the function,
-// the bound's derivation and the tie rule in include/meshray/lara_meshray.h.
+// any, and which of E eyes see a point.  A second walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records:
+// trimesh.h), with the ray-triangle function of raytri.h per record and the margined entry parameter of raybox.h per
+// box.  Interface, the function, the bound's derivation and the tie rule in include/meshray/lara_meshray.h.
 //
 //   mr_cast_kernel<MASKED>        one thread per ray: the walk, then t, face and the barycentrics of the best record
 //   mr_occluded_kernel            one thread per ray: the same walk, ended by the first accepted triangle
@@ -29,12 +29,12 @@ __device__ __forceinline__ bool mr_leaf(MrBest &best, const LaraRay &ray, const 
     for (int k = 0; k < 8; k++) {
         const long long r = 8ll * leaf + k;
         if (r >= T) break;
-        const MbRec m = mb_load(rec, (int)r);
+        const TriRec m = tri_load(rec, (int)r);
         if (m.id < 0 || m.id == skip) continue;
         double t, b[3];
         if (!lara_raytri(ray, t_min, t_max, m.p[0], m.p[1], m.p[2], t, b)) continue;
         if (ANY) return true;
-        if (t < best.t || (t == best.t && m.id < best.id)) { best.t = t; best.id = m.id; best.pos = (int)r; }
+        if (t < best.t || (t == best.t && m.id < best.id)) { best.t = t; best.id = m.id; best.pos = (int)r; }      // (Nearest's rule, on t)
     }
     return false;
 }
@@ -91,16 +91,16 @@ mr_cast_kernel(const int R, const float *__restrict__ o, const float *__restrict
     if (i >= R) return;
     const LaraRay ray = mr_ray(o, d, (size_t)i);
     const double lo = t_min ? (double)t_min[i] : 0.0, hi = t_max ? (double)t_max[i] : (double)INFINITY;
-    MrBest best{INFINITY, MM_NONE, 0};
+    MrBest best{INFINITY, NEAREST_NONE, 0};
     mr_walk<false, MASKED>(best, ray, lo, hi, -1, bvh);
-    const bool none = best.id == MM_NONE;
+    const bool none = best.id == NEAREST_NONE;
     t[i] = none ? INFINITY : (float)best.t;
     face[i] = none ? -1 : best.id;
     if (!bary) return;
     double b[3] = {NAN, NAN, NAN};
     if (!none) {
         const MbHeader *hdr = (const MbHeader *)bvh;
-        const MbRec m = mb_load((const float4 *)(bvh + hdr->L.rec), best.pos);
+        const TriRec m = tri_load((const float4 *)(bvh + hdr->L.rec), best.pos);
         double tt;
         lara_raytri(ray, lo, hi, m.p[0], m.p[1], m.p[2], tt, b);
     }
@@ -115,7 +115,7 @@ mr_occluded_kernel(const int R, const float *__restrict__ o, const float *__rest
     if (i >= R) return;
     const LaraRay ray = mr_ray(o, d, (size_t)i);
     const double lo = t_min ? (double)t_min[i] : 0.0, hi = t_max ? (double)t_max[i] : (double)INFINITY;
-    MrBest best{INFINITY, MM_NONE, 0};
+    MrBest best{INFINITY, NEAREST_NONE, 0};
     out[i] = mr_walk<true, true>(best, ray, lo, hi, -1, bvh) ? 1 : 0;
 }
 
@@ -133,7 +133,7 @@ mr_visible_kernel(const int N, const float *__restrict__ p, const int *__restric
             const float of[3] = {eyes[3 * e], eyes[3 * e + 1], eyes[3 * e + 2]};
             const float df[3] = {pf[0] - of[0], pf[1] - of[1], pf[2] - of[2]};
             const LaraRay ray = lara_ray_setup(of, df);
-            MrBest best{INFINITY, MM_NONE, 0};
+            MrBest best{INFINITY, NEAREST_NONE, 0};
             if (!mr_walk<true, true>(best, ray, 0.0, (double)t_hi, ignore, bvh)) word |= 1ull << e;
         }
     }

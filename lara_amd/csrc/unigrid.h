@@ -1,10 +1,12 @@
 // unigrid.h -- what the two uniform-grid searches share (meshmetrics.hip: nearest point; meshdist.hip: nearest triangle): the grid
-// record and the wave that derives it from a bounding box, the cell rule, the resolution rule and the three-launch inclusive scan.
-// The rules are stated in include/meshmetrics/lara_meshmetrics.h.  Everything sits in an unnamed namespace: each unit that includes
-// this header owns its copies.  Include it from units built with -ffp-contract=off only.
+// record and the wave that derives it from a bounding box, the cell rule, the Chebyshev ring walk with its bound (mm_rings), the
+// resolution rule and the three-launch inclusive scan.  The box reduction and the candidate are trimesh.h's.  The rules are stated
+// in include/meshmetrics/lara_meshmetrics.h.  Everything sits in an unnamed namespace: each unit that includes this header owns
+// its copies.  Include it from units built with -ffp-contract=off only.
 #pragma once
 #include "common.h"
 #include "wave.h"
+#include "trimesh.h"
 
 #include <cmath>
 
@@ -13,7 +15,6 @@ namespace {
 constexpr int MM_SCAN_ITEMS = 4, MM_SCAN_BLOCK = 256 * MM_SCAN_ITEMS;      // elements per workgroup of the scan
 constexpr int MM_BOUNDS_BLOCKS = 1024;
 constexpr float MM_MARGIN = 3.814697265625e-06f;                           // 2^-18
-constexpr int MM_NONE = 0x7fffffff;
 constexpr int MM_MAX_GRID = 256;
 
 struct MmGrid {
@@ -88,32 +89,11 @@ int mm_scan(const T *in, T *out, T *bsum, const long long n, hipStream_t s) {
     return LARA2DGS_OK;
 }
 
-__device__ __forceinline__ float mm_wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float mm_wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
 // one wave: the box of all partials (part[block][6] = min x y z, max x y z) -> the grid record
 __global__ void __launch_bounds__(64)
 mm_bounds_finish(const int blocks, const float *__restrict__ part, const int R, MmGrid *__restrict__ grid) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = threadIdx.x; b < blocks; b += 64)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            lo[j] = fminf(lo[j], part[b * 6 + j]);
-            hi[j] = fmaxf(hi[j], part[b * 6 + 3 + j]);
-        }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        lo[j] = mm_wave_min(lo[j]);
-        hi[j] = mm_wave_max(hi[j]);
-    }
+    box_gather_partials(blocks, part, lo, hi);
     if (threadIdx.x != 0) return;
     MmGrid g;
     float ext[3], emax = 0.0f;
@@ -143,6 +123,46 @@ mm_bounds_finish(const int blocks, const float *__restrict__ part, const int R, 
 __device__ __forceinline__ int mm_cell_axis(const float u_scaled, const int Ra) {      // clamp(floor(u), 0, Ra - 1); a NaN -> 0
     const float f = floorf(u_scaled);
     return f >= 0.0f ? (f < (float)Ra ? (int)f : Ra - 1) : 0;
+}
+
+// of a query at u = q - g.lo: its cell, and the margin its bound gives away to the rounding of u and of the cells' faces
+__device__ __forceinline__ void mm_locate(const MmGrid &g, const float u[3], int c[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) c[a] = mm_cell_axis(u[a] * g.inv_h, g.R[a]);
+}
+__device__ __forceinline__ float mm_margin(const MmGrid &g, const float u[3]) {
+    return fmaxf(fmaxf(fabsf(u[0]), fabsf(u[1])), fmaxf(fabsf(u[2]), g.ext)) * MM_MARGIN;
+}
+
+// The Chebyshev ring search around cell c: ring r = the cells at Chebyshev distance r, as contiguous runs of one x row handed to
+// visit(c0, c1); after each ring accept(bound) says whether the caller's candidate is nearer than `bound`, the distance from the
+// query to the nearest face of the cube of rings 0 .. r that is not a face of the grid, less the margin.  true: accepted within
+// rings 0 .. rmax
+template <class Visit, class Accept>
+__device__ __forceinline__ bool mm_rings(const MmGrid &g, const float u[3], const int c[3], const int rmax, Visit visit, Accept accept) {
+    const float margin = mm_margin(g, u);
+    bool done = false;
+    for (int r = 0; r <= rmax && !done; r++) {
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.R[2] - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.R[1] - 1);
+        const int xa = max(c[0] - r, 0), xb = min(c[0] + r, g.R[0] - 1);
+        for (int z = z0; z <= z1; z++)
+            for (int y = y0; y <= y1; y++) {
+                const int row = (z * g.R[1] + y) * g.R[0];
+                if (z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r) visit(row + xa, row + xb);
+                else {      // (r > 0 here) the ring's two cells of an inner row
+                    if (c[0] - r >= 0) visit(row + c[0] - r, row + c[0] - r);
+                    if (c[0] + r < g.R[0]) visit(row + c[0] + r, row + c[0] + r);
+                }
+            }
+        float gap = INFINITY;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (c[a] - r > 0) gap = fminf(gap, u[a] - (float)(c[a] - r) * g.h);
+            if (c[a] + r + 1 < g.R[a]) gap = fminf(gap, (float)(c[a] + r + 1) * g.h - u[a]);
+        }
+        done = accept(fmaxf(0.0f, gap - margin));
+    }
+    return done;
 }
 
 int mm_resolution(const int64_t M) {

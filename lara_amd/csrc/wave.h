@@ -1,5 +1,5 @@
 // wave.h -- device primitives shared by the translation units: MFMA operand vectors, bf16 conversion, the 64-lane butterfly
-// sum and the DPP move the wave-level reductions are built from.
+// sum, minimum and maximum, and the DPP move the wave-level reductions are built from.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +40,18 @@ __device__ __forceinline__ T wave_sum_xor(T v) {
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_xor(v); }
 __device__ __forceinline__ double wave_sum(double v) { return wave_sum_xor(v); }
 __device__ __forceinline__ int wave_sum(int v) { return wave_sum_xor(v); }
+
+// wave-wide minimum / maximum by the same butterfly (fminf / fmaxf skip a NaN)
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
 
 // wave-wide inclusive prefix sum over the lanes (Hillis-Steele on __shfl_up); lane = the caller's lane id, 0..63
 template <class T>

@@ -23,20 +23,12 @@ import numpy as np
 import torch
 
 from . import meshmetrics
-from ._native import alloc_bytes, call, host_array, query, require_device
+from ._native import StreamWorkspace, call, host_array, query, require_device, rows3
 
 MAX_VIEWS, MAX_CELLS, MAX_THRESHOLDS, ROW = 64, 1 << 27, 8, 13      # include/depthsurface/lara_depthsurface.h
 NORMALS_NONE, NORMALS_GIVEN, NORMALS_DEPTH = 0, 1, 2
 
-_workspaces = {}      # (device index, stream) -> byte tensor, grown on demand
-
-
-def _workspace(dev, nbytes):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[key] = alloc_bytes(nbytes, dev)
-    return ws
+_workspace = StreamWorkspace()      # its own: ``meshmetrics.nearest`` runs while a call here holds it
 
 
 def cameras(ixt, c2w, invert=False):
@@ -130,9 +122,7 @@ def thin(points, normals, voxel, *, max_cells=MAX_CELLS, return_dropped=False):
     when the grid would have more than ``max_cells`` (at most 2^27) cells."""
     require_device(points)
     dev = points.device
-    P = points.detach().to(torch.float32).contiguous()
-    if P.dim() != 2 or P.shape[1] != 3:
-        raise RuntimeError("lara_amd.depthsurface: expected points [N,3]")
+    P = rows3(points, dev, "points", "depthsurface")
     Nn = normals.detach().to(dev, torch.float32).contiguous() if normals is not None else None
     if Nn is not None and tuple(Nn.shape) != tuple(P.shape):
         raise RuntimeError("lara_amd.depthsurface: normals must have the shape of the points")
@@ -169,9 +159,7 @@ def observe(points, depth, mask, ixt, c2w, tau, background_is_free=True, *, dept
     ``shrink`` (``meshray.visibility``).  None: the bits of before."""
     D, M, mbytes, V, H, W = _maps(depth, mask)
     dev = D.device
-    P = points.detach().to(dev, torch.float32).contiguous()
-    if P.dim() != 2 or P.shape[1] != 3:
-        raise RuntimeError("lara_amd.depthsurface: expected points [N,3]")
+    P = rows3(points, dev, "points", "depthsurface")
     k, pose = cameras(ixt, c2w, invert=True)
     if k.shape[0] != V:
         raise ValueError("lara_amd.depthsurface: one camera per depth map")

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import meshmetrics
-from ._native import call, host_array, query, require_device
+from ._native import call, host_array, query, require_device, rows3
 
 ROW = 48                                # include/meshalign/lara_meshalign.h
 _PCA_SIGNS = ((1.0, 1.0, 1.0), (1.0, -1.0, -1.0), (-1.0, 1.0, -1.0), (-1.0, -1.0, 1.0))      # the four proper axis flips, in candidate order
@@ -47,9 +47,7 @@ def transform_points(points, T, normals=None, *, out=None):
     write, which may be the inputs.  No host read."""
     require_device(points)
     dev = points.device
-    P = points.detach().to(torch.float32).contiguous()
-    if P.dim() != 2 or P.shape[1] != 3:
-        raise RuntimeError("lara_amd.meshalign: expected points [N,3]")
+    P = rows3(points, dev, "points", "meshalign")
     T, s = _similarity(T)
     Nn = None
     if normals is not None:

@@ -17,7 +17,8 @@ from __future__ import annotations
 
 import torch
 
-from ._native import alloc_bytes, call, host_array, query, require_device
+from ._native import call, host_array
+from .meshdist import _TriangleSearch
 
 MAX_LEVELS = 9                                                  # include/meshbvh/lara_meshbvh.h
 HEADER_INTS, HDR_BAD, HDR_VALID, HDR_TRIANGLES, HDR_LEVELS = 4, 0, 1, 2, 3
@@ -31,26 +32,17 @@ def layout(T):
     return {"keys": out[0], "records": out[1], "total": out[3], "levels": [(out[4 + 2 * k], out[5 + 2 * k]) for k in range(out[2])]}
 
 
-class TriangleBVH:
+class TriangleBVH(_TriangleSearch):
     """The hierarchy of one mesh (``vertices`` [Nv,3] fp32 on the device, ``triangles`` [T,3] of any integer type), built on the
     current stream without a host read.  ``counts`` is a device int32 [4] view of the header: triangles never taken as candidates
-    (an index outside [0, Nv) or a coordinate that is not finite), the valid ones, T, the number of levels."""
+    (an index outside [0, Nv) or a coordinate that is not finite), the valid ones, T, the number of levels.  ``face_normals`` and
+    ``query`` are ``TriangleGrid``'s, and ``query`` returns its bits; nothing falls back."""
+    _module, _falls_back = "meshbvh", False
 
-    def __init__(self, vertices, triangles):
-        require_device(vertices)
-        dev = vertices.device
-        V = vertices.detach().to(torch.float32).contiguous()
-        if V.dim() != 2 or V.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-            raise RuntimeError("lara_amd.meshbvh: expected vertices [Nv,3] and triangles [T,3]")
-        F = triangles.to(device=dev, dtype=torch.int32).contiguous()
-        if V.shape[0] == 0:
-            raise ValueError("lara_amd.meshbvh: the mesh has no vertices")
-        T = F.shape[0]
-        nbytes = query("lara_meshbvh_bytes", T, error=ValueError("lara_amd.meshbvh: the mesh has no triangles (or 2^26 and more)"))
-        self.vertices, self.triangles, self.device = V, F, dev
+    def _build(self):
+        dev, V, F, T = self.device, self.vertices, self.triangles, self.n_triangles
+        self.bvh = self._buffer("lara_meshbvh_bytes")
         self.layout = layout(T)
-        self.bvh = alloc_bytes(nbytes, dev)
-        self._normals = None
         call("lara_meshbvh_keys", dev, V.shape[0], T, V, F, self.bvh)
         with torch.cuda.device(dev):
             self.keys = self.bvh[self.layout["keys"]:self.layout["keys"] + 8 * T].view(torch.int64)
@@ -58,9 +50,8 @@ class TriangleBVH:
         call("lara_meshbvh_build", dev, V.shape[0], T, V, F, self.bvh)
         self.counts = self.bvh[:4 * HEADER_INTS].view(torch.int32)
 
-    @property
-    def n_triangles(self):
-        return self.triangles.shape[0]
+    def _query(self, N, Q, dist, face, closest, fallbacks):
+        call("lara_meshbvh_query", self.device, N, Q, self.bvh, dist, face, closest)
 
     @property
     def nbytes(self):
@@ -76,33 +67,6 @@ class TriangleBVH:
         """[n_k,6] fp32 view of level ``k``'s boxes (lo, hi)."""
         o, n = self.layout["levels"][k]
         return self.bvh[o:o + 24 * n].view(torch.float32).view(-1, 6)
-
-    @property
-    def face_normals(self):
-        """[T,3] fp32 unit face normals (zero where a face has no area), computed once: ``TriangleGrid``'s."""
-        if self._normals is None:
-            self._normals = torch.empty(self.n_triangles, 3, dtype=torch.float32, device=self.device)
-            call("lara_meshdist_face_normals", self.device, self.vertices.shape[0], self.n_triangles, self.vertices, self.triangles,
-                 self._normals)
-        return self._normals
-
-    @torch.no_grad()
-    def query(self, points, return_closest=False, return_fallbacks=False):
-        """(dist [N] fp32, face [N] int32[, closest [N,3] fp32][, fallbacks: a zero device int32 [1]]) of ``points`` [N,3]: the
-        bits ``TriangleGrid.query`` returns.  face = -1 and dist = +inf for a point with a coordinate that is not finite, or when
-        the mesh has no valid triangle.  Nothing falls back; ``fallbacks`` is there for the callers that sum it.  No host read."""
-        Q = points.detach().to(self.device, torch.float32).contiguous()
-        if Q.dim() != 2 or Q.shape[1] != 3:
-            raise RuntimeError("lara_amd.meshbvh: expected points [N,3]")
-        N = Q.shape[0]
-        if N >= 1 << 30:
-            raise ValueError("lara_amd.meshbvh: 2^30 points and more")
-        dist = torch.empty(N, dtype=torch.float32, device=self.device)
-        face = torch.empty(N, dtype=torch.int32, device=self.device)
-        closest = torch.empty(N, 3, dtype=torch.float32, device=self.device) if return_closest else None
-        call("lara_meshbvh_query", self.device, N, Q, self.bvh, dist, face, closest)
-        fallbacks = torch.zeros(1, dtype=torch.int32, device=self.device) if return_fallbacks else None
-        return (dist, face) + ((closest,) if return_closest else ()) + ((fallbacks,) if return_fallbacks else ())
 
 
 @torch.no_grad()

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import meshmetrics
-from ._native import alloc_bytes, call, host_array, query, require_device
+from ._native import alloc_bytes, call, host_array, query, require_device, rows3
 
 RMAX, MAX_SPAN, MAX_GRID = 4, 4, 256                           # include/meshdist/lara_meshdist.h
 HEADER_INTS, HDR_BAD, HDR_LARGE, HDR_PAIRS, HDR_TRIANGLES = 4, 0, 1, 2, 3
@@ -31,28 +31,29 @@ def grid_resolution(T):
     return query("lara_meshdist_grid_resolution", int(T))
 
 
-class TriangleGrid:
-    """The search structure of one mesh (``vertices`` [Nv,3] fp32 on the device, ``triangles`` [T,3] of any integer type), built
-    on the current stream without a host read.  ``counts`` is a device int32 [4] view of the grid's header: triangles never taken
-    as candidates (an index outside [0, Nv) or a coordinate that is not finite), the large list's length, the (triangle, cell)
-    pairs, T."""
+class _TriangleSearch:
+    """What the search structures over one mesh share (``TriangleGrid`` here, ``meshbvh.TriangleBVH``): the mesh as the kernels
+    take it, the face normals, and ``query`` around the one call that differs.  A subclass names its ``_module``, says whether its
+    search ``_falls_back`` to brute force, builds its buffer in ``_build()`` and runs its search in ``_query(...)``."""
 
     def __init__(self, vertices, triangles):
         require_device(vertices)
         dev = vertices.device
         V = vertices.detach().to(torch.float32).contiguous()
         if V.dim() != 2 or V.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-            raise RuntimeError("lara_amd.meshdist: expected vertices [Nv,3] and triangles [T,3]")
+            raise RuntimeError(f"lara_amd.{self._module}: expected vertices [Nv,3] and triangles [T,3]")
         F = triangles.to(device=dev, dtype=torch.int32).contiguous()
         if V.shape[0] == 0:
-            raise ValueError("lara_amd.meshdist: the mesh has no vertices")
-        nbytes = query("lara_meshdist_grid_bytes", F.shape[0],
-                       error=ValueError("lara_amd.meshdist: the mesh has no triangles (or 2^26 and more)"))
+            raise ValueError(f"lara_amd.{self._module}: the mesh has no vertices")
         self.vertices, self.triangles, self.device = V, F, dev
-        self.grid = alloc_bytes(nbytes, dev)
         self._normals = None
-        call("lara_meshdist_build", dev, V.shape[0], F.shape[0], V, F, self.grid)
-        self.counts = self.grid[:4 * HEADER_INTS].view(torch.int32)
+        self._build()
+
+    def _buffer(self, bytes_query):
+        """The structure's uninitialised buffer, sized by the library for this mesh."""
+        nbytes = query(bytes_query, self.n_triangles,
+                       error=ValueError(f"lara_amd.{self._module}: the mesh has no triangles (or 2^26 and more)"))
+        return alloc_bytes(nbytes, self.device)
 
     @property
     def n_triangles(self):
@@ -69,19 +70,37 @@ class TriangleGrid:
 
     @torch.no_grad()
     def query(self, points, return_closest=False, return_fallbacks=False):
-        """(dist [N] fp32, face [N] int32[, closest [N,3] fp32][, fallbacks: device int32 [1]]) of ``points`` [N,3].  face = -1
-        and dist = +inf for a point with a coordinate that is not finite, or when the mesh has no valid triangle.  No host read."""
-        Q = points.detach().to(self.device, torch.float32).contiguous()
-        if Q.dim() != 2 or Q.shape[1] != 3:
-            raise RuntimeError("lara_amd.meshdist: expected points [N,3]")
+        """(dist [N] fp32, face [N] int32[, closest [N,3] fp32][, fallbacks: device int32 [1]]) of ``points`` [N,3]: the same bits
+        from either structure.  face = -1 and dist = +inf for a point with a coordinate that is not finite, or when the mesh has no
+        valid triangle.  ``fallbacks``: the queries brute force settled (the grid), zero where nothing falls back (the hierarchy);
+        there for the callers that sum it.  No host read."""
+        Q = rows3(points, self.device, "points", self._module)
         N = Q.shape[0]
-        nbytes = query("lara_meshdist_query_workspace_bytes", N, error=ValueError("lara_amd.meshdist: 2^30 points and more"))
+        if N >= 1 << 30:
+            raise ValueError(f"lara_amd.{self._module}: 2^30 points and more")
         dist = torch.empty(N, dtype=torch.float32, device=self.device)
         face = torch.empty(N, dtype=torch.int32, device=self.device)
         closest = torch.empty(N, 3, dtype=torch.float32, device=self.device) if return_closest else None
-        fallbacks = torch.zeros(1, dtype=torch.int32, device=self.device)
-        call("lara_meshdist_query", self.device, N, Q, self.grid, dist, face, closest, fallbacks, meshmetrics._workspace(self.device, nbytes))
+        fallbacks = torch.zeros(1, dtype=torch.int32, device=self.device) if return_fallbacks or self._falls_back else None
+        self._query(N, Q, dist, face, closest, fallbacks)
         return (dist, face) + ((closest,) if return_closest else ()) + ((fallbacks,) if return_fallbacks else ())
+
+
+class TriangleGrid(_TriangleSearch):
+    """The search structure of one mesh (``vertices`` [Nv,3] fp32 on the device, ``triangles`` [T,3] of any integer type), built
+    on the current stream without a host read.  ``counts`` is a device int32 [4] view of the grid's header: triangles never taken
+    as candidates (an index outside [0, Nv) or a coordinate that is not finite), the large list's length, the (triangle, cell)
+    pairs, T."""
+    _module, _falls_back = "meshdist", True
+
+    def _build(self):
+        self.grid = self._buffer("lara_meshdist_grid_bytes")
+        call("lara_meshdist_build", self.device, self.vertices.shape[0], self.n_triangles, self.vertices, self.triangles, self.grid)
+        self.counts = self.grid[:4 * HEADER_INTS].view(torch.int32)
+
+    def _query(self, N, Q, dist, face, closest, fallbacks):
+        ws = meshmetrics._workspace(self.device, query("lara_meshdist_query_workspace_bytes", N))
+        call("lara_meshdist_query", self.device, N, Q, self.grid, dist, face, closest, fallbacks, ws)
 
 
 def search_structure(search):

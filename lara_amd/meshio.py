@@ -21,22 +21,18 @@ import numpy as np
 import torch
 
 from . import mesh
-from ._native import alloc_bytes, call, query, require_device
+from ._native import StreamWorkspace, call, query, require_device
 
 BLOCK_LINES, MAX_F32_TOKEN, MAX_U32_TOKEN, MAX_VERTEX_LINE, MAX_FACE_LINE = 256, 15, 10, 98, 35     # include/meshio/lara_meshio.h
 PLY_FACE_ROW, MAX_VERTICES, MAX_TRIANGLES, MAX_INDEX = 13, 2 ** 31 - 1, (2 ** 31 - 1) // 3, 2 ** 31 - 2
 FORMATS = ("obj", "ply")
 
-_workspaces = {}      # (device index, stream) -> byte tensor, grown on demand
+_bytes = StreamWorkspace()
 _pinned = None        # the host side of write_mesh's one copy, grown on demand
 
 
 def _workspace(dev, nbytes):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[key] = alloc_bytes(nbytes, dev)
-    return ws[:nbytes].view(torch.int64)
+    return _bytes(dev, nbytes)[:nbytes].view(torch.int64)
 
 
 def _mark(marks, name):

@@ -20,20 +20,12 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._native import alloc_bytes, call, host_array, query, require_device
+from ._native import StreamWorkspace, call, host_array, query, require_device
 
 MAX_SAMPLES, RMAX, MAX_GRID, MAX_THRESHOLDS, ROW = 1 << 22, 4, 256, 8, 12      # include/meshmetrics/lara_meshmetrics.h
 THRESHOLDS = (0.005, 0.01, 0.02)      # in the units of the meshes; LaRa's scenes live in [-1, 1]^3 or smaller boxes
 
-_workspaces = {}      # (device index, stream) -> byte tensor, grown on demand
-
-
-def _workspace(dev, nbytes):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[key] = alloc_bytes(nbytes, dev)
-    return ws
+_workspace = StreamWorkspace()      # (meshdist and meshalign take theirs from here too)
 
 
 def grid_resolution(M):

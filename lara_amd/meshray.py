@@ -21,7 +21,7 @@ import math
 
 import torch
 
-from ._native import call
+from ._native import call, rows3
 
 MAX_EYES = 64                                                    # include/meshray/lara_meshray.h
 MASKED_ORDER = 1
@@ -81,9 +81,7 @@ def visibility(bvh, points, eyes, faces=None, shrink=2.0 ** -10):
     """int64 [N]: bit e is set when no triangle of ``bvh`` -- but ``faces[i]``, the one point i lies on -- meets the ray from
     ``eyes[e]`` to ``points[i]`` before the last ``shrink`` of it (d = fl32(point - eye), the window [0, 1 - shrink]).  A point
     with a coordinate that is not finite has 0.  At most 64 eyes."""
-    P = points.detach().to(bvh.device, torch.float32).contiguous()
-    if P.dim() != 2 or P.shape[1] != 3:
-        raise RuntimeError("lara_amd.meshray: expected points [N,3]")
+    P = rows3(points, bvh.device, "points", "meshray")
     E = torch.as_tensor(eyes).detach().to(bvh.device, torch.float32).contiguous()
     if E.dim() != 2 or E.shape[1] != 3 or E.shape[0] > MAX_EYES:
         raise ValueError(f"lara_amd.meshray: expected eyes [E,3] with E <= {MAX_EYES}")

@@ -18,7 +18,7 @@ import os
 
 import torch
 
-from ._native import alloc_bytes, call, host_array, query, require_device
+from ._native import StreamWorkspace, call, host_array, query, require_device
 
 ALBEDO = (0.25, 0.5, 0.8)               # configs/render/scene.xml: the bsdf's diffuse_reflectance
 BACKGROUND = (0.722, 0.376, 0.161)      # tools/meshRender.py:44
@@ -26,7 +26,7 @@ AMBIENT, DIFFUSE = 0.25, 0.75
 OUTPUTS = ("face_id", "depth", "normal", "frames", "info")
 SUBPIXEL, RANGE, FAR = 256, 1 << 22, 1 << 30      # include/meshrender/lara_meshrender.h
 
-_workspaces = {}      # (device index, stream) -> byte tensor, grown on demand
+_workspace = StreamWorkspace()      # its own: sections of it stay alive across calls
 
 
 def section_offsets(n_views, H, W, Nv, T):
@@ -34,14 +34,6 @@ def section_offsets(n_views, H, W, Nv, T):
     offs = host_array("l", 4)
     call("lara_meshrender_section_offsets", None, n_views, H, W, Nv, T, offs)
     return tuple(offs)
-
-
-def _workspace(dev, nbytes):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _workspaces[key] = alloc_bytes(nbytes, dev)
-    return ws
 
 
 def workspace_sections(ws, n_views, H, W, Nv, T):
