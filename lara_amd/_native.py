@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/`` and ``include/meshray/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/`` and ``include/meshsign/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -300,6 +300,16 @@ i lara_meshray_raytri_host(l p*8)
 i lara_meshray_box_entry_host(l p*6)
 """
 
+# include/meshsign/lara_meshsign.h, likewise; ``tests/test_meshsign.py`` holds this table to its header.
+MESHSIGN_SIGNATURES = """
+i lara_meshsign_rows(i p i p*3 s)
+i lara_meshsign_vote(i i p p i p*4 s)
+i lara_meshsign_counts(i p*5 s)
+i lara_meshsign_volume(p p s)
+i lara_meshsign_cross_host(l p*6)
+i lara_meshsign_rows_host(i p i l p*3)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -310,8 +320,9 @@ _SIGS_MESHDIST = _parse_signatures(MESHDIST_SIGNATURES)
 _SIGS_MESHALIGN = _parse_signatures(MESHALIGN_SIGNATURES)
 _SIGS_MESHBVH = _parse_signatures(MESHBVH_SIGNATURES)
 _SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
+_SIGS_MESHSIGN = _parse_signatures(MESHSIGN_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY}
+             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

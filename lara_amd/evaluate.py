@@ -329,6 +329,7 @@ class Evaluator:
         self.names, self.depth_accs = [], []
         self.psnrs, self.ssims, self.lpips_vggs, self.lpips_alexs = [], [], [], []
         self.geometry = []          # [(name, scores)] of add_geometry; empty: the JSON is the reference's
+        self.volume = []            # [(name, volume_iou)] of add_volume; empty: no key of it is written
 
     def add_scores(self, name, psnr=None, ssim=None, depth_acc=None, lpips_vgg=None, lpips_alex=None):
         """One scene's numbers (evaluation.py:92-95, :111, :113)."""
@@ -374,6 +375,16 @@ class Evaluator:
             raise ValueError("lara_amd.evaluate: the scenes of one Evaluator share their geometry thresholds")
         self.geometry.append((name, keep))
 
+    def add_volume(self, name, scores):
+        """One scene's volumetric IoU: the dict `lara_amd.meshsign.volume_scores` returns.  Written as ``volume_name``,
+        ``volume_iou`` and ``volume_iou_mean`` (None where a scene has None), behind every other key."""
+        iou = scores["volume_iou"]
+        self.volume.append((name, None if iou is None else float(iou)))
+
+    def _volume_summary(self):
+        vals = [v for _, v in self.volume]
+        return {"volume_name": [n for n, _ in self.volume], "volume_iou": vals, "volume_iou_mean": self._mean(vals)}
+
     GEOMETRY_SCALARS = ("accuracy", "completeness", "chamfer", "chamfer_sq", "normal_consistency")
     GEOMETRY_LISTS = ("precision", "recall", "fscore")          # one entry per threshold
 
@@ -397,7 +408,10 @@ class Evaluator:
         """The dictionary evaluation.py:167-172 dumps ('depth_acc' ends up holding the MEAN: the reference's update overwrites
         the per-scene list under the same key), or None when no scene had image scores (:164)."""
         if not self.psnrs:
-            return self._geometry_summary() if self.geometry else None
+            out = self._geometry_summary() if self.geometry else None
+            if self.volume:
+                out = dict(out or {}, **self._volume_summary())
+            return out
         if self.eval_depth and self.depth_accs:
             cols = list(zip(*self.depth_accs))
             mean_depth = [sum(c) / len(c) for c in cols]
@@ -409,6 +423,8 @@ class Evaluator:
                "lpips_alex_mean": self._mean(self.lpips_alexs)}
         if self.geometry:          # (behind the reference's keys, and only when add_geometry was called)
             out.update(self._geometry_summary())
+        if self.volume:            # (likewise, and only when add_volume was called)
+            out.update(self._volume_summary())
         return out
 
     def write(self, metric_path):
