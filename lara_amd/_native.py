@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/`` and ``include/meshsign/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/`` and ``include/meshtopo/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -310,6 +310,22 @@ i lara_meshsign_cross_host(l p*6)
 i lara_meshsign_rows_host(i p i l p*3)
 """
 
+# include/meshtopo/lara_meshtopo.h, likewise; ``tests/test_meshtopo.py`` holds this table to its header.
+MESHTOPO_SIGNATURES = """
+i lara_meshtopo_halfedge_keys(i i p*3 s)
+i lara_meshtopo_edge_heads(l p p s)
+i lara_meshtopo_edge_rows(l l p*10 s)
+i lara_meshtopo_report(i i l p*6 s)
+i lara_meshtopo_boundary_vertices(i l p*3 s)
+i lara_meshtopo_pair_keys(l p p s)
+i lara_meshtopo_corner_keys(i i p p s)
+i lara_meshtopo_csr(i l p i p p s)
+i lara_meshtopo_vertex_normals(i p*4 i p p s)
+i lara_meshtopo_smooth_pass(i p*4 d p s)
+i lara_meshtopo_normals_host(i p*4 i p p)
+i lara_meshtopo_smooth_host(i p*4 d p)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -321,8 +337,9 @@ _SIGS_MESHALIGN = _parse_signatures(MESHALIGN_SIGNATURES)
 _SIGS_MESHBVH = _parse_signatures(MESHBVH_SIGNATURES)
 _SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
 _SIGS_MESHSIGN = _parse_signatures(MESHSIGN_SIGNATURES)
+_SIGS_MESHTOPO = _parse_signatures(MESHTOPO_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN}
+             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN, **_SIGS_MESHTOPO}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

@@ -330,6 +330,7 @@ class Evaluator:
         self.psnrs, self.ssims, self.lpips_vggs, self.lpips_alexs = [], [], [], []
         self.geometry = []          # [(name, scores)] of add_geometry; empty: the JSON is the reference's
         self.volume = []            # [(name, volume_iou)] of add_volume; empty: no key of it is written
+        self.topology = []          # [(name, report)] of add_topology; empty: no key of it is written
 
     def add_scores(self, name, psnr=None, ssim=None, depth_acc=None, lpips_vgg=None, lpips_alex=None):
         """One scene's numbers (evaluation.py:92-95, :111, :113)."""
@@ -385,6 +386,20 @@ class Evaluator:
         vals = [v for _, v in self.volume]
         return {"volume_name": [n for n, _ in self.volume], "volume_iou": vals, "volume_iou_mean": self._mean(vals)}
 
+    def add_topology(self, name, report):
+        """One scene's mesh connectivity: the dict `lara_amd.meshtopo.MeshTopology.report` returns.  Written as ``topology_name``,
+        ``topology_closed``, ``topology_oriented``, ``topology_boundary_edges``, ``topology_nonmanifold_edges`` and
+        ``topology_euler``, one entry per scene, behind every other key."""
+        self.topology.append((name, {"closed": bool(report["is_closed"]), "oriented": bool(report["is_oriented"]),
+                                     "boundary_edges": int(report["n_boundary"]), "nonmanifold_edges": int(report["n_nonmanifold"]),
+                                     "euler": int(report["euler"])}))
+
+    def _topology_summary(self):
+        out = {"topology_name": [n for n, _ in self.topology]}
+        for k in ("closed", "oriented", "boundary_edges", "nonmanifold_edges", "euler"):
+            out["topology_" + k] = [r[k] for _, r in self.topology]
+        return out
+
     GEOMETRY_SCALARS = ("accuracy", "completeness", "chamfer", "chamfer_sq", "normal_consistency")
     GEOMETRY_LISTS = ("precision", "recall", "fscore")          # one entry per threshold
 
@@ -411,6 +426,8 @@ class Evaluator:
             out = self._geometry_summary() if self.geometry else None
             if self.volume:
                 out = dict(out or {}, **self._volume_summary())
+            if self.topology:
+                out = dict(out or {}, **self._topology_summary())
             return out
         if self.eval_depth and self.depth_accs:
             cols = list(zip(*self.depth_accs))
@@ -425,6 +442,8 @@ class Evaluator:
             out.update(self._geometry_summary())
         if self.volume:            # (likewise, and only when add_volume was called)
             out.update(self._volume_summary())
+        if self.topology:          # (likewise, and only when add_topology was called)
+            out.update(self._topology_summary())
         return out
 
     def write(self, metric_path):

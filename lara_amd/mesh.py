@@ -238,7 +238,8 @@ class MeshExtractor:
     @torch.no_grad()
     def extract(self, save_mesh_path, dataset_name, voxel_size=2 / 256, sdf_trunc=0.08, alpha_thres=0.08, depth_trunc=10,
                 sample=None, fov=None, device='cuda', cams=None, chunk=8, *, simplify_voxel=None, simplify_target=None,
-                simplify_contraction="quadric", writer="host"):
+                simplify_contraction="quadric", writer="host", smooth_iterations=None, smooth_method="taubin", smooth_lambda=0.5,
+                smooth_mu=-0.53, normals=False):
         """tools/meshExtractor.py:51-135: render the views, fuse them into a block-sparse TSDF volume (Open3D's
         ``ScalableTSDFVolume`` semantics, lara_amd.tsdf), marching cubes, ``clean_mesh`` (crop to the box, the 10 largest
         clusters), ``write_obj(save_mesh_path)``.  ``cams``: the views (the reference's ``MiniCam``s or
@@ -249,7 +250,11 @@ class MeshExtractor:
         with ``simplify_contraction``) before it is written, and ``last_simplify_info`` holds its ``info``; with both None
         nothing changes.  ``writer``: "host" (the default) writes through ``write_obj``; "device" through
         ``lara_amd.meshio.write_mesh``, which builds the file's bytes on the device and takes the format from the path's extension
-        (``.obj``: the same bytes; ``.ply``: binary PLY)."""
+        (``.obj``: the same bytes; ``.ply``: binary PLY).  ``smooth_iterations`` (None: no smoothing): the cleaned mesh's vertices go
+        through ``lara_amd.meshtopo`` before the simplification -- ``smooth_method`` "taubin" (``smooth_lambda``, ``smooth_mu``) or
+        "laplacian" (``smooth_lambda``) -- and ``last_smooth_info`` says what ran; triangles and colours stay.  ``normals=True``
+        (``writer="device"`` and a ``.ply`` path only) writes ``meshtopo.vertex_normals`` of the final mesh with it.  With the
+        defaults nothing changes and ``lara_amd.meshtopo`` is not imported."""
         from .batch import build_rays, fov_to_ixt
         from .renderer import Renderer
         from .tsdf import TSDFVolume
@@ -257,6 +262,16 @@ class MeshExtractor:
             raise ValueError("lara_amd.mesh.MeshExtractor: give simplify_voxel or simplify_target, not both")
         if writer not in ("host", "device"):
             raise ValueError('lara_amd.mesh.MeshExtractor: writer is "host" or "device"')
+        if smooth_iterations is not None:
+            if smooth_method not in ("taubin", "laplacian"):
+                raise ValueError('lara_amd.mesh.MeshExtractor: smooth_method is "taubin" or "laplacian"')
+            if int(smooth_iterations) < 0 or not all(math.isfinite(float(x)) for x in (smooth_lambda, smooth_mu)):
+                raise ValueError("lara_amd.mesh.MeshExtractor: smooth_iterations must be >= 0, smooth_lambda and smooth_mu finite")
+        if normals:
+            if writer != "device":
+                raise ValueError('lara_amd.mesh.MeshExtractor: normals=True needs writer="device" (the OBJ text of the host writer takes none)')
+            if not str(save_mesh_path).lower().endswith(".ply"):
+                raise ValueError("lara_amd.mesh.MeshExtractor: normals=True needs a .ply path (OBJ output takes no normals)")
         if cams is None:
             from tools.gen_video_path import uni_mesh_path          # LaRa's module (the reference's camera path)
             cams = uni_mesh_path(16, dataset_name, sample, fov)
@@ -313,6 +328,17 @@ class MeshExtractor:
         self._mark("clean_mesh")
         self.last_info = info
         self.raw_mesh = (verts, tris, cols)
+        self.last_smooth_info = None
+        if smooth_iterations is not None:
+            from . import meshtopo
+            topo = meshtopo.MeshTopology(v, t)
+            if smooth_method == "taubin":
+                v = topo.smooth_taubin(smooth_iterations, smooth_lambda, smooth_mu)
+            else:
+                v = topo.smooth_laplacian(smooth_iterations, smooth_lambda)
+            self.last_smooth_info = {"method": smooth_method, "iterations": int(smooth_iterations), "lambda": float(smooth_lambda),
+                                     "mu": float(smooth_mu) if smooth_method == "taubin" else None, "n_edges": topo.n_edges}
+            self._mark("smooth")
         self.last_simplify_info = None
         if simplify_voxel is not None or simplify_target is not None:
             from . import meshsimplify
@@ -324,7 +350,11 @@ class MeshExtractor:
             self._mark("simplify")
         if writer == "device":
             from . import meshio
-            meshio.write_mesh(save_mesh_path, v, t, c)
+            if normals:
+                from . import meshtopo
+                meshio.write_mesh(save_mesh_path, v, t, c, meshtopo.vertex_normals(v, t))
+            else:
+                meshio.write_mesh(save_mesh_path, v, t, c)
         else:
             write_obj(save_mesh_path, v, t, c)
         self._mark("write_obj")

@@ -189,9 +189,10 @@ _HEADER_RE = re.compile(rb"ply\nformat binary_little_endian 1\.0\ncomment lara_a
                         rb"element face (\d+)\nproperty list uchar int vertex_indices\nend_header\n")
 
 
-def read_ply(path):
+def read_ply(path, return_normals=False):
     """(vertices [Nv,3] fp32, triangles [T,3] int64, colors [Nv,3] fp32 = u8 / 255 or None) of a file this module wrote: the rows
-    through ``np.frombuffer`` with a structured dtype built from the header.  Normals, when the file has them, are skipped.  Any
+    through ``np.frombuffer`` with a structured dtype built from the header.  Normals, when the file has them, are skipped, or with
+    ``return_normals`` returned as a fourth item ([Nv,3] fp32, the file's bits; None when the file has none).  Any
     other header, a face that is no triangle or a size that does not fit raises ValueError."""
     with open(path, "rb") as f:
         data = f.read()
@@ -214,7 +215,13 @@ def read_ply(path):
     if has_c:
         c = np.stack([rows["red"], rows["green"], rows["blue"]], axis=1).astype(np.float32) / np.float32(255) if nv \
             else np.zeros((0, 3), np.float32)
-    return v, faces["i"].astype(np.int64).reshape(-1, 3), c
+    t = faces["i"].astype(np.int64).reshape(-1, 3)
+    if not return_normals:
+        return v, t, c
+    n = None
+    if has_n:
+        n = np.stack([rows["nx"], rows["ny"], rows["nz"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    return v, t, c, n
 
 
 def read_mesh(path):
