@@ -28,6 +28,26 @@
  *
  * lara_vit_forward: `save` = NULL is the inference form (nothing kept).  Otherwise `save` (lara_vit_save_bytes) receives everything
  * lara_vit_backward reads; the output is the same bit for bit.
+ *
+ * What `save` holds (lara_vit_save_offsets: byte offsets, n = 17, in this order; every region starts 256-byte aligned).  M = N T token
+ * rows (row n T + t), Mp = M rounded up to 128, Tp = T rounded up to 64, NP = N hw patch rows, Pp = NP rounded up to 128, NH = N heads:
+ *    0 patches    bf16 [Pp, 768]     step 1's rows, element (ch, ky, kx); rows >= NP are zero
+ *    1 xfin       fp32 [M, C]        the residual stream behind the last block (what the final LayerNorm reads)
+ *    2 stf        fp32 [M, 2]        (mean, rstd) of xfin's rows; the class-token rows (t = 0) are NOT written
+ *    3 the first block's base, 4 the block stride: block i's regions start at base + i * stride + the offsets below
+ *    5 xin        fp32 [M, C]        the block's input (block 0: the tokens of step 2; block i + 1's xin is block i's output)
+ *    6 xn1        bf16 [Mp, C]       bf16(LN1(xin)); rows >= M are zero
+ *    7 st1        fp32 [M, 2]        (mean, rstd) of xin's rows
+ *    8 q, 9 k, 10 v  bf16 [NH, Tp, 64]  head-major bf16(xn1 . Wqkv^T + bf16(b)); tokens t >= T are zero
+ *   11 o          bf16 [Mp, C]       the attention output, heads merged (head h: columns 64 h ..); rows >= M are zero
+ *   12 lse        fp32 [NH, Tp]      max + log(sum exp) of every query's scaled scores; entries t >= T are NOT written
+ *   13 xmid       fp32 [M, C]        xin + bf16(o . Wproj^T + bf16(b))
+ *   14 xn2        bf16 [Mp, C]       bf16(LN2(xmid)); rows >= M are zero
+ *   15 st2        fp32 [M, 2]        (mean, rstd) of xmid's rows
+ *   16 h          bf16 [Mp, F]       bf16(xn2 . W1^T + bf16(b1)), the GELU's input (its output is recomputed); rows >= M are zero
+ * The zero rows are part of the contract: the weight gradients are products over all Mp (Pp) rows.  Host code only; returns 0, or
+ * LARA2DGS_E_INVALID for dims the entry points refuse, a null `offsets` or n != 17.
+ *
  * lara_vit_backward: `grad` = dL/d(out) fp32 [N, hw, C]; writes (does not accumulate) every parameter gradient, fp32, in `grads`
  * (same order and shapes as `params`; grads[1] is the gradient of the resampled [T, C] table).  Bit-reproducible: no float atomics.
  * Parameter gradients are fixed-order partial sums (lara_gemm_tn_bf16 for the weights); the attention backward runs one wave per
@@ -65,6 +85,7 @@ typedef struct {
 
 int64_t lara_vit_workspace_bytes(const lara_vit_dims *d, int32_t training);
 int64_t lara_vit_save_bytes(const lara_vit_dims *d);
+int lara_vit_save_offsets(const lara_vit_dims *d, int64_t *offsets, int32_t n);
 
 int lara_vit_forward(const lara_vit_dims *d, const float *images, const float *const *params, float *out, void *save,
                      void *workspace, void *stream);

@@ -171,6 +171,7 @@ i lara_tsdf_mesh_emit(i p f p*9 s)
 # include/lara_vit.h
 l lara_vit_workspace_bytes(VitDims i)
 l lara_vit_save_bytes(VitDims)
+i lara_vit_save_offsets(VitDims p i)
 i lara_vit_forward(VitDims p*5 s)
 i lara_vit_backward(VitDims p*5 s)
 """

@@ -724,6 +724,17 @@ int64_t lara_vit_save_bytes(const lara_vit_dims *d) {
     return (int64_t)save_layout(g).total;
 }
 
+int lara_vit_save_offsets(const lara_vit_dims *d, int64_t *offsets, int32_t n) {
+    Geo g;
+    if (!make_geo(d, g) || !offsets || n != 17) return LARA2DGS_E_INVALID;
+    const SaveLay sl = save_layout(g);
+    const BlkOff &b = sl.b;
+    const size_t o[17] = {sl.patches, sl.xfin, sl.stf, sl.blk0, sl.blk_bytes, b.xin, b.xn1, b.st1, b.q, b.k, b.v, b.o, b.lse, b.xmid, b.xn2,
+                          b.st2, b.h};
+    for (int i = 0; i < 17; i++) offsets[i] = (int64_t)o[i];
+    return LARA2DGS_OK;
+}
+
 int64_t lara_vit_workspace_bytes(const lara_vit_dims *d, int32_t training) {
     Geo g;
     if (!make_geo(d, g)) return LARA2DGS_E_INVALID;

@@ -111,7 +111,7 @@ def table_mismatches(include_dir=None):
 def test_signature_table_equals_the_headers():
     """Every function the headers declare has a row, every row a declaration, and they agree in the return type and, position by
     position, in the kind of every parameter (pointer / int32 / int64 / float)."""
-    assert len(header_functions()) == len(_native._SIGS) == 91
+    assert len(header_functions()) == len(_native._SIGS) == 92
     assert table_mismatches() == []
 
 
@@ -122,7 +122,7 @@ def test_stream_flag_follows_the_prototype():
         for name, params in re.findall(r"\b(lara2dgs_\w+|lara_\w+)\s*\(([^()]*)\)\s*;", text):
             assert _native._SIGS[name][2] == bool(re.search(r"void\s*\*\s*stream\s*$", params)), name
             seen += 1
-    assert seen == 91
+    assert seen == 92
 
 
 def test_a_changed_prototype_fails_the_table_check(tmp_path):
@@ -261,6 +261,47 @@ def test_block_save_offsets_follow_the_save_area(hip_lib):
     for bad in ((1, 4, 10), (1, 4, 12), (1, 5, 11), (1, 2, 11), (-1, 4, 11)):
         assert fn(bad[0], bad[1], offs, bad[2]) == -1
     assert fn(1, 4, None, 11) == -1
+
+
+def test_vit_save_offsets_follow_the_save_area(hip_lib):
+    """lara_vit_save_offsets (host code only): patches, xfin, stf, the first block's base, the block stride and the twelve
+    per-block offsets -- increasing, 256-byte aligned, every region inside lara_vit_save_bytes with room for what the header
+    says it holds; bad dims, a null array or a wrong count are refused."""
+    fn = hip_lib.lara_vit_save_offsets
+
+    def dims(N, views, H, W, C, F, depth, heads=None):
+        d = _native.VitDims()
+        d.N, d.views, d.H, d.W, d.C, d.F, d.depth, d.eps = N, views, H, W, C, F, depth, 1e-6
+        d.heads = C // 64 if heads is None else heads
+        return d
+    rup = lambda v, m: (v + m - 1) // m * m
+    offs = (ctypes.c_int64 * 17)()
+    for case in ((1, 1, 16, 16, 64, 64, 1), (3, 1, 64, 128, 128, 192, 1), (2, 2, 112, 144, 320, 1280, 2), (3, 1, 128, 128, 1024, 256, 1),
+                 (16, 4, 512, 512, 768, 3072, 12)):
+        N, _, H, W, C, F, depth = case
+        d = dims(*case)
+        assert fn(ctypes.byref(d), offs, 17) == 0
+        o = list(offs)
+        total = hip_lib.lara_vit_save_bytes(ctypes.byref(d))
+        T = 1 + (H // 16) * (W // 16)
+        M, Mp, Tp, NH, Pp = N * T, rup(N * T, 128), rup(T, 64), N * C // 64, rup(N * (T - 1), 128)
+        assert all(v % 256 == 0 for v in o)
+        head, base, stride, blk = o[:3], o[3], o[4], o[5:]
+        assert head[0] == 0 and head == sorted(set(head)) and blk[0] == 0 and blk == sorted(set(blk))
+        assert base + depth * stride == total
+        sizes = [Pp * 768 * 2, M * C * 4, M * 8]                                                    # patches xfin stf
+        assert all(b - a >= n for a, b, n in zip(head, head[1:] + [base], sizes))
+        hd = NH * Tp * 64 * 2
+        sizes = [M * C * 4, Mp * C * 2, M * 8, hd, hd, hd, Mp * C * 2, NH * Tp * 4, M * C * 4, Mp * C * 2, M * 8, Mp * F * 2]
+        assert all(b - a >= n for a, b, n in zip(blk, blk[1:] + [stride], sizes))                   # xin .. h
+    good = (1, 1, 16, 16, 64, 64, 1)
+    for n in (16, 18, 0, -1):
+        assert fn(ctypes.byref(dims(*good)), offs, n) == -1
+    assert fn(ctypes.byref(dims(*good)), None, 17) == -1 and fn(None, offs, 17) == -1
+    for bad in ((0, 1, 16, 16, 64, 64, 1), (3, 2, 16, 16, 64, 64, 1), (1, 1, 24, 16, 64, 64, 1), (1, 1, 16, 16, 96, 64, 1),
+                (1, 1, 16, 16, 1088, 64, 1), (1, 1, 16, 16, 64, 32, 1), (1, 1, 16, 16, 64, 64, 0), (1, 1, 16, 16, 64, 64, 65)):
+        assert fn(ctypes.byref(dims(*bad)), offs, 17) == -1, bad
+    assert fn(ctypes.byref(dims(*good, heads=2)), offs, 17) == -1
 
 
 def test_sizes_and_layout_are_consistent(hip_lib):
