@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/`` and ``include/meshtopo/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/``, ``include/meshtopo/`` and ``include/meshwind/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -327,6 +327,16 @@ i lara_meshtopo_normals_host(i p*4 i p p)
 i lara_meshtopo_smooth_host(i p*4 d p)
 """
 
+# include/meshwind/lara_meshwind.h, likewise; ``tests/test_meshwind.py`` holds this table to its header.
+MESHWIND_SIGNATURES = """
+l lara_meshwind_moments_bytes(i)
+i lara_meshwind_moments(i p p s)
+i lara_meshwind_rows(i p*3 d p*3 s)
+i lara_meshwind_classify(i p d d p*4 s)
+i lara_meshwind_solid_host(l p*3)
+i lara_meshwind_brute_host(i p l p p)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -339,8 +349,10 @@ _SIGS_MESHBVH = _parse_signatures(MESHBVH_SIGNATURES)
 _SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
 _SIGS_MESHSIGN = _parse_signatures(MESHSIGN_SIGNATURES)
 _SIGS_MESHTOPO = _parse_signatures(MESHTOPO_SIGNATURES)
+_SIGS_MESHWIND = _parse_signatures(MESHWIND_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN, **_SIGS_MESHTOPO}
+             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN, **_SIGS_MESHTOPO,
+             **_SIGS_MESHWIND}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 
