@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/``, ``include/meshtopo/`` and ``include/meshwind/``), and the checked call the modules of this package go through.
+the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/``, ``include/meshtopo/``, ``include/meshwind/`` and ``include/meshtexture/``), and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -337,6 +337,17 @@ i lara_meshwind_solid_host(l p*3)
 i lara_meshwind_brute_host(i p l p p)
 """
 
+# include/meshtexture/lara_meshtexture.h, likewise; ``tests/test_meshtexture.py`` holds this table to its header.
+MESHTEXTURE_SIGNATURES = """
+i lara_meshtexture_atlas_size(i*3 p)
+i lara_meshtexture_texels(i*4 p*5 s)
+i lara_meshtexture_texels_host(i*4 p*5)
+i lara_meshtexture_bake(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3 s)
+i lara_meshtexture_bake_host(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3)
+i lara_meshtexture_sample(i*3 l p*3 i f*3 p s)
+i lara_meshtexture_sample_host(i*3 l p*3 i f*3 p)
+"""
+
 _SIGS = _parse_signatures(SIGNATURES)
 _SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
 _SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
@@ -350,9 +361,10 @@ _SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
 _SIGS_MESHSIGN = _parse_signatures(MESHSIGN_SIGNATURES)
 _SIGS_MESHTOPO = _parse_signatures(MESHTOPO_SIGNATURES)
 _SIGS_MESHWIND = _parse_signatures(MESHWIND_SIGNATURES)
+_SIGS_MESHTEXTURE = _parse_signatures(MESHTEXTURE_SIGNATURES)
 _ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
              **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN, **_SIGS_MESHTOPO,
-             **_SIGS_MESHWIND}
+             **_SIGS_MESHWIND, **_SIGS_MESHTEXTURE}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 

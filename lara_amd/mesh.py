@@ -239,7 +239,7 @@ class MeshExtractor:
     def extract(self, save_mesh_path, dataset_name, voxel_size=2 / 256, sdf_trunc=0.08, alpha_thres=0.08, depth_trunc=10,
                 sample=None, fov=None, device='cuda', cams=None, chunk=8, *, simplify_voxel=None, simplify_target=None,
                 simplify_contraction="quadric", writer="host", smooth_iterations=None, smooth_method="taubin", smooth_lambda=0.5,
-                smooth_mu=-0.53, normals=False):
+                smooth_mu=-0.53, normals=False, texture_patch=None, texture_max_texels=None, texture_blend="weighted"):
         """tools/meshExtractor.py:51-135: render the views, fuse them into a block-sparse TSDF volume (Open3D's
         ``ScalableTSDFVolume`` semantics, lara_amd.tsdf), marching cubes, ``clean_mesh`` (crop to the box, the 10 largest
         clusters), ``write_obj(save_mesh_path)``.  ``cams``: the views (the reference's ``MiniCam``s or
@@ -254,7 +254,11 @@ class MeshExtractor:
         through ``lara_amd.meshtopo`` before the simplification -- ``smooth_method`` "taubin" (``smooth_lambda``, ``smooth_mu``) or
         "laplacian" (``smooth_lambda``) -- and ``last_smooth_info`` says what ran; triangles and colours stay.  ``normals=True``
         (``writer="device"`` and a ``.ply`` path only) writes ``meshtopo.vertex_normals`` of the final mesh with it.  With the
-        defaults nothing changes and ``lara_amd.meshtopo`` is not imported."""
+        defaults nothing changes and ``lara_amd.meshtopo`` is not imported.  ``texture_patch`` (a patch size) or ``texture_max_texels``
+        (a texel budget), one of them at most, a ``.obj`` path, the host writer and at most 64 views only: the views' float images and cameras are kept, the final mesh
+        -- after smoothing and simplification -- is baked from them by ``lara_amd.meshtexture.bake`` (``texture_blend``, the vertex
+        colours as the fallback) and written by ``write_textured_obj`` with its ``.mtl`` and ``.png``; ``last_texture`` holds the
+        ``Texture``.  With both None ``lara_amd.meshtexture`` is not imported and the written bytes are what they were."""
         from .batch import build_rays, fov_to_ixt
         from .renderer import Renderer
         from .tsdf import TSDFVolume
@@ -272,10 +276,24 @@ class MeshExtractor:
                 raise ValueError('lara_amd.mesh.MeshExtractor: normals=True needs writer="device" (the OBJ text of the host writer takes none)')
             if not str(save_mesh_path).lower().endswith(".ply"):
                 raise ValueError("lara_amd.mesh.MeshExtractor: normals=True needs a .ply path (OBJ output takes no normals)")
+        textured = texture_patch is not None or texture_max_texels is not None
+        if textured:
+            if texture_patch is not None and texture_max_texels is not None:
+                raise ValueError("lara_amd.mesh.MeshExtractor: give texture_patch or texture_max_texels, not both")
+            if not str(save_mesh_path).lower().endswith(".obj"):
+                raise ValueError("lara_amd.mesh.MeshExtractor: a textured mesh needs a .obj path")
+            if texture_blend not in ("weighted", "best"):
+                raise ValueError('lara_amd.mesh.MeshExtractor: texture_blend is "weighted" or "best"')
+            if texture_patch is not None and int(texture_patch) < 3:
+                raise ValueError("lara_amd.mesh.MeshExtractor: texture_patch must be >= 3")
+            if normals or writer != "host":
+                raise ValueError('lara_amd.mesh.MeshExtractor: a textured mesh is written by the host writer (writer="host", no normals)')
         if cams is None:
             from tools.gen_video_path import uni_mesh_path          # LaRa's module (the reference's camera path)
             cams = uni_mesh_path(16, dataset_name, sample, fov)
         cams = list(cams)
+        if textured and len(cams) > 64:
+            raise ValueError("lara_amd.mesh.MeshExtractor: a texture is baked from at most 64 views")
         _centers, _shs, _opacity, _scaling, _rotation, mask = self.gs_params
         opacity, scaling, rotation = _opacity[mask], _scaling[mask], _rotation[mask]     # meshExtractor.py:85
         if self.aabb is not None:                                                        # meshExtractor.py:54-58
@@ -290,6 +308,7 @@ class MeshExtractor:
         self.last_grid = (origin, voxel_size, res)
         vol = TSDFVolume(origin, voxel_size, sdf_trunc, res, device=device)
         self._mark("start")
+        kept = []                     # (image [n,H,W,3], ixt [n,3,3], c2w [n,4,4]) of every chunk, for the texture
         for o in range(0, len(cams), chunk):
             part = cams[o:o + chunk]
             for cam in part:
@@ -313,6 +332,8 @@ class MeshExtractor:
             acc = torch.stack([p["acc_map"].reshape(H, W) for p in pkgs])
             depth = torch.where(acc < alpha_thres, torch.zeros_like(depth), depth)
             color = (torch.stack([p["image"].reshape(H, W, 3) for p in pkgs]) * 255).to(torch.uint8).float()
+            if textured:
+                kept.append((torch.stack([p["image"].reshape(H, W, 3) for p in pkgs]).float(), ixt.float().cpu(), c2w.float().cpu()))
             K = torch.tensor([_intrinsics(cam) for cam in part])
             E = torch.stack([cam.world_view_transform.T for cam in part]).reshape(-1, 4, 4)
             if self.aabb is not None:                                                    # meshExtractor.py:95-97
@@ -348,6 +369,18 @@ class MeshExtractor:
                 v, t, c, sinfo = meshsimplify.simplify_to(v, t, c, simplify_target, simplify_contraction)
             self.last_simplify_info = sinfo
             self._mark("simplify")
+        self.last_texture = None
+        if textured:
+            from . import meshtexture
+            if len({tuple(k[0].shape[1:]) for k in kept}) != 1:
+                raise RuntimeError("lara_amd.mesh.MeshExtractor: a textured mesh needs views of one image size")
+            self.last_texture = meshtexture.bake(v, t, torch.cat([k[0] for k in kept]), torch.cat([k[1] for k in kept]),
+                                                 torch.cat([k[2] for k in kept]), patch=texture_patch, max_texels=texture_max_texels,
+                                                 vertex_colors=c, blend=texture_blend)
+            self._mark("texture")
+            meshtexture.write_textured_obj(save_mesh_path, v, t, self.last_texture)
+            self._mark("write_obj")
+            return v, t, c
         if writer == "device":
             from . import meshio
             if normals:
