@@ -14,6 +14,10 @@
  *          grid = (xy + 0.5) / (w, h) * 2 - 1 and align_corners=False the sample position is exactly (x, y)]
  *   out[v][c][i] = s_c  (c = 0..6),   out[v][7][i] = | s_7 - z |
  *
+ * A (point, view) whose position is not finite (q.z = 0, a NaN or inf coordinate) or lies far outside the image has no tap inside:
+ * channels 0..6 are 0 and channel 7 is |0 - z|, the backward adds nothing of it to the three map gradients, and no other point is
+ * affected; only d_points of a point with a non-finite position is unspecified (NaN, as autograd's is).
+ *
  * points [n,3]; w2cs [V,4,4]; ixts [V,3,3]; img_ref [V,3,h,w] (planar, as `_inps[i]`); image [V,h,w,3],
  * acc_map [V,h,w], depth [V,h,w,1] (channel-last, as `render_img` returns them); out [V,8,n].  fp32, device.
  * Backward: g_out [V,8,n] -> d_points [n,3] (overwritten) and ACCUMULATES into d_image, d_acc_map, d_depth
