@@ -1,5 +1,5 @@
 """The one ctypes binding of ``liblara2dgs.so``: the loader, the mirrors of the header structs, the signature of every function
-the 14 headers under ``include/`` declare (and, in tables of their own, those of ``include/meshrender/``, ``include/meshmetrics/``, ``include/meshsimplify/``, ``include/depthsurface/``, ``include/meshio/``, ``include/meshdist/``, ``include/meshalign/``, ``include/meshbvh/``, ``include/meshray/``, ``include/meshsign/``, ``include/meshtopo/``, ``include/meshwind/`` and ``include/meshtexture/``), and the checked call the modules of this package go through.
+the headers under ``include/`` declare, and the checked call the modules of this package go through.
 
 The headers are the contract; ``SIGNATURES`` and the ``Structure`` classes below are its Python copy, and
 ``tests/test_abi_cpu.py`` holds one against the other (names, order, kinds) without the library or a device.  A new entry point
@@ -89,6 +89,15 @@ i lara2dgs_profile_collect(p i p i)
 l lara_coarse_decoder_padded_rows(l)
 i lara_coarse_decoder_forward(i*3 p*7 f f p*5 s)
 i lara_coarse_decoder_backward(i*3 p*19 s)
+# include/lara_depthsurface.h
+l lara_depthsurface_backproject_workspace_bytes(i*3)
+i lara_depthsurface_backproject_count(i*3 p p i i f p p s)
+i lara_depthsurface_backproject_emit(i*3 p p i i f p p i p f p*4 s)
+l lara_depthsurface_thin_workspace_bytes(i i)
+i lara_depthsurface_thin(i p p f i p*5 s)
+i lara_depthsurface_observe(i p i*3 p p i f p p f i p s)
+l lara_depthsurface_reduce_workspace_bytes(i)
+i lara_depthsurface_reduce(i i p*5 i p*3 s)
 # include/lara_eval.h
 l lara_eval_workspace_doubles(i*6)
 i lara_eval_scores(i*3 ImageView ImageView p i*3 p*3 i i p*3 s)
@@ -139,6 +148,17 @@ l lara_lpips_workspace_bytes(LpipsNet i*3)
 i lara_lpips_forward(LpipsNet i*3 ImageView ImageView f f p p s)
 i lara_lpips_conv2d(i*9 p*4 s)
 i lara_lpips_maxpool(i*6 p p s)
+# include/lara_meshalign.h
+i lara_meshalign_transform(i p*3 d p p s)
+l lara_meshalign_accumulate_workspace_bytes(i)
+i lara_meshalign_accumulate(i*3 p*6 f p*3 s)
+# include/lara_meshbvh.h
+l lara_meshbvh_bytes(i)
+i lara_meshbvh_layout(i p)
+i lara_meshbvh_keys(i i p*3 s)
+i lara_meshbvh_build(i i p*3 s)
+i lara_meshbvh_query(i p*5 s)
+i lara_meshbvh_box_bound_host(l p*3)
 # include/lara_meshclean.h
 i lara_mesh_crop(l l p*5 s)
 i lara_mesh_compact_rows(l i p*4 s)
@@ -146,6 +166,90 @@ i lara_mesh_cluster_labels(l p l p*6 s)
 i lara_mesh_cluster_stats(l l p*4 l p*5 s)
 i lara_mesh_keep_clusters(l l p*7 s)
 i lara_mesh_remap(l l p*4 s)
+# include/lara_meshdist.h
+i lara_meshdist_grid_resolution(i)
+l lara_meshdist_grid_bytes(i)
+i lara_meshdist_build(i i p*3 s)
+l lara_meshdist_query_workspace_bytes(i)
+i lara_meshdist_query(i p*7 s)
+i lara_meshdist_face_normals(i i p*3 s)
+i lara_meshdist_point_triangle_host(l p*4)
+# include/lara_meshio.h
+l lara_meshio_obj_workspace_bytes(l l)
+i lara_meshio_obj_lengths(l p p l p i p s)
+i lara_meshio_obj_emit(l p p l p i p p s)
+l lara_meshio_ply_body_bytes(l l i i)
+l lara_meshio_ply_workspace_bytes()
+i lara_meshio_ply_pack(l p*3 l p i p p s)
+i lara_meshio_format_f32_host(l p*3)
+i lara_meshio_format_u32_host(l p*3)
+# include/lara_meshmetrics.h
+l lara_meshmetrics_sample_workspace_bytes(i)
+i lara_meshmetrics_sample_surface(i i p p i i p*6 s)
+i lara_meshmetrics_grid_resolution(i)
+l lara_meshmetrics_nearest_workspace_bytes(i i)
+i lara_meshmetrics_nearest(i i p*6 s)
+l lara_meshmetrics_reduce_workspace_bytes(i)
+i lara_meshmetrics_reduce(i i p*4 i p*3 s)
+# include/lara_meshray.h
+i lara_meshray_cast(i p*8 s)
+i lara_meshray_cast_other_order(i p*8 s)
+i lara_meshray_occluded(i p*6 s)
+i lara_meshray_visible(i p p i p f p p s)
+i lara_meshray_raytri_host(l p*8)
+i lara_meshray_box_entry_host(l p*6)
+# include/lara_meshrender.h
+l lara_meshrender_workspace_bytes(i*5)
+i lara_meshrender_section_offsets(i*5 p)
+i lara_meshrender_views(i*5 p*6 f p i p*7 s)
+# include/lara_meshsign.h
+i lara_meshsign_rows(i p i p*3 s)
+i lara_meshsign_vote(i i p p i p*4 s)
+i lara_meshsign_counts(i p*5 s)
+i lara_meshsign_volume(p p s)
+i lara_meshsign_cross_host(l p*6)
+i lara_meshsign_rows_host(i p i l p*3)
+# include/lara_meshsimplify.h
+l lara_meshsimplify_cells_workspace_bytes(l)
+i lara_meshsimplify_cells(l p f p*5 s)
+i lara_meshsimplify_clusters(l p*5 s)
+l lara_meshsimplify_triangles_workspace_bytes(l)
+i lara_meshsimplify_triangles(l*3 p*8 s)
+i lara_meshsimplify_corner_keys(l l p*5 s)
+i lara_meshsimplify_bucket_count(l l p p s)
+l lara_meshsimplify_bucket_workspace_bytes(l l)
+i lara_meshsimplify_bucket_fill(l l p*4 s)
+i lara_meshsimplify_sums(l*3 p*7 i p*3 s)
+i lara_meshsimplify_solve(l l i p*4 f p*4 s)
+i lara_meshsimplify_vertex_map(l l p*4 s)
+# include/lara_meshtexture.h
+i lara_meshtexture_atlas_size(i*3 p)
+i lara_meshtexture_texels(i*4 p*5 s)
+i lara_meshtexture_texels_host(i*4 p*5)
+i lara_meshtexture_bake(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3 s)
+i lara_meshtexture_bake_host(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3)
+i lara_meshtexture_sample(i*3 l p*3 i f*3 p s)
+i lara_meshtexture_sample_host(i*3 l p*3 i f*3 p)
+# include/lara_meshtopo.h
+i lara_meshtopo_halfedge_keys(i i p*3 s)
+i lara_meshtopo_edge_heads(l p p s)
+i lara_meshtopo_edge_rows(l l p*10 s)
+i lara_meshtopo_report(i i l p*6 s)
+i lara_meshtopo_boundary_vertices(i l p*3 s)
+i lara_meshtopo_pair_keys(l p p s)
+i lara_meshtopo_corner_keys(i i p p s)
+i lara_meshtopo_csr(i l p i p p s)
+i lara_meshtopo_vertex_normals(i p*4 i p p s)
+i lara_meshtopo_smooth_pass(i p*4 d p s)
+i lara_meshtopo_normals_host(i p*4 i p p)
+i lara_meshtopo_smooth_host(i p*4 d p)
+# include/lara_meshwind.h
+l lara_meshwind_moments_bytes(i)
+i lara_meshwind_moments(i p p s)
+i lara_meshwind_rows(i p*3 d p*3 s)
+i lara_meshwind_classify(i p d d p*4 s)
+i lara_meshwind_solid_host(l p*3)
+i lara_meshwind_brute_host(i p l p p)
 # include/lara_pointfeat.h
 l lara_point_feats_workspace_bytes(i*3)
 i lara_point_feats_forward(i*4 p*9 s)
@@ -203,168 +307,7 @@ def _parse_signatures(text):
     return table
 
 
-# include/meshrender/lara_meshrender.h, in the same notation.  A table of its own: ``tests/test_abi_cpu.py`` pins the number of
-# functions the headers directly under ``include/`` declare, and ``SIGNATURES`` with it; ``tests/test_meshrender.py`` holds this
-# table to its header with the same comparison.
-MESHRENDER_SIGNATURES = """
-l lara_meshrender_workspace_bytes(i*5)
-i lara_meshrender_section_offsets(i*5 p)
-i lara_meshrender_views(i*5 p*6 f p i p*7 s)
-"""
-
-# include/meshmetrics/lara_meshmetrics.h, likewise; ``tests/test_meshmetrics.py`` holds this table to its header.
-MESHMETRICS_SIGNATURES = """
-l lara_meshmetrics_sample_workspace_bytes(i)
-i lara_meshmetrics_sample_surface(i i p p i i p*6 s)
-i lara_meshmetrics_grid_resolution(i)
-l lara_meshmetrics_nearest_workspace_bytes(i i)
-i lara_meshmetrics_nearest(i i p*6 s)
-l lara_meshmetrics_reduce_workspace_bytes(i)
-i lara_meshmetrics_reduce(i i p*4 i p*3 s)
-"""
-
-# include/meshsimplify/lara_meshsimplify.h, likewise; ``tests/test_meshsimplify.py`` holds this table to its header.
-MESHSIMPLIFY_SIGNATURES = """
-l lara_meshsimplify_cells_workspace_bytes(l)
-i lara_meshsimplify_cells(l p f p*5 s)
-i lara_meshsimplify_clusters(l p*5 s)
-l lara_meshsimplify_triangles_workspace_bytes(l)
-i lara_meshsimplify_triangles(l*3 p*8 s)
-i lara_meshsimplify_corner_keys(l l p*5 s)
-i lara_meshsimplify_bucket_count(l l p p s)
-l lara_meshsimplify_bucket_workspace_bytes(l l)
-i lara_meshsimplify_bucket_fill(l l p*4 s)
-i lara_meshsimplify_sums(l*3 p*7 i p*3 s)
-i lara_meshsimplify_solve(l l i p*4 f p*4 s)
-i lara_meshsimplify_vertex_map(l l p*4 s)
-"""
-
-# include/depthsurface/lara_depthsurface.h, likewise; ``tests/test_depthsurface.py`` holds this table to its header.
-DEPTHSURFACE_SIGNATURES = """
-l lara_depthsurface_backproject_workspace_bytes(i*3)
-i lara_depthsurface_backproject_count(i*3 p p i i f p p s)
-i lara_depthsurface_backproject_emit(i*3 p p i i f p p i p f p*4 s)
-l lara_depthsurface_thin_workspace_bytes(i i)
-i lara_depthsurface_thin(i p p f i p*5 s)
-i lara_depthsurface_observe(i p i*3 p p i f p p f i p s)
-l lara_depthsurface_reduce_workspace_bytes(i)
-i lara_depthsurface_reduce(i i p*5 i p*3 s)
-"""
-
-# include/meshio/lara_meshio.h, likewise; ``tests/test_meshio.py`` holds this table to its header.
-MESHIO_SIGNATURES = """
-l lara_meshio_obj_workspace_bytes(l l)
-i lara_meshio_obj_lengths(l p p l p i p s)
-i lara_meshio_obj_emit(l p p l p i p p s)
-l lara_meshio_ply_body_bytes(l l i i)
-l lara_meshio_ply_workspace_bytes()
-i lara_meshio_ply_pack(l p*3 l p i p p s)
-i lara_meshio_format_f32_host(l p*3)
-i lara_meshio_format_u32_host(l p*3)
-"""
-
-# include/meshdist/lara_meshdist.h, likewise; ``tests/test_meshdist.py`` holds this table to its header.
-MESHDIST_SIGNATURES = """
-i lara_meshdist_grid_resolution(i)
-l lara_meshdist_grid_bytes(i)
-i lara_meshdist_build(i i p*3 s)
-l lara_meshdist_query_workspace_bytes(i)
-i lara_meshdist_query(i p*7 s)
-i lara_meshdist_face_normals(i i p*3 s)
-i lara_meshdist_point_triangle_host(l p*4)
-"""
-
-# include/meshalign/lara_meshalign.h, likewise; ``tests/test_meshalign.py`` holds this table to its header.
-MESHALIGN_SIGNATURES = """
-i lara_meshalign_transform(i p*3 d p p s)
-l lara_meshalign_accumulate_workspace_bytes(i)
-i lara_meshalign_accumulate(i*3 p*6 f p*3 s)
-"""
-
-# include/meshbvh/lara_meshbvh.h, likewise; ``tests/test_meshbvh.py`` holds this table to its header.
-MESHBVH_SIGNATURES = """
-l lara_meshbvh_bytes(i)
-i lara_meshbvh_layout(i p)
-i lara_meshbvh_keys(i i p*3 s)
-i lara_meshbvh_build(i i p*3 s)
-i lara_meshbvh_query(i p*5 s)
-i lara_meshbvh_box_bound_host(l p*3)
-"""
-
-# include/meshray/lara_meshray.h, likewise; ``tests/test_meshray.py`` holds this table to its header.
-MESHRAY_SIGNATURES = """
-i lara_meshray_cast(i p*8 s)
-i lara_meshray_cast_other_order(i p*8 s)
-i lara_meshray_occluded(i p*6 s)
-i lara_meshray_visible(i p p i p f p p s)
-i lara_meshray_raytri_host(l p*8)
-i lara_meshray_box_entry_host(l p*6)
-"""
-
-# include/meshsign/lara_meshsign.h, likewise; ``tests/test_meshsign.py`` holds this table to its header.
-MESHSIGN_SIGNATURES = """
-i lara_meshsign_rows(i p i p*3 s)
-i lara_meshsign_vote(i i p p i p*4 s)
-i lara_meshsign_counts(i p*5 s)
-i lara_meshsign_volume(p p s)
-i lara_meshsign_cross_host(l p*6)
-i lara_meshsign_rows_host(i p i l p*3)
-"""
-
-# include/meshtopo/lara_meshtopo.h, likewise; ``tests/test_meshtopo.py`` holds this table to its header.
-MESHTOPO_SIGNATURES = """
-i lara_meshtopo_halfedge_keys(i i p*3 s)
-i lara_meshtopo_edge_heads(l p p s)
-i lara_meshtopo_edge_rows(l l p*10 s)
-i lara_meshtopo_report(i i l p*6 s)
-i lara_meshtopo_boundary_vertices(i l p*3 s)
-i lara_meshtopo_pair_keys(l p p s)
-i lara_meshtopo_corner_keys(i i p p s)
-i lara_meshtopo_csr(i l p i p p s)
-i lara_meshtopo_vertex_normals(i p*4 i p p s)
-i lara_meshtopo_smooth_pass(i p*4 d p s)
-i lara_meshtopo_normals_host(i p*4 i p p)
-i lara_meshtopo_smooth_host(i p*4 d p)
-"""
-
-# include/meshwind/lara_meshwind.h, likewise; ``tests/test_meshwind.py`` holds this table to its header.
-MESHWIND_SIGNATURES = """
-l lara_meshwind_moments_bytes(i)
-i lara_meshwind_moments(i p p s)
-i lara_meshwind_rows(i p*3 d p*3 s)
-i lara_meshwind_classify(i p d d p*4 s)
-i lara_meshwind_solid_host(l p*3)
-i lara_meshwind_brute_host(i p l p p)
-"""
-
-# include/meshtexture/lara_meshtexture.h, likewise; ``tests/test_meshtexture.py`` holds this table to its header.
-MESHTEXTURE_SIGNATURES = """
-i lara_meshtexture_atlas_size(i*3 p)
-i lara_meshtexture_texels(i*4 p*5 s)
-i lara_meshtexture_texels_host(i*4 p*5)
-i lara_meshtexture_bake(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3 s)
-i lara_meshtexture_bake_host(i*4 p*5 i*3 p*5 f f i*3 p f*3 p*3)
-i lara_meshtexture_sample(i*3 l p*3 i f*3 p s)
-i lara_meshtexture_sample_host(i*3 l p*3 i f*3 p)
-"""
-
 _SIGS = _parse_signatures(SIGNATURES)
-_SIGS_MESHRENDER = _parse_signatures(MESHRENDER_SIGNATURES)
-_SIGS_MESHMETRICS = _parse_signatures(MESHMETRICS_SIGNATURES)
-_SIGS_MESHSIMPLIFY = _parse_signatures(MESHSIMPLIFY_SIGNATURES)
-_SIGS_DEPTHSURFACE = _parse_signatures(DEPTHSURFACE_SIGNATURES)
-_SIGS_MESHIO = _parse_signatures(MESHIO_SIGNATURES)
-_SIGS_MESHDIST = _parse_signatures(MESHDIST_SIGNATURES)
-_SIGS_MESHALIGN = _parse_signatures(MESHALIGN_SIGNATURES)
-_SIGS_MESHBVH = _parse_signatures(MESHBVH_SIGNATURES)
-_SIGS_MESHRAY = _parse_signatures(MESHRAY_SIGNATURES)
-_SIGS_MESHSIGN = _parse_signatures(MESHSIGN_SIGNATURES)
-_SIGS_MESHTOPO = _parse_signatures(MESHTOPO_SIGNATURES)
-_SIGS_MESHWIND = _parse_signatures(MESHWIND_SIGNATURES)
-_SIGS_MESHTEXTURE = _parse_signatures(MESHTEXTURE_SIGNATURES)
-_ALL_SIGS = {**_SIGS, **_SIGS_MESHRENDER, **_SIGS_MESHMETRICS, **_SIGS_MESHSIMPLIFY, **_SIGS_DEPTHSURFACE, **_SIGS_MESHIO,
-             **_SIGS_MESHDIST, **_SIGS_MESHALIGN, **_SIGS_MESHBVH, **_SIGS_MESHRAY, **_SIGS_MESHSIGN, **_SIGS_MESHTOPO,
-             **_SIGS_MESHWIND, **_SIGS_MESHTEXTURE}
 _handle = None          # the loaded library ...
 _handle_path = None     # ... and the path it was loaded from
 
@@ -383,7 +326,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C lara_amd/csrc`. "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    for name, (restype, argtypes, _) in _ALL_SIGS.items():
+    for name, (restype, argtypes, _) in _SIGS.items():
         fn = getattr(lib, name)         # (a row without a symbol behind it fails here, not at the first call)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.lara2dgs_abi_version() != ABI_VERSION:
@@ -409,7 +352,7 @@ def call(name: str, device, *args):
     None as NULL; ints (raw addresses among them), floats, struct instances and host arrays go as they are; the device's
     current stream is appended where the prototype ends in ``void *stream``.  Nothing is copied, cast or made contiguous."""
     lib = load_library()
-    _, argtypes, has_stream = _ALL_SIGS[name]
+    _, argtypes, has_stream = _SIGS[name]
     with torch.cuda.device(device) if device is not None else contextlib.nullcontext():
         a = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
         if has_stream:
@@ -424,8 +367,8 @@ def call(name: str, device, *args):
 def query(name: str, *args, error=None) -> int:
     """A ``*_bytes`` / ``*_floats`` / ``*_blocks`` / ``*_rows`` query (host code).  A negative answer raises like a failed
     call, or raises ``error`` where the caller has a better message for sizes the library refuses."""
-    if len(args) != len(_ALL_SIGS[name][1]):
-        raise TypeError(f"lara_amd: {name} takes {len(_ALL_SIGS[name][1])} arguments, got {len(args)}")
+    if len(args) != len(_SIGS[name][1]):
+        raise TypeError(f"lara_amd: {name} takes {len(_SIGS[name][1])} arguments, got {len(args)}")
     n = int(getattr(load_library(), name)(*args))
     if n < 0:
         if error is not None:

@@ -1,6 +1,6 @@
 // boxbound.h -- the margined lower bound of the squared distance from a point to an axis-aligned box, one function for the device
 // and the host (meshbvh.hip's query kernel and lara_meshbvh_box_bound_host).  fp32 inputs, every operation in double, in the order
-// written here and stated in include/meshbvh/lara_meshbvh.h, where the margin is derived; the unit is built with -ffp-contract=off.
+// written here and stated in include/lara_meshbvh.h, where the margin is derived; the unit is built with -ffp-contract=off.
 // The result never exceeds the d2 lara_tridist (tridist.h) computes for a triangle with its vertices in the box.
 #pragma once
 

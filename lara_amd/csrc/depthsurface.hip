@@ -1,6 +1,6 @@
 // depthsurface.hip -- a ground-truth surface from depth maps on gfx950: ordered back-projection of the valid pixels, thinning to one
 // point per occupied voxel, the per-view observation test, and the masked reduction of one direction's distances.  Interface,
-// formulas and the order contract in include/depthsurface/lara_depthsurface.h.
+// formulas and the order contract in include/lara_depthsurface.h.
 //
 //   ds_count_kernel / ds_offsets_kernel / ds_emit_kernel   the ordered compaction, generic over "is item g selected" and "write item g
 //                                                          at rank r": 1024 consecutive items per workgroup in four coalesced passes,
@@ -16,7 +16,7 @@
 #include "common.h"
 #include "wave.h"
 #include "rowsum.h"
-#include "../../include/depthsurface/lara_depthsurface.h"
+#include "../../include/lara_depthsurface.h"
 
 #include <cmath>
 

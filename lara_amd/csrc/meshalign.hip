@@ -1,6 +1,6 @@
 // meshalign.hip -- the device side of ICP on gfx950: the transform of a point set by a 3x4 similarity and the one-pass reduction
 // of N correspondences to the 48-double row the host solves one iteration from.  Interface, the sequences and the summation order
-// in include/meshalign/lara_meshalign.h.
+// in include/lara_meshalign.h.
 //
 //   ma_transform_kernel     one thread per row: points and (optionally) normals, in double, one rounding to fp32
 //   ma_accumulate_kernel    one pair per lane; every one of the 46 sums is butterflied as soon as its term exists, so a lane never
@@ -11,7 +11,7 @@
 #include "common.h"
 #include "wave.h"
 #include "rowsum.h"
-#include "../../include/meshalign/lara_meshalign.h"
+#include "../../include/lara_meshalign.h"
 
 #include <cmath>
 

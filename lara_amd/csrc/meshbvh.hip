@@ -1,6 +1,6 @@
 // meshbvh.hip -- exact point-to-triangle distances at any distance on gfx950: a bounding-volume hierarchy over a mesh's triangles,
 // Morton-sorted records under an implicit complete 8-ary tree of boxes, and a stackless walk that prunes with the margined bound of
-// boxbound.h.  Interface, the key and box rules, the margin and the tie rule in include/meshbvh/lara_meshbvh.h; the distance is
+// boxbound.h.  Interface, the key and box rules, the margin and the tie rule in include/lara_meshbvh.h; the distance is
 // tridist.h's, and the validity rule, the record, the tie rule and the result write are trimesh.h's, the functions meshdist.hip runs,
 // so the two searches return the same bits.
 //

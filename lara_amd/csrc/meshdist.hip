@@ -1,6 +1,6 @@
 // meshdist.hip -- exact point-to-triangle distances on gfx950: a uniform grid over a mesh's triangles, the ring search of
 // meshmetrics.hip carried over from points to triangles, and a brute-force kernel for the queries the rings do not settle.
-// Interface, the grid rule, the cover argument and the tie rule in include/meshdist/lara_meshdist.h; the distance itself in tridist.h;
+// Interface, the grid rule, the cover argument and the tie rule in include/lara_meshdist.h; the distance itself in tridist.h;
 // the record, the validity rule, the box reduction, the candidate and the result write in trimesh.h, shared with meshbvh.hip.
 //
 //   md_pack_kernel                          48-byte records {p0, p1, p2, id or -1}; the box of the valid triangles; the bad count
@@ -16,7 +16,7 @@
 #include "common.h"
 #include "unigrid.h"
 #include "tridist.h"
-#include "../../include/meshdist/lara_meshdist.h"
+#include "../../include/lara_meshdist.h"
 
 #include <cmath>
 

@@ -1,5 +1,5 @@
 // meshio.hip -- the extracted mesh as file bytes on gfx950: OBJ text and binary PLY rows.  Interface, the text's definition and the
-// limits in include/meshio/lara_meshio.h; the number formatting (exact "%.9g", integer arithmetic) in fmt9g.h.
+// limits in include/lara_meshio.h; the number formatting (exact "%.9g", integer arithmetic) in fmt9g.h.
 //
 //   mio_obj_lengths_kernel<FACE>   one thread per line, 256 lines per workgroup: the line's tokens are decomposed only for their
 //                                  lengths, the workgroup adds them up and stores one int64 total
@@ -13,7 +13,7 @@
 #include "common.h"
 #include "wave.h"
 #include "fmt9g.h"
-#include "../../include/meshio/lara_meshio.h"
+#include "../../include/lara_meshio.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // meshmetrics.hip -- geometry scores between two surfaces on gfx950: surface sampling, exact nearest neighbours over a uniform
 // grid, and the reduction behind Chamfer / F-score / normal consistency.  Interface, formulas, the termination rule and its margin
-// in include/meshmetrics/lara_meshmetrics.h.
+// in include/lara_meshmetrics.h.
 //
 //   mm_area_kernel / mm_area_total_kernel   double triangle areas; their fixed-order sum and the bad-index count (one workgroup)
 //   mm_quantise_kernel                      q = floor(area 2^s)
@@ -17,7 +17,7 @@
 #include "common.h"
 #include "unigrid.h"
 #include "rowsum.h"
-#include "../../include/meshmetrics/lara_meshmetrics.h"
+#include "../../include/lara_meshmetrics.h"
 
 #include <cmath>
 

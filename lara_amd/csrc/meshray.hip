@@ -1,7 +1,7 @@
 // meshray.hip -- ray queries on the triangle hierarchy of meshbvh.hip on gfx950: the first triangle a ray meets, whether it meets
 // any, and which of E eyes see a point.  A second walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records:
 // trimesh.h), with the ray-triangle function of raytri.h per record and the margined entry parameter of raybox.h per
-// box.  Interface, the function, the bound's derivation and the tie rule in include/meshray/lara_meshray.h.
+// box.  Interface, the function, the bound's derivation and the tie rule in include/lara_meshray.h.
 //
 //   mr_cast_kernel<MASKED>        one thread per ray: the walk, then t, face and the barycentrics of the best record
 //   mr_occluded_kernel            one thread per ray: the same walk, ended by the first accepted triangle
@@ -12,7 +12,7 @@
 #include "raytri.h"
 #include "raybox.h"
 #include "meshbvh_layout.h"
-#include "../../include/meshray/lara_meshray.h"
+#include "../../include/lara_meshray.h"
 
 #include <cmath>
 

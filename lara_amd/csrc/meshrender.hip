@@ -1,6 +1,6 @@
 // meshrender.hip -- z-buffer triangle rasteriser for the extracted mesh's turntable on gfx950: ~0.5 M marching-cubes triangles of
 // one to four pixels each per 512 x 512 view.  Interface, layouts, the fill rule and every formula in
-// include/meshrender/lara_meshrender.h.
+// include/lara_meshrender.h.
 //
 //   mr_fill_kernel     keys <- all ones, info / list counters <- 0
 //   mr_snap_kernel     stage V: one thread per (view, vertex) -> {snapped x, y, view z}
@@ -13,7 +13,7 @@
 // instructions.
 #include "common.h"
 #include "wave.h"
-#include "../../include/meshrender/lara_meshrender.h"
+#include "../../include/lara_meshrender.h"
 
 namespace {
 

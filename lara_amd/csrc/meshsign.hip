@@ -2,7 +2,7 @@
 // rays per point counted with their orientation, the vote over them with the signed distance, the lattice counts of a volume IoU,
 // and the mesh's signed volume.  A third walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records: trimesh.h),
 // with the crossing of raycross.h per record and the margined entry parameter of raybox.h per box; the walk's step is bvhwalk.h's.
-// Interface, the rules and the orders of summation in include/meshsign/lara_meshsign.h.
+// Interface, the rules and the orders of summation in include/lara_meshsign.h.
 //
 //   ms_rows_kernel       one thread per (point, ray), blockIdx.y = ray: the walk without a best-so-far, every accepted record counted
 //   ms_vote_kernel       one thread per point: the vote, the status bits, the sign on the distance
@@ -17,7 +17,7 @@
 #include "bvhwalk.h"
 #include "meshbvh_layout.h"
 #include "rowsum.h"
-#include "../../include/meshsign/lara_meshsign.h"
+#include "../../include/lara_meshsign.h"
 
 #include <cmath>
 

@@ -1,10 +1,10 @@
-// meshsimplify.hip -- vertex-clustering simplification of a triangle mesh (include/meshsimplify/lara_meshsimplify.h): cells and
+// meshsimplify.hip -- vertex-clustering simplification of a triangle mesh (include/lara_meshsimplify.h): cells and
 // clusters through a hash table, triangle survival through a second one, per-cluster buckets in ascending order, fixed-order
 // double sums per cluster (a wave each), a closed-form Cholesky solve.  Integer atomics only; every loop bounded; built with -ffp-contract=off.
 #include "common.h"
 #include "launch.h"
 #include "wave.h"
-#include "../../include/meshsimplify/lara_meshsimplify.h"
+#include "../../include/lara_meshsimplify.h"
 
 namespace {
 

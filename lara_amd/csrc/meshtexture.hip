@@ -2,7 +2,7 @@
 // closed-form atlas, the blend of the views that see it, and bilinear reads of the result.  The three per-element functions live in
 // texatlas.h, one definition for the device and the host; the kernels here and the *_host entries below run them over the texels
 // or samples.  Visibility is meshray.hip's walk, called from python between the first two kernels.  Interface, the layout and the
-// orders of operations in include/meshtexture/lara_meshtexture.h.
+// orders of operations in include/lara_meshtexture.h.
 //
 //   mt_texels_kernel     one thread per texel: owner, point, anchor
 //   mt_bake_kernel       one thread per texel: the views in index order
@@ -10,7 +10,7 @@
 // No LDS, no atomics: two calls give the same bits.  Built with -ffp-contract=off.
 #include "common.h"
 #include "texatlas.h"
-#include "../../include/meshtexture/lara_meshtexture.h"
+#include "../../include/lara_meshtexture.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // meshtopo.hip -- the connectivity of a triangle mesh on gfx950: half-edge keys, the rows of the unique edges, the report, the two
 // CSR adjacency tables, vertex normals and the smoothing pass.  The sorts between the stages are the caller's.  Interface, the
-// definitions and the orders of summation in include/meshtopo/lara_meshtopo.h; the two per-vertex functions in meshtopo_ops.h.
+// definitions and the orders of summation in include/lara_meshtopo.h; the two per-vertex functions in meshtopo_ops.h.
 //
 //   mt_keys_kernel          one thread per triangle: the three undirected edge keys, or the sentinel; bit 0 of err
 //   mt_corner_keys_kernel   one thread per triangle: the three (vertex, half-edge) keys, or the sentinel
@@ -16,7 +16,7 @@
 #include "common.h"
 #include "wave.h"
 #include "meshtopo_ops.h"
-#include "../../include/meshtopo/lara_meshtopo.h"
+#include "../../include/lara_meshtopo.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// meshtopo_ops.h -- the two per-vertex functions of include/meshtopo/lara_meshtopo.h, one definition for the device and the host
+// meshtopo_ops.h -- the two per-vertex functions of include/lara_meshtopo.h, one definition for the device and the host
 // (meshtopo.hip's kernels, lara_meshtopo_normals_host, lara_meshtopo_smooth_host, tools/meshtopo_hostcheck.cpp): the normal of a
 // vertex over its row of the face table and the smoothing step of a vertex over its row of the neighbour table.  Double arithmetic
 // on the fp32 inputs, one rounding to fp32 at the end; the rows are walked from their first entry to their last, and that order is

@@ -2,7 +2,7 @@
 // moments in a buffer of their own, a walk that sums the exact term of solidangle.h near the point and a node's dipole term far
 // from it, and the classification of the sums (the two host entries: meshwind_host.h).  A fourth walk over the buffer
 // lara_meshbvh_build wrote (meshbvh_layout.h; its records: trimesh.h), and the first that needs per-node data beyond boxes; the
-// walk's step is bvhwalk.h's.  Interface, the rules and the orders of summation in include/meshwind/lara_meshwind.h.
+// walk's step is bvhwalk.h's.  Interface, the rules and the orders of summation in include/lara_meshwind.h.
 //
 //   mw_leaf_kernel       one thread per stored slot of level 0: the sums over its up-to-8 valid records, in stored order
 //   mw_level_kernel      one thread per stored slot of level k: the sums over its 8 children, in slot order; one launch a level
@@ -15,7 +15,7 @@
 #include "meshbvh_layout.h"
 #include "solidangle.h"
 #include "meshwind_host.h"
-#include "../../include/meshwind/lara_meshwind.h"
+#include "../../include/lara_meshwind.h"
 
 #include <cmath>
 

@@ -1,4 +1,4 @@
-// meshwind_host.h -- the two host entries of include/meshwind/lara_meshwind.h as plain C++ on solidangle.h: meshwind.hip's
+// meshwind_host.h -- the two host entries of include/lara_meshwind.h as plain C++ on solidangle.h: meshwind.hip's
 // lara_meshwind_solid_host and lara_meshwind_brute_host are these loops behind their argument checks, and
 // tools/meshwind_hostcheck.cpp builds the same loops into a stand-alone program.  No device is touched.
 #pragma once

@@ -1,6 +1,6 @@
 // raybox.h -- the margined entry parameter of a ray into an axis-aligned box, one function for the device and the host
 // (meshray.hip's walk and lara_meshray_box_entry_host).  fp32 box, the ray as lara_ray_setup (raytri.h) left it, every operation in
-// double, in the order written here and stated in include/meshray/lara_meshray.h, where the margins are derived; the unit is built
+// double, in the order written here and stated in include/lara_meshray.h, where the margins are derived; the unit is built
 // with -ffp-contract=off.  Whenever lara_raytri computes a hit at t for a triangle with its vertices in the box, the result is
 // finite and <= t.
 #pragma once

@@ -1,7 +1,7 @@
 // raycross.h -- one crossing of a ray through a triangle, with its orientation: one function for the device and the host
 // (meshsign.hip's counting walk, lara_meshsign_cross_host, tools/meshsign_hostcheck.cpp).  It accepts exactly when lara_raytri
 // (raytri.h) accepts in the window [0, +inf), and computes U, V, W again through lara_raytri_shear in raytri.h's order: under
-// -ffp-contract=off the same sequence gives the same bits.  Stated in include/meshsign/lara_meshsign.h.
+// -ffp-contract=off the same sequence gives the same bits.  Stated in include/lara_meshsign.h.
 #pragma once
 
 #include "raytri.h"

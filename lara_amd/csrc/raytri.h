@@ -1,6 +1,6 @@
 // raytri.h -- does a ray meet a triangle, and where: one function for the device and the host (meshray.hip's kernels and
 // lara_meshray_raytri_host).  fp32 inputs, every operation in double, in the order written here and stated in
-// include/meshray/lara_meshray.h; the unit is built with -ffp-contract=off, so this sequence is the instruction sequence.
+// include/lara_meshray.h; the unit is built with -ffp-contract=off, so this sequence is the instruction sequence.
 // The ray is sheared so that it runs along +z, once per ray (lara_ray_setup); a vertex's sheared position depends on the ray and
 // the vertex alone, so every triangle around an edge or a vertex classifies the ray against the same computed points, and the
 // edge functions U, V, W -- one product pair and one subtraction each, monotone under rounding -- never give two neighbours

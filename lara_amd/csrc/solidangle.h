@@ -1,7 +1,7 @@
 // solidangle.h -- the signed solid angle of one triangle seen from a point (Van Oosterom and Strackee): one function for the device
 // and the host (meshwind.hip's walk, lara_meshwind_solid_host, lara_meshwind_brute_host, tools/meshwind_hostcheck.cpp).  All
 // arithmetic is double on the fp32 inputs, in the order written here; under -ffp-contract=off the sequence is the instructions, and
-// atan2 is the only operation that is not correctly rounded.  Stated in include/meshwind/lara_meshwind.h.
+// atan2 is the only operation that is not correctly rounded.  Stated in include/lara_meshwind.h.
 #pragma once
 
 #include <cmath>

@@ -1,4 +1,4 @@
-// texatlas.h -- the closed-form texture atlas of include/meshtexture/lara_meshtexture.h and its three per-element functions, one
+// texatlas.h -- the closed-form texture atlas of include/lara_meshtexture.h and its three per-element functions, one
 // definition for the device and the host (meshtexture.hip's kernels, the lara_meshtexture_*_host entries,
 // tools/meshtexture_hostcheck.cpp): the owner of a texel, a texel's surface point and anchor, a texel's baked colour over the views,
 // and a bilinear read of the atlas at (face, barycentrics).  Integer arithmetic for the layout; double arithmetic on the fp32 inputs

@@ -1,6 +1,6 @@
 // tridist.h -- the squared distance from a point to a triangle and the closest point, one function for the device and the host
 // (meshdist.hip's kernels and lara_meshdist_point_triangle_host).  fp32 inputs, every operation in double, in the order written
-// here and stated in include/meshdist/lara_meshdist.h; the unit is built with -ffp-contract=off, so this sequence is the
+// here and stated in include/lara_meshdist.h; the unit is built with -ffp-contract=off, so this sequence is the
 // instruction sequence.  With finite fp32 inputs no intermediate leaves double's range (|n . n| < 2^520) and the result is finite.
 #pragma once
 

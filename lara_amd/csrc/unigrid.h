@@ -1,7 +1,7 @@
 // unigrid.h -- what the two uniform-grid searches share (meshmetrics.hip: nearest point; meshdist.hip: nearest triangle): the grid
 // record and the wave that derives it from a bounding box, the cell rule, the Chebyshev ring walk with its bound (mm_rings), the
 // resolution rule and the three-launch inclusive scan.  The box reduction and the candidate are trimesh.h's.  The rules are stated
-// in include/meshmetrics/lara_meshmetrics.h.  Everything sits in an unnamed namespace: each unit that includes this header owns
+// in include/lara_meshmetrics.h.  Everything sits in an unnamed namespace: each unit that includes this header owns
 // its copies.  Include it from units built with -ffp-contract=off only.
 #pragma once
 #include "common.h"

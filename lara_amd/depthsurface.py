@@ -1,4 +1,4 @@
-"""Geometry scores of an extracted mesh against ground-truth DEPTH MAPS on the device (include/depthsurface/lara_depthsurface.h,
+"""Geometry scores of an extracted mesh against ground-truth DEPTH MAPS on the device (include/lara_depthsurface.h,
 csrc/depthsurface.hip); opt-in like every module here.  LaRa's evaluation sets ship no ground-truth surface, only ``tar_dep`` /
 ``tar_msk`` / ``tar_ixt`` / ``tar_c2w`` (GSO) and ``tar_nrm`` (gobjaverse); this module makes the surface and scores against it:
 
@@ -25,7 +25,7 @@ import torch
 from . import meshmetrics
 from ._native import StreamWorkspace, call, host_array, query, require_device, rows3
 
-MAX_VIEWS, MAX_CELLS, MAX_THRESHOLDS, ROW = 64, 1 << 27, 8, 13      # include/depthsurface/lara_depthsurface.h
+MAX_VIEWS, MAX_CELLS, MAX_THRESHOLDS, ROW = 64, 1 << 27, 8, 13      # include/lara_depthsurface.h
 NORMALS_NONE, NORMALS_GIVEN, NORMALS_DEPTH = 0, 1, 2
 
 _workspace = StreamWorkspace()      # its own: ``meshmetrics.nearest`` runs while a call here holds it

@@ -1,4 +1,4 @@
-"""Rigid and similarity alignment (ICP) of two surfaces before they are scored (include/meshalign/lara_meshalign.h,
+"""Rigid and similarity alignment (ICP) of two surfaces before they are scored (include/lara_meshalign.h,
 csrc/meshalign.hip); opt-in like every module here.
 
   * ``transform_points``  a 4x4 similarity applied to points (and normals) on the device, in double, one rounding to fp32;
@@ -25,7 +25,7 @@ import torch
 from . import meshmetrics
 from ._native import call, host_array, query, require_device, rows3
 
-ROW = 48                                # include/meshalign/lara_meshalign.h
+ROW = 48                                # include/lara_meshalign.h
 _PCA_SIGNS = ((1.0, 1.0, 1.0), (1.0, -1.0, -1.0), (-1.0, 1.0, -1.0), (-1.0, -1.0, 1.0))      # the four proper axis flips, in candidate order
 
 

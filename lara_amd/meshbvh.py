@@ -1,5 +1,5 @@
 """Exact point-to-triangle distances at any distance from the mesh: a bounding-volume hierarchy over the triangles, the second
-search structure next to ``meshdist.TriangleGrid`` (include/meshbvh/lara_meshbvh.h, csrc/meshbvh.hip, csrc/boxbound.h); opt-in like
+search structure next to ``meshdist.TriangleGrid`` (include/lara_meshbvh.h, csrc/meshbvh.hip, csrc/boxbound.h); opt-in like
 every module here.
 
   * ``TriangleBVH``   the triangles sorted by the Morton code of their box centres (the sort itself is ``torch.sort`` between two
@@ -20,7 +20,7 @@ import torch
 from ._native import call, host_array
 from .meshdist import _TriangleSearch
 
-MAX_LEVELS = 9                                                  # include/meshbvh/lara_meshbvh.h
+MAX_LEVELS = 9                                                  # include/lara_meshbvh.h
 HEADER_INTS, HDR_BAD, HDR_VALID, HDR_TRIANGLES, HDR_LEVELS = 4, 0, 1, 2, 3
 
 

@@ -1,4 +1,4 @@
-"""Exact point-to-triangle distances on the device, and the geometry scores measured with them (include/meshdist/lara_meshdist.h,
+"""Exact point-to-triangle distances on the device, and the geometry scores measured with them (include/lara_meshdist.h,
 csrc/meshdist.hip, csrc/tridist.h); opt-in like every module here.
 
   * ``TriangleGrid``    a uniform grid over a mesh's triangles, built once: every triangle is registered in the cells its bounding
@@ -22,7 +22,7 @@ import torch
 from . import meshmetrics
 from ._native import alloc_bytes, call, host_array, query, require_device, rows3
 
-RMAX, MAX_SPAN, MAX_GRID = 4, 4, 256                           # include/meshdist/lara_meshdist.h
+RMAX, MAX_SPAN, MAX_GRID = 4, 4, 256                           # include/lara_meshdist.h
 HEADER_INTS, HDR_BAD, HDR_LARGE, HDR_PAIRS, HDR_TRIANGLES = 4, 0, 1, 2, 3
 
 

@@ -1,4 +1,4 @@
-"""The extracted mesh as a file, serialised on the device (include/meshio/lara_meshio.h, csrc/meshio.hip, csrc/fmt9g.h); opt-in like
+"""The extracted mesh as a file, serialised on the device (include/lara_meshio.h, csrc/meshio.hip, csrc/fmt9g.h); opt-in like
 every module here.  ``mesh.write_obj`` copies the mesh to the host and formats ~850 k lines with numpy string operations; here the
 text is built by kernels and the host only copies and writes it:
 
@@ -23,7 +23,7 @@ import torch
 from . import mesh
 from ._native import StreamWorkspace, call, query, require_device
 
-BLOCK_LINES, MAX_F32_TOKEN, MAX_U32_TOKEN, MAX_VERTEX_LINE, MAX_FACE_LINE = 256, 15, 10, 98, 35     # include/meshio/lara_meshio.h
+BLOCK_LINES, MAX_F32_TOKEN, MAX_U32_TOKEN, MAX_VERTEX_LINE, MAX_FACE_LINE = 256, 15, 10, 98, 35     # include/lara_meshio.h
 PLY_FACE_ROW, MAX_VERTICES, MAX_TRIANGLES, MAX_INDEX = 13, 2 ** 31 - 1, (2 ** 31 - 1) // 3, 2 ** 31 - 2
 FORMATS = ("obj", "ply")
 

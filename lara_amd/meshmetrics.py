@@ -1,5 +1,5 @@
 """Geometry scores between an extracted mesh and a ground-truth surface on the device: accuracy, completeness, Chamfer distance,
-precision / recall / F-score at distance thresholds and normal consistency (include/meshmetrics/lara_meshmetrics.h,
+precision / recall / F-score at distance thresholds and normal consistency (include/lara_meshmetrics.h,
 csrc/meshmetrics.hip); opt-in like every module here.
 
   * ``sample_surface``  n points on a triangle mesh: area-weighted (integer-quantised areas, an exact prefix sum), stratified
@@ -22,7 +22,7 @@ import torch
 
 from ._native import StreamWorkspace, call, host_array, query, require_device
 
-MAX_SAMPLES, RMAX, MAX_GRID, MAX_THRESHOLDS, ROW = 1 << 22, 4, 256, 8, 12      # include/meshmetrics/lara_meshmetrics.h
+MAX_SAMPLES, RMAX, MAX_GRID, MAX_THRESHOLDS, ROW = 1 << 22, 4, 256, 8, 12      # include/lara_meshmetrics.h
 THRESHOLDS = (0.005, 0.01, 0.02)      # in the units of the meshes; LaRa's scenes live in [-1, 1]^3 or smaller boxes
 
 _workspace = StreamWorkspace()      # (meshdist and meshalign take theirs from here too)

@@ -1,5 +1,5 @@
 """Ray queries on a mesh's triangles on the device: the first triangle a ray meets, whether it meets any, which eyes see a point
-past the mesh, and depth maps of the mesh (include/meshray/lara_meshray.h, csrc/meshray.hip, csrc/raytri.h, csrc/raybox.h); opt-in
+past the mesh, and depth maps of the mesh (include/lara_meshray.h, csrc/meshray.hip, csrc/raytri.h, csrc/raybox.h); opt-in
 like every module here.  Every function takes a built ``meshbvh.TriangleBVH`` and walks the buffer it holds; nothing is added to it.
 
   * ``raycast``       per ray the smallest t with o + t d on a triangle, inside [t_min, t_max], and that triangle (an exact tie: the
@@ -23,7 +23,7 @@ import torch
 
 from ._native import call, rows3
 
-MAX_EYES = 64                                                    # include/meshray/lara_meshray.h
+MAX_EYES = 64                                                    # include/lara_meshray.h
 MASKED_ORDER = 1
 
 

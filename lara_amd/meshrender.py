@@ -1,5 +1,5 @@
 """The mesh turntable of LaRa's evaluation loop (evaluation.py:150-155, tools/meshRender.py) on the device: a deterministic
-z-buffer triangle rasteriser (include/meshrender/lara_meshrender.h, csrc/meshrender.hip); opt-in like every module here.
+z-buffer triangle rasteriser (include/lara_meshrender.h, csrc/meshrender.hip); opt-in like every module here.
 
 The reference hands the mesh to Mitsuba (rough plastic under an HDR environment, 512 path-traced samples per pixel and frame).
 Mitsuba is not available and its image is not imitated.  What a user of ``lara_amd.mesh.MeshExtractor`` gets here is the mesh
@@ -24,13 +24,13 @@ ALBEDO = (0.25, 0.5, 0.8)               # configs/render/scene.xml: the bsdf's d
 BACKGROUND = (0.722, 0.376, 0.161)      # tools/meshRender.py:44
 AMBIENT, DIFFUSE = 0.25, 0.75
 OUTPUTS = ("face_id", "depth", "normal", "frames", "info")
-SUBPIXEL, RANGE, FAR = 256, 1 << 22, 1 << 30      # include/meshrender/lara_meshrender.h
+SUBPIXEL, RANGE, FAR = 256, 1 << 22, 1 << 30      # include/lara_meshrender.h
 
 _workspace = StreamWorkspace()      # its own: sections of it stay alive across calls
 
 
 def section_offsets(n_views, H, W, Nv, T):
-    """Byte offsets of the workspace's (SNAP, KEYS, LIST, COUNT) sections (include/meshrender/lara_meshrender.h)."""
+    """Byte offsets of the workspace's (SNAP, KEYS, LIST, COUNT) sections (include/lara_meshrender.h)."""
     offs = host_array("l", 4)
     call("lara_meshrender_section_offsets", None, n_views, H, W, Nv, T, offs)
     return tuple(offs)

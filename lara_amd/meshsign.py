@@ -1,5 +1,5 @@
 """Is a point inside a mesh, on the device: crossings of fixed rays counted on a mesh's triangle hierarchy, the vote over them, signed
-distances, and the volumetric IoU of two meshes (include/meshsign/lara_meshsign.h, csrc/meshsign.hip, csrc/raycross.h,
+distances, and the volumetric IoU of two meshes (include/lara_meshsign.h, csrc/meshsign.hip, csrc/raycross.h,
 csrc/bvhwalk.h); opt-in like every module here.  Every function takes a built ``meshbvh.TriangleBVH`` and walks the buffer it
 holds; nothing is added to it.
 
@@ -28,7 +28,7 @@ import torch
 
 from ._native import call, rows3
 
-MAX_RAYS = 3                                                     # include/meshsign/lara_meshsign.h
+MAX_RAYS = 3                                                     # include/lara_meshsign.h
 RULES = {"parity": 0, "winding": 1}
 DIRECTIONS = ((1.0, 0.375, 0.6875), (-0.4375, 1.0, 0.3125), (0.5625, -0.3125, -1.0))
 STATUS_DISAGREE, STATUS_UNUSABLE, STATUS_NONE = 1, 2, 4

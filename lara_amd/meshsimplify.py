@@ -1,4 +1,4 @@
-"""Simplify a triangle mesh on the device by vertex clustering (include/meshsimplify/lara_meshsimplify.h,
+"""Simplify a triangle mesh on the device by vertex clustering (include/lara_meshsimplify.h,
 csrc/meshsimplify.hip); opt-in like every module here.  The last stage of the mesh path: it reads (vertices, triangles, colors)
 as ``lara_amd.mesh.clean_mesh`` returns them and returns the same triple.
 
@@ -19,7 +19,7 @@ import torch
 from ._native import alloc_bytes, call, query, require_device
 from .mesh import _compact
 
-ERR_INDEX, ERR_PROBE, ERR_NONFINITE, ERR_NEGATIVE, ERR_EXTENT = 1, 2, 4, 8, 16      # include/meshsimplify/lara_meshsimplify.h
+ERR_INDEX, ERR_PROBE, ERR_NONFINITE, ERR_NEGATIVE, ERR_EXTENT = 1, 2, 4, 8, 16      # include/lara_meshsimplify.h
 MAX_CELL = 1 << 21
 N_DEGENERATE, N_DUPLICATE, N_ZERO_AREA, N_CLAMPED, COUNTERS = 0, 1, 2, 3, 4
 CONTRACTIONS = ("average", "quadric")

@@ -1,5 +1,5 @@
 """A texture atlas for a mesh, baked on the device from the views that were rendered to build it
-(include/meshtexture/lara_meshtexture.h, csrc/meshtexture.hip, csrc/texatlas.h); opt-in like every module here.  Per-vertex colours
+(include/lara_meshtexture.h, csrc/meshtexture.hip, csrc/texatlas.h); opt-in like every module here.  Per-vertex colours
 carry a voxel's worth of appearance per vertex; once ``meshsimplify`` has run, a triangle spans many voxels and the surface between
 its vertices is a blend of three colours.  The rendered views still hold the appearance at image resolution: this module writes it
 into an atlas the simplified mesh carries along.
@@ -35,7 +35,7 @@ import torch
 
 from ._native import call, host_array, require_device
 
-MIN_PATCH, MAX_PATCH, MAX_VIEWS, MAX_POWER = 3, 4096, 64, 8      # include/meshtexture/lara_meshtexture.h
+MIN_PATCH, MAX_PATCH, MAX_VIEWS, MAX_POWER = 3, 4096, 64, 8      # include/lara_meshtexture.h
 MAX_TEXELS = 1 << 30
 DEFAULT_PATCH = 8
 BLENDS = {"weighted": 0, "best": 1}

@@ -1,4 +1,4 @@
-"""The connectivity of a triangle mesh on the device: which triangles share an edge (include/meshtopo/lara_meshtopo.h,
+"""The connectivity of a triangle mesh on the device: which triangles share an edge (include/lara_meshtopo.h,
 csrc/meshtopo.hip, csrc/meshtopo_ops.h); opt-in like every module here.
 
   * ``MeshTopology``      the unique undirected edges in ascending (lo, hi) with their incident faces -- ``edges`` [E,2], ``edge_n`` [E]
@@ -33,7 +33,7 @@ import torch
 
 from ._native import call, host_array, require_device, rows3
 
-SENTINEL = (1 << 63) - 1                                          # include/meshtopo/lara_meshtopo.h
+SENTINEL = (1 << 63) - 1                                          # include/lara_meshtopo.h
 REPORT_FIELDS = ("n_vertices", "n_referenced", "n_triangles", "n_valid", "n_degenerate", "n_edges", "n_boundary", "n_manifold",
                  "n_nonmanifold", "n_inconsistent", "n_boundary_vertices", "max_degree")
 CSR_NEIGHBORS, CSR_FACES = 0, 1

@@ -1,5 +1,5 @@
 """Generalised (solid-angle) winding numbers of a mesh, on the device: w(q) = (1 / 4 pi) x the sum of the signed solid angles of all
-triangles seen from q, walked over a mesh's triangle hierarchy with per-node moments (include/meshwind/lara_meshwind.h,
+triangles seen from q, walked over a mesh's triangle hierarchy with per-node moments (include/lara_meshwind.h,
 csrc/meshwind.hip, csrc/solidangle.h, csrc/bvhwalk.h); opt-in like every module here.  For an outward-oriented closed mesh w is 1
 inside and 0 outside; where the mesh has holes, open boundaries, duplicated or non-manifold parts it degrades smoothly, which the
 crossing counts of ``meshsign`` do not: this is the inside/outside for the open surfaces ``MeshExtractor`` returns.
@@ -31,7 +31,7 @@ from . import meshsign
 from ._native import alloc_bytes, call, query, require_device, rows3
 from .meshbvh import TriangleBVH
 
-SLOT_BYTES, HEADER_BYTES = 64, 256                              # include/meshwind/lara_meshwind.h
+SLOT_BYTES, HEADER_BYTES = 64, 256                              # include/lara_meshwind.h
 RULE = "solid_angle"
 STATUS_UNDECIDED, STATUS_NOT_FINITE = 1, 4
 

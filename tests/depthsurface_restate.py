@@ -1,4 +1,4 @@
-"""include/depthsurface/lara_depthsurface.h restated in numpy, twice: in fp32 in the written order (what the kernels must give bit
+"""include/lara_depthsurface.h restated in numpy, twice: in fp32 in the written order (what the kernels must give bit
 for bit where the header fixes every operation) and in float64 on the same fp32 inputs (the true values of the formulas), plus
 the set of (sample, view) decisions of the observation test that are AMBIGUOUS: a comparison of it, evaluated in float64, lies
 within 2^-18 relative of the magnitudes it compares, so that the fp32 evaluation may legitimately land on either side.

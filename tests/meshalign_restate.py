@@ -1,4 +1,4 @@
-"""include/meshalign/lara_meshalign.h restated in float64 (numpy, no GPU): the transform's sequence, the 48-entry row term by term
+"""include/lara_meshalign.h restated in float64 (numpy, no GPU): the transform's sequence, the 48-entry row term by term
 (with the sum of the terms' magnitudes, which the summation-order bar of tests/test_meshalign_gpu.py is made of), and the ICP loop of
 lara_amd/meshalign.py over brute-force closest triangles (tests/meshdist_restate.py).  The two host solves are the module's own
 (float64 numpy, no device): tests/test_meshalign.py holds them to known motions through this row."""

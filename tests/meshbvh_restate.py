@@ -1,4 +1,4 @@
-"""include/meshbvh/lara_meshbvh.h restated in numpy (no GPU): the keys with the fp32 cell rule, the sorted order, the records, every
+"""include/lara_meshbvh.h restated in numpy (no GPU): the keys with the fp32 cell rule, the sorted order, the records, every
 level's boxes, the margined bound in float64, and the walk itself -- seed, fixed order, strict skip rule -- on the float64 distance
 of tests/meshdist_restate.py.  tests/test_meshbvh.py holds the host entry and the pruning logic to this file;
 tests/test_meshbvh_gpu.py holds the kernels to it."""

@@ -1,4 +1,4 @@
-"""include/meshdist/lara_meshdist.h restated in float64 (numpy, no GPU): the point-to-triangle distance in the header's operation
+"""include/lara_meshdist.h restated in float64 (numpy, no GPU): the point-to-triangle distance in the header's operation
 order, an independent seven-region (Ericson) closest point, brute force over a mesh, the unit face normals, and the grid search
 itself -- cells, large list, rings, bound -- with the fp32 cell rule.  tests/test_meshdist.py holds this file to closed forms and
 the host entry to it; tests/test_meshdist_gpu.py holds the kernels to it."""

@@ -1,4 +1,4 @@
-"""numpy / Python restatements of include/meshio/lara_meshio.h: the "%.9g" token, the decimal index, the PLY file as a structured
+"""numpy / Python restatements of include/lara_meshio.h: the "%.9g" token, the decimal index, the PLY file as a structured
 array's ``tobytes()``, the colour rule in float64.  The OBJ text is not restated: its target is the file ``mesh.write_obj`` writes."""
 import numpy as np
 

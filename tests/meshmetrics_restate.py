@@ -1,4 +1,4 @@
-"""include/meshmetrics/lara_meshmetrics.h restated in float64 and exact integers (numpy, no GPU): the surface sampler, brute-force
+"""include/lara_meshmetrics.h restated in float64 and exact integers (numpy, no GPU): the surface sampler, brute-force
 nearest neighbours and the scores.  tests/test_meshmetrics.py holds this file to closed forms; tests/test_meshmetrics_gpu.py
 holds the kernels to it."""
 import math

@@ -1,4 +1,4 @@
-"""include/meshray/lara_meshray.h restated in numpy float64 (no GPU): the ray-triangle function of csrc/raytri.h in its operation
+"""include/lara_meshray.h restated in numpy float64 (no GPU): the ray-triangle function of csrc/raytri.h in its operation
 order, the unsheared triple-product form it replaces (for the teeth test), the margined entry parameter of csrc/raybox.h and an
 un-inflated slab test, brute force over all triangles, and the walk over the restated hierarchy of tests/meshbvh_restate.py with
 both sibling orders, counting triangle tests.  tests/test_meshray.py holds the host entries and the pruning logic to this file;

@@ -1,4 +1,4 @@
-"""include/meshrender/lara_meshrender.h restated in float64 and exact integers (numpy int64: every product stays below 2^47), without
+"""include/lara_meshrender.h restated in float64 and exact integers (numpy int64: every product stays below 2^47), without
 the library or a device.  The reference of tests/test_meshrender.py and tests/test_meshrender_gpu.py.
 
 ``snap_vertices`` is stage V; ``rasterize`` is stages R and S from a stage-V array (snapped x, y and view z) -- its own, or

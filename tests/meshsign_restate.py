@@ -1,4 +1,4 @@
-"""include/meshsign/lara_meshsign.h restated in numpy float64 (no GPU): the crossing of csrc/raycross.h on the restated ray-triangle
+"""include/lara_meshsign.h restated in numpy float64 (no GPU): the crossing of csrc/raycross.h on the restated ray-triangle
 function of tests/meshray_restate.py, brute force over all triangles, the counting walk over the restated hierarchy of
 tests/meshbvh_restate.py (with the un-inflated slab test on request, for the teeth test), the vote, the lattice in numpy fp32, the
 eight counts and the mesh's volume.  tests/test_meshsign.py holds the host entries and the pruning logic to this file;

@@ -1,4 +1,4 @@
-"""numpy restatement of include/meshsimplify/lara_meshsimplify.h as lara_amd.meshsimplify composes it: fp32 cell arithmetic, fp64
+"""numpy restatement of include/lara_meshsimplify.h as lara_amd.meshsimplify composes it: fp32 cell arithmetic, fp64
 everything else, integer triangle rules.  The authority the kernels are held to (tests/test_meshsimplify_gpu.py) and that
 tests/test_meshsimplify.py holds to closed forms.  No GPU, no library."""
 import math

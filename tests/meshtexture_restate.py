@@ -1,4 +1,4 @@
-"""include/meshtexture/lara_meshtexture.h restated in numpy (int64 for the layout, float64 in the header's order for the rest):
+"""include/lara_meshtexture.h restated in numpy (int64 for the layout, float64 in the header's order for the rest):
 what tests/test_meshtexture.py holds the host entries to and tests/test_meshtexture_gpu.py the kernels, as integers and bit
 patterns.  Nothing here is shared with lara_amd/meshtexture.py."""
 import math

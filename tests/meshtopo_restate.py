@@ -1,4 +1,4 @@
-"""include/meshtopo/lara_meshtopo.h restated in numpy, int64 and float64: the validity rule, the table of unique edges, the report,
+"""include/lara_meshtopo.h restated in numpy, int64 and float64: the validity rule, the table of unique edges, the report,
 the two CSR adjacency tables, the two per-vertex functions with the header's order of operations, and the smoothing loops.  Written
 from the header, not from the kernels: unique edges come from ``np.unique`` over (lo, hi) pairs, the adjacency from ``np.lexsort``.
 The per-vertex sums run over the rank inside a row, one vector addition per rank, so every vertex adds its terms one by one in the

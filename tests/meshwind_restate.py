@@ -1,4 +1,4 @@
-"""include/meshwind/lara_meshwind.h restated in numpy float64 (no GPU): the term of csrc/solidangle.h in the header's operation order
+"""include/lara_meshwind.h restated in numpy float64 (no GPU): the term of csrc/solidangle.h in the header's operation order
 (with the `num == 0` rule, and without it on request, for the teeth test), brute force over all valid triangles, the moments over
 the restated hierarchy of tests/meshbvh_restate.py in the header's summation order, the walk with its counters -- all points in
 lockstep, each with a state of its own, so a point's sum is added in its walk's order -- and the classification.

@@ -1,5 +1,5 @@
 """The C-ABI library builds for gfx950 without a GPU, loads, and exports every symbol that
-include/lara2dgs.h declares; the Python copy of the ABI (lara_amd/_native.py) agrees with the headers, function by
+the headers under include/ declare; the Python copy of the ABI (lara_amd/_native.py) agrees with the headers, function by
 function and struct by struct.  No compute calls here (no GPU)."""
 import ctypes
 import os
@@ -34,10 +34,11 @@ def header_texts(include_dir=None):
     return texts
 
 
-def header_functions(include_dir=None):
-    """{name: (return kind, [parameter kinds])} of every prototype: return 'i' / 'l' / 'z' (const char *)."""
-    out = {}
-    for text in header_texts(include_dir).values():
+def header_functions_by_file(include_dir=None):
+    """{header file name: {name: (return kind, [parameter kinds])}} of every prototype: return 'i' / 'l' / 'z' (const char *)."""
+    by_file = {}
+    for hdr, text in header_texts(include_dir).items():
+        out = by_file[hdr] = {}
         text = re.sub(_STRUCT_RE, "", text, flags=re.S)
         text = re.sub(r"^\s*#.*$", "", text, flags=re.M).replace('extern "C" {', "")
         for stmt in text.split(";"):
@@ -51,9 +52,14 @@ def header_functions(include_dir=None):
                 for p in params.split(","):
                     d = re.match(r"(.*?)(\w+)\s*(\[[^\]]*\])?$", p.strip())
                     kinds.append(_c_kind(d.group(1) + (d.group(3) or "")))
-            assert name not in out, f"{name} is declared twice"
+            assert not any(name in fns for fns in by_file.values()), f"{name} is declared twice"
             out[name] = ("z" if "char" in ret else _c_kind(ret), kinds)
-    return out
+    return by_file
+
+
+def header_functions(include_dir=None):
+    """{name: (return kind, [parameter kinds])} over all headers."""
+    return {name: sig for fns in header_functions_by_file(include_dir).values() for name, sig in fns.items()}
 
 
 def header_structs(include_dir=None):
@@ -111,8 +117,24 @@ def table_mismatches(include_dir=None):
 def test_signature_table_equals_the_headers():
     """Every function the headers declare has a row, every row a declaration, and they agree in the return type and, position by
     position, in the kind of every parameter (pointer / int32 / int64 / float)."""
-    assert len(header_functions()) == len(_native._SIGS) == 92
-    assert table_mismatches() == []
+    assert table_mismatches() == []             # (first: it names the function, the count below only counts)
+    assert len(header_functions()) == len(_native._SIGS) == 183
+
+
+# how many functions each header declares: a function that moves between headers, or a header that appears or goes, shows here
+FUNCTIONS_PER_HEADER = {
+    "lara2dgs.h": 16, "lara_coarsedec.h": 3, "lara_depthsurface.h": 8, "lara_eval.h": 3, "lara_featvol.h": 3, "lara_finedec.h": 8,
+    "lara_groupattn.h": 20, "lara_loss.h": 6, "lara_lpips.h": 4, "lara_meshalign.h": 3, "lara_meshbvh.h": 6, "lara_meshclean.h": 6,
+    "lara_meshdist.h": 7, "lara_meshio.h": 8, "lara_meshmetrics.h": 7, "lara_meshray.h": 6, "lara_meshrender.h": 3,
+    "lara_meshsign.h": 6, "lara_meshsimplify.h": 12, "lara_meshtexture.h": 7, "lara_meshtopo.h": 12, "lara_meshwind.h": 6,
+    "lara_pointfeat.h": 7, "lara_rays.h": 1, "lara_surface.h": 6, "lara_tsdf.h": 4, "lara_vit.h": 5,
+}
+
+
+def test_each_header_declares_its_pinned_number_of_functions():
+    assert {hdr: len(fns) for hdr, fns in header_functions_by_file().items()} == FUNCTIONS_PER_HEADER
+    assert sum(FUNCTIONS_PER_HEADER.values()) == 183
+    assert [d for d in os.listdir(os.path.join(ROOT, "include")) if not d.endswith(".h")] == [], "include/ is flat"
 
 
 def test_stream_flag_follows_the_prototype():
@@ -122,7 +144,7 @@ def test_stream_flag_follows_the_prototype():
         for name, params in re.findall(r"\b(lara2dgs_\w+|lara_\w+)\s*\(([^()]*)\)\s*;", text):
             assert _native._SIGS[name][2] == bool(re.search(r"void\s*\*\s*stream\s*$", params)), name
             seen += 1
-    assert seen == 92
+    assert seen == 183
 
 
 def test_a_changed_prototype_fails_the_table_check(tmp_path):
@@ -242,7 +264,7 @@ def test_header_declares_the_three_reference_entry_points():
 
 def test_library_exports_every_declared_symbol(hip_lib):
     for name in declared_functions():
-        assert hasattr(hip_lib, name), f"{name} declared in lara2dgs.h but not exported"
+        assert hasattr(hip_lib, name), f"{name} declared in a header but not exported"
     assert hip_lib.lara2dgs_abi_version() == rasterizer.ABI_VERSION
 
 

@@ -1,4 +1,4 @@
-"""include/depthsurface/lara_depthsurface.h: the signature table held to the header, the two numpy restatements
+"""include/lara_depthsurface.h: its constants held to the module's, the two numpy restatements
 (tests/depthsurface_restate.py: fp32 in the written order, float64 true values) held to each other on every case of
 tests/depthsurface_cases.py, the cap on the ambiguous share of the observation cases, the library's refusals, and the score dict on
 its way through the Evaluator -- no GPU.  tests/test_depthsurface_gpu.py holds the kernels to the restatements.
@@ -6,45 +6,28 @@ its way through the Evaluator -- no GPU.  tests/test_depthsurface_gpu.py holds t
 Bars (u = 2^-24).  A back-projected coordinate takes two roundings for a (b), one for a d, one for each product with R and one
 for each of the three additions: first order 4 u (|R0 px| + |R1 py|) + u |R2 d| + u (|s1| + |s2| + |s3|) <= 7 u S with S the sum of
 the four magnitudes added; the bar is 8 u S.  The observation bits of the two restatements must agree outside the ambiguous set."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, depthsurface, evaluate
+from lara_amd import depthsurface, evaluate
 from tests import depthsurface_cases as C
 from tests import depthsurface_restate as R
 
-STREAMED = ("lara_depthsurface_backproject_count", "lara_depthsurface_backproject_emit", "lara_depthsurface_thin",
-            "lara_depthsurface_observe", "lara_depthsurface_reduce")
 AMBIGUOUS_CAP = 0.005
 
 
-def test_signature_table_equals_its_header():
-    """include/depthsurface/lara_depthsurface.h against `_native.DEPTHSURFACE_SIGNATURES`, with the comparison tests/test_abi_cpu.py
-    applies to the headers directly under include/: names, return types, every parameter's kind in order, the stream flag."""
+def test_header_constants_equal_the_modules():
+    """The limits and the normal modes of include/lara_depthsurface.h, as the header defines them and as the module and the
+    restatement repeat them."""
     from tests import test_abi_cpu as abi
-    declared = abi.header_functions(os.path.join(abi.ROOT, "include", "depthsurface"))
-    table = _native._SIGS_DEPTHSURFACE
-    assert sorted(declared) == sorted(table) and len(table) == 8
-    assert not set(table) & (set(_native._SIGS) | set(_native._SIGS_MESHRENDER) | set(_native._SIGS_MESHMETRICS) | set(_native._SIGS_MESHSIMPLIFY))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in STREAMED)
-    assert abi.header_structs(os.path.join(abi.ROOT, "include", "depthsurface")) == {}
     assert (depthsurface.MAX_VIEWS, depthsurface.MAX_CELLS, depthsurface.MAX_THRESHOLDS, depthsurface.ROW) == (64, 1 << 27, 8, 13)
     assert (depthsurface.NORMALS_NONE, depthsurface.NORMALS_GIVEN, depthsurface.NORMALS_DEPTH) == (0, 1, 2)
-    text = abi.header_texts(os.path.join(abi.ROOT, "include", "depthsurface"))["lara_depthsurface.h"]
+    text = abi.header_texts()["lara_depthsurface.h"]
     for macro, value in (("MAX_VIEWS", "64"), ("MAX_CELLS", "(1 << 27)"), ("MAX_THRESHOLDS", "8"), ("ROW", "13"), ("NORMALS_NONE", "0"),
                          ("NORMALS_GIVEN", "1"), ("NORMALS_DEPTH", "2")):
         assert f"#define LARA_DEPTHSURFACE_{macro} {value}\n" in text
     assert (R.MAX_CELLS, R.ROW) == (depthsurface.MAX_CELLS, depthsurface.ROW)
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_DEPTHSURFACE:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_refusals(hip_lib):

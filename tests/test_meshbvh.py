@@ -1,11 +1,10 @@
-"""include/meshbvh/lara_meshbvh.h without a GPU: the signature table held to the header, the library's refusals and its size formula;
+"""include/lara_meshbvh.h without a GPU: the header's constants held to the module's, the library's refusals and its size formula;
 the margined bound of csrc/boxbound.h, through its host entry, held under the distance csrc/tridist.h computes (the host entry of
 meshdist) on random, flat, shifted and degenerate pairs -- and an unmargined float64 bound shown to FAIL on the flat ones, so the
 cases bite; the restated walk (tests/meshbvh_restate.py) held to restated brute force on every case of tests/meshdist_cases.py;
 the ``search=`` keyword's refusals and the Evaluator hook.  tests/test_meshbvh_gpu.py holds the kernels to the same restatement.
 
 The bound's bar is the contract itself, with no tolerance: bound(q, box) <= d2(q, t) as computed, for every triangle t in the box."""
-import os
 import sys
 
 import numpy as np
@@ -21,33 +20,14 @@ from tests import meshdist_restate as R
 F32 = np.float32
 
 
-def test_signature_table_equals_its_header():
+def test_header_constants_equal_the_modules():
     from lara_amd import meshbvh
     from tests import test_abi_cpu as abi
-    inc = os.path.join(abi.ROOT, "include", "meshbvh")
-    declared = abi.header_functions(inc)
-    table = _native._SIGS_MESHBVH
-    assert sorted(declared) == sorted(table) and len(table) == 6
-    others = (_native._SIGS, _native._SIGS_MESHRENDER, _native._SIGS_MESHMETRICS, _native._SIGS_MESHSIMPLIFY,
-              _native._SIGS_DEPTHSURFACE, _native._SIGS_MESHIO, _native._SIGS_MESHDIST, _native._SIGS_MESHALIGN)
-    assert not any(set(table) & set(o) for o in others)
-    assert all(set(o) <= set(_native._ALL_SIGS) for o in others + (table,))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in ("lara_meshbvh_keys", "lara_meshbvh_build", "lara_meshbvh_query"))
-    assert abi.header_structs(inc) == {}
     assert (meshbvh.MAX_LEVELS, meshbvh.HEADER_INTS) == (9, 4) == (RB.MAX_LEVELS, 4)
     assert (meshbvh.HDR_BAD, meshbvh.HDR_VALID, meshbvh.HDR_TRIANGLES, meshbvh.HDR_LEVELS) == (0, 1, 2, 3)
-    text = abi.header_texts(inc)["lara_meshbvh.h"]
+    text = abi.header_texts()["lara_meshbvh.h"]
     for macro, value in (("MAX_LEVELS", 9), ("HEADER_INTS", 4), ("HDR_BAD", 0), ("HDR_VALID", 1), ("HDR_TRIANGLES", 2), ("HDR_LEVELS", 3)):
         assert f"#define LARA_MESHBVH_{macro} {value}\n" in text
-    # the count the headers directly under include/ declare, which tests/test_abi_cpu.py pins, did not move
-    assert not set(table) & set(abi.header_functions())
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHBVH:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_refusals_and_the_size_formula(hip_lib):

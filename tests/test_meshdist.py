@@ -1,54 +1,35 @@
-"""The float64 restatement of include/meshdist/lara_meshdist.h (tests/meshdist_restate.py) held to closed forms and to an
+"""The float64 restatement of include/lara_meshdist.h (tests/meshdist_restate.py) held to closed forms and to an
 independent seven-region routine; the host entry -- csrc/tridist.h, the function the kernels run -- held to the restatement; the
-restated grid search held to restated brute force on the cases of tests/meshdist_cases.py; the signature table held to the header,
+restated grid search held to restated brute force on the cases of tests/meshdist_cases.py; the header's constants held to the module's,
 the library's refusals, and the hooks into `meshmetrics`, `depthsurface` and the Evaluator -- no GPU.
 tests/test_meshdist_gpu.py holds the kernels to the same restatement.
 
 Bars (u = 2^-24, S = the largest coordinate magnitude of the pair): |d - d64| <= 8 u d64 + 2^-40 S.  The host entry works in double
 like the restatement, so it sits orders of magnitude inside the bar; the d2 bits are compared too and the outcome is printed."""
 import ctypes
-import os
 import sys
 
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, evaluate, meshmetrics
+from lara_amd import evaluate, meshmetrics
 from tests import meshdist_cases as C
 from tests import meshdist_restate as R
 
 F32 = np.float32
 
 
-def test_signature_table_equals_its_header():
+def test_header_constants_equal_the_modules():
     from lara_amd import meshdist
     from tests import test_abi_cpu as abi
-    inc = os.path.join(abi.ROOT, "include", "meshdist")
-    declared = abi.header_functions(inc)
-    table = _native._SIGS_MESHDIST
-    assert sorted(declared) == sorted(table) and len(table) == 7
-    others = (_native._SIGS, _native._SIGS_MESHRENDER, _native._SIGS_MESHMETRICS, _native._SIGS_MESHSIMPLIFY,
-              _native._SIGS_DEPTHSURFACE, _native._SIGS_MESHIO)
-    assert not any(set(table) & set(o) for o in others)
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in ("lara_meshdist_build", "lara_meshdist_query", "lara_meshdist_face_normals"))
-    assert abi.header_structs(inc) == {}
     assert (meshdist.RMAX, meshdist.MAX_SPAN, meshdist.MAX_GRID, meshdist.HEADER_INTS) == (4, 4, 256, 4) == \
         (R.RMAX, R.MAX_SPAN, R.MAX_GRID, 4)
     assert (meshdist.HDR_BAD, meshdist.HDR_LARGE, meshdist.HDR_PAIRS, meshdist.HDR_TRIANGLES) == (0, 1, 2, 3)
-    text = abi.header_texts(inc)["lara_meshdist.h"]
+    text = abi.header_texts()["lara_meshdist.h"]
     for macro, value in (("RMAX", 4), ("MAX_SPAN", 4), ("MAX_GRID", 256), ("HEADER_INTS", 4), ("HDR_BAD", 0), ("HDR_LARGE", 1),
                          ("HDR_PAIRS", 2), ("HDR_TRIANGLES", 3)):
         assert f"#define LARA_MESHDIST_{macro} {value}\n" in text
-    # the count the headers directly under include/ declare, which tests/test_abi_cpu.py pins, did not move
-    assert not set(table) & set(abi.header_functions())
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHDIST:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_refusals(hip_lib):

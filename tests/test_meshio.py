@@ -1,37 +1,24 @@
-"""include/meshio/lara_meshio.h without a GPU: the signature table held to the header, the formatting routines of csrc/fmt9g.h (through
+"""include/lara_meshio.h without a GPU: the header's constants held to the module's, the formatting routines of csrc/fmt9g.h (through
 the library's host-only entries) held to Python's own "%.9g" and str(), the cases of tests/meshio_cases.py, the PLY restatement
 through read_ply, the header text, and the refusals.  tests/test_meshio_gpu.py holds the kernels to write_obj's bytes and to the
 restatement.  Every comparison here is an equality of bytes or bits: the routines are exact, so there is no bar."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, mesh, meshio
+from lara_amd import mesh, meshio
 from tests import meshio_cases as C
 from tests import meshio_restate as R
 
-STREAMED = ("lara_meshio_obj_lengths", "lara_meshio_obj_emit", "lara_meshio_ply_pack")
 FILL = 0xA5
 
 
-def test_signature_table_equals_its_header():
-    """include/meshio/lara_meshio.h against `_native.MESHIO_SIGNATURES`, with the comparison tests/test_abi_cpu.py applies to the
-    headers directly under include/: names, return types, every parameter's kind in order, the stream flag; the macros pinned."""
+def test_header_constants_equal_the_modules():
+    """The macros of include/lara_meshio.h pinned, equal to the module's, and consistent with one another."""
     from tests import test_abi_cpu as abi
-    declared = abi.header_functions(os.path.join(abi.ROOT, "include", "meshio"))
-    table = _native._SIGS_MESHIO
-    assert sorted(declared) == sorted(table) and len(table) == 8
-    assert not set(table) & (set(_native._SIGS) | set(_native._SIGS_MESHRENDER) | set(_native._SIGS_MESHMETRICS)
-                             | set(_native._SIGS_MESHSIMPLIFY) | set(_native._SIGS_DEPTHSURFACE))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in STREAMED)
-    assert abi.header_structs(os.path.join(abi.ROOT, "include", "meshio")) == {}
-    assert set(table) <= set(_native._ALL_SIGS)
-    text = abi.header_texts(os.path.join(abi.ROOT, "include", "meshio"))["lara_meshio.h"]
+    text = abi.header_texts()["lara_meshio.h"]
     for macro, value in (("BLOCK_LINES", 256), ("MAX_F32_TOKEN", 15), ("MAX_U32_TOKEN", 10), ("MAX_VERTEX_LINE", 98), ("MAX_FACE_LINE", 35),
                          ("PLY_FACE_ROW", 13), ("MAX_VERTICES", 2 ** 31 - 1), ("MAX_TRIANGLES", (2 ** 31 - 1) // 3),
                          ("MAX_INDEX", 2 ** 31 - 2), ("ERR_INDEX", 1)):
@@ -40,11 +27,6 @@ def test_signature_table_equals_its_header():
     assert (meshio.PLY_FACE_ROW, meshio.MAX_VERTICES, meshio.MAX_TRIANGLES, meshio.MAX_INDEX) == (13, 2 ** 31 - 1, (2 ** 31 - 1) // 3, 2 ** 31 - 2)
     assert meshio.MAX_VERTEX_LINE == 1 + 6 * (1 + meshio.MAX_F32_TOKEN) + 1 and meshio.MAX_FACE_LINE == 1 + 3 * (1 + meshio.MAX_U32_TOKEN) + 1
     assert 3 * meshio.MAX_TRIANGLES < 2 ** 31 <= 3 * (meshio.MAX_TRIANGLES + 1) and C.MAX_INDEX == meshio.MAX_INDEX
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHIO:
-        assert getattr(hip_lib, name) is not None
 
 
 def _format_f32(lib, bits):

@@ -1,40 +1,25 @@
-"""The float64 / integer restatement of include/meshmetrics/lara_meshmetrics.h (tests/meshmetrics_restate.py) held to closed forms,
-the signature table held to the header, the library's refusals, and the Evaluator's geometry hook -- no GPU.
+"""The float64 / integer restatement of include/lara_meshmetrics.h (tests/meshmetrics_restate.py) held to closed forms,
+the header's constants held to the module's, the library's refusals, and the Evaluator's geometry hook -- no GPU.
 tests/test_meshmetrics_gpu.py holds the kernels to this restatement."""
 import ctypes
 import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, evaluate, meshmetrics
+from lara_amd import evaluate, meshmetrics
 from tests import meshmetrics_restate as R
 
 
-def test_signature_table_equals_its_header():
-    """include/meshmetrics/lara_meshmetrics.h against `_native.MESHMETRICS_SIGNATURES`, with the comparison tests/test_abi_cpu.py
-    applies to the headers directly under include/: names, return types, every parameter's kind in order, the stream flag."""
+def test_header_constants_equal_the_modules():
+    """The limits of include/lara_meshmetrics.h, as the header defines them and as the module repeats them."""
     from tests import test_abi_cpu as abi
-    declared = abi.header_functions(os.path.join(abi.ROOT, "include", "meshmetrics"))
-    table = _native._SIGS_MESHMETRICS
-    assert sorted(declared) == sorted(table) and len(table) == 7
-    assert not set(table) & (set(_native._SIGS) | set(_native._SIGS_MESHRENDER))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in ("lara_meshmetrics_sample_surface", "lara_meshmetrics_nearest", "lara_meshmetrics_reduce"))
-    assert abi.header_structs(os.path.join(abi.ROOT, "include", "meshmetrics")) == {}
     assert (meshmetrics.MAX_SAMPLES, meshmetrics.RMAX, meshmetrics.MAX_GRID, meshmetrics.MAX_THRESHOLDS, meshmetrics.ROW) == \
         (1 << 22, 4, 256, 8, 12)
-    text = abi.header_texts(os.path.join(abi.ROOT, "include", "meshmetrics"))["lara_meshmetrics.h"]
+    text = abi.header_texts()["lara_meshmetrics.h"]
     for macro, value in (("MAX_SAMPLES", "(1 << 22)"), ("RMAX", "4"), ("MAX_GRID", "256"), ("MAX_THRESHOLDS", "8"), ("ROW", "12")):
         assert f"#define LARA_MESHMETRICS_{macro} {value}\n" in text
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHMETRICS:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_refusals(hip_lib):

@@ -1,4 +1,4 @@
-"""include/meshray/lara_meshray.h without a GPU: the signature table held to the header and the library's refusals; the ray-triangle
+"""include/lara_meshray.h without a GPU: the header's constants held to the module's and the library's refusals; the ray-triangle
 function of csrc/raytri.h, through its host entry, equal to the float64 restatement (tests/meshray_restate.py) bit for bit on every
 ray set of tests/meshray_cases.py; watertightness on the two spheres -- and the unsheared triple-product form shown to LOSE a ray
 there, so the rays bite; the margined entry parameter of csrc/raybox.h, through its host entry, held under the t the host function
@@ -7,14 +7,13 @@ to restated brute force on every case with both sibling orders; the visibility r
 of `depthsurface`.  tests/test_meshray_gpu.py holds the kernels to the same restatement.
 
 The bound's bar is the contract itself, with no tolerance: a finite entry <= t wherever the function computes a hit."""
-import os
 import sys
 
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, evaluate
+from lara_amd import evaluate
 from tests import meshbvh_restate as RB
 from tests import meshdist_restate as R
 from tests import meshray_cases as MC
@@ -22,33 +21,14 @@ from tests import meshray_restate as RR
 
 F32 = np.float32
 AMBIGUOUS_CAP = 0.005
-STREAMED = ("lara_meshray_cast", "lara_meshray_cast_other_order", "lara_meshray_occluded", "lara_meshray_visible")
 
 
-def test_signature_table_equals_its_header():
+def test_header_constants_equal_the_modules():
     from lara_amd import meshray
     from tests import test_abi_cpu as abi
-    inc = os.path.join(abi.ROOT, "include", "meshray")
-    declared = abi.header_functions(inc)
-    table = _native._SIGS_MESHRAY
-    assert sorted(declared) == sorted(table) and len(table) == 6
-    others = (_native._SIGS, _native._SIGS_MESHRENDER, _native._SIGS_MESHMETRICS, _native._SIGS_MESHSIMPLIFY,
-              _native._SIGS_DEPTHSURFACE, _native._SIGS_MESHIO, _native._SIGS_MESHDIST, _native._SIGS_MESHALIGN, _native._SIGS_MESHBVH)
-    assert not any(set(table) & set(o) for o in others)
-    assert all(set(o) <= set(_native._ALL_SIGS) for o in others + (table,))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in STREAMED)
-    assert abi.header_structs(inc) == {}
-    text = abi.header_texts(inc)["lara_meshray.h"]
+    text = abi.header_texts()["lara_meshray.h"]
     assert f"#define LARA_MESHRAY_MAX_EYES {meshray.MAX_EYES}\n" in text and meshray.MAX_EYES == RR.MAX_EYES == 64
     assert f"#define LARA_MESHRAY_MASKED_ORDER {meshray.MASKED_ORDER}\n" in text
-    assert not set(table) & set(abi.header_functions())
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHRAY:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_refusals(hip_lib):

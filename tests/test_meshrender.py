@@ -1,15 +1,14 @@
-"""The float64 / integer restatement of include/meshrender/lara_meshrender.h (tests/meshrender_restate.py) held to closed forms, and the
+"""The float64 / integer restatement of include/lara_meshrender.h (tests/meshrender_restate.py) held to closed forms, and the
 cases of tests/meshrender_cases.py held to what they are built to show -- no GPU.  tests/test_meshrender_gpu.py holds the
 kernels to this restatement."""
 import ctypes
-import os
 from fractions import Fraction
 
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, meshrender
+from lara_amd import meshrender
 from tests import meshrender_cases as C
 from tests import meshrender_restate as R
 
@@ -148,21 +147,6 @@ def test_each_mutation_fails_exactly_what_it_touches(results):
     mt = restate(case_c, mutate="tie_high")[0]
     assert np.array_equal(mt["face"], c["face"]) and np.array_equal(mt["depth"], c["depth"])
     assert np.array_equal(restate(case_b, mutate="tie_high")[0]["face"], b["face"])
-
-
-def test_signature_table_equals_its_header():
-    """include/meshrender/lara_meshrender.h against `_native.MESHRENDER_SIGNATURES`, with the comparison tests/test_abi_cpu.py
-    applies to the headers directly under include/ (its parser, its kinds): names, return types, every parameter's kind in
-    order, and the stream flag."""
-    from tests import test_abi_cpu as abi
-    declared = abi.header_functions(os.path.join(abi.ROOT, "include", "meshrender"))
-    table = _native._SIGS_MESHRENDER
-    assert sorted(declared) == sorted(table) and len(table) == 3
-    assert not set(table) & set(_native._SIGS)
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name == "lara_meshrender_views")
-    assert abi.header_structs(os.path.join(abi.ROOT, "include", "meshrender")) == {}
 
 
 def test_workspace_layout_and_refused_sizes(hip_lib):

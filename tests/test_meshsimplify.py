@@ -1,46 +1,26 @@
-"""The numpy restatement of include/meshsimplify/lara_meshsimplify.h (tests/meshsimplify_restate.py) held to closed forms, the
-signature table held to the header, the library's exports and refusals -- no GPU.  tests/test_meshsimplify_gpu.py holds the
+"""The numpy restatement of include/lara_meshsimplify.h (tests/meshsimplify_restate.py) held to closed forms, the
+header's constants held to the module's, the library's refusals -- no GPU.  tests/test_meshsimplify_gpu.py holds the
 kernels to this restatement."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from lara_amd import _native, meshsimplify
+from lara_amd import meshsimplify
 from tests import meshsimplify_restate as R
 
-STREAMED = ("lara_meshsimplify_cells", "lara_meshsimplify_clusters", "lara_meshsimplify_triangles", "lara_meshsimplify_corner_keys",
-            "lara_meshsimplify_bucket_count", "lara_meshsimplify_bucket_fill", "lara_meshsimplify_sums", "lara_meshsimplify_solve",
-            "lara_meshsimplify_vertex_map")
 
-
-def test_signature_table_equals_its_header():
-    """include/meshsimplify/lara_meshsimplify.h against `_native.MESHSIMPLIFY_SIGNATURES`, with the comparison
-    tests/test_abi_cpu.py applies to the headers directly under include/ (and tests/test_meshmetrics.py to its header): names,
-    return types, every parameter's kind in order, the stream flag."""
+def test_header_constants_equal_the_modules():
+    """The error bits, the cell limit and the counter slots of include/lara_meshsimplify.h, as the header defines them and as
+    the module and the restatement repeat them."""
     from tests import test_abi_cpu as abi
-    declared = abi.header_functions(os.path.join(abi.ROOT, "include", "meshsimplify"))
-    table = _native._SIGS_MESHSIMPLIFY
-    assert sorted(declared) == sorted(table) and len(table) == 12
-    assert not set(table) & (set(_native._SIGS) | set(_native._SIGS_MESHRENDER) | set(_native._SIGS_MESHMETRICS))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in STREAMED)
-    assert abi.header_structs(os.path.join(abi.ROOT, "include", "meshsimplify")) == {}
     assert (meshsimplify.ERR_INDEX, meshsimplify.ERR_PROBE, meshsimplify.ERR_NONFINITE, meshsimplify.ERR_NEGATIVE,
             meshsimplify.ERR_EXTENT, meshsimplify.MAX_CELL, meshsimplify.COUNTERS) == (1, 2, 4, 8, 16, 1 << 21, 4)
-    text = abi.header_texts(os.path.join(abi.ROOT, "include", "meshsimplify"))["lara_meshsimplify.h"]
+    text = abi.header_texts()["lara_meshsimplify.h"]
     for macro, value in (("ERR_INDEX", "1"), ("ERR_PROBE", "2"), ("ERR_NONFINITE", "4"), ("ERR_NEGATIVE", "8"), ("ERR_EXTENT", "16"),
                          ("MAX_CELL", "(1 << 21)"), ("N_DEGENERATE", "0"), ("N_DUPLICATE", "1"), ("N_ZERO_AREA", "2"),
                          ("N_CLAMPED", "3"), ("COUNTERS", "4")):
         assert f"#define LARA_MESHSIMPLIFY_{macro} {value}\n" in text
     assert R.MAX_CELL == meshsimplify.MAX_CELL
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHSIMPLIFY:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_size_queries_and_entry_points_refuse_bad_sizes(hip_lib):

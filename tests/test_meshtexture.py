@@ -1,5 +1,5 @@
-"""include/meshtexture/lara_meshtexture.h without a GPU, through the library's host twins (which run csrc/texatlas.h, the functions the
-kernels run): the signature table held to the header; the layout's owner and (a, b) tables against a plain double loop; the
+"""include/lara_meshtexture.h without a GPU, through the library's host twins (which run csrc/texatlas.h, the functions the
+kernels run): the header's constants held to the module's; the layout's owner and (a, b) tables against a plain double loop; the
 footprint property of the atlas -- a bilinear read inside a triangle touches only texels the triangle owns -- over a dense barycentric
 sample of every triangle for S = 3, 4, 7, 8; `corner_uvs`, points and anchors equal to the restatement (tests/meshtexture_restate.py)
 AS BIT PATTERNS; the bake's texture, view and alpha equal exactly and its weight as bits, on every case of tests/meshtexture_cases.py,
@@ -22,7 +22,6 @@ from tests import meshtexture_cases as TC
 from tests import meshtexture_restate as X
 
 F32 = np.float32
-STREAMED = ("lara_meshtexture_texels", "lara_meshtexture_bake", "lara_meshtexture_sample")
 PATCHES = (3, 4, 7, 8)
 
 
@@ -43,35 +42,20 @@ def _host_bake(c, kw, **more):
                    occlusion=False, host=True, mask=None if m is None else _t(m), vertex_colors=None if vc is None else _t(vc), **kw, **more)
 
 
-def test_signature_table_equals_its_header():
-    from lara_amd import meshtexture as MT
+def test_header_constants_equal_the_modules():
+    """The limits and blend modes of include/lara_meshtexture.h equal the module's; every entry but the size query either takes
+    the stream or is a host twin."""
+    from lara_amd import meshray, meshtexture as MT
     from tests import test_abi_cpu as abi
-    inc = os.path.join(abi.ROOT, "include", "meshtexture")
-    declared = abi.header_functions(inc)
-    table = _native._SIGS_MESHTEXTURE
-    assert sorted(declared) == sorted(table) and len(table) == 7
-    others = (_native._SIGS, _native._SIGS_MESHRENDER, _native._SIGS_MESHMETRICS, _native._SIGS_MESHSIMPLIFY,
-              _native._SIGS_DEPTHSURFACE, _native._SIGS_MESHIO, _native._SIGS_MESHDIST, _native._SIGS_MESHALIGN, _native._SIGS_MESHBVH,
-              _native._SIGS_MESHRAY, _native._SIGS_MESHSIGN, _native._SIGS_MESHTOPO, _native._SIGS_MESHWIND)
-    assert not any(set(table) & set(o) for o in others)
-    assert all(set(o) <= set(_native._ALL_SIGS) for o in others + (table,))
-    for name, (restype, argtypes, has_stream) in table.items():
-        assert (abi._ctypes_kind(restype), [abi._ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (name in STREAMED)
-        assert name in STREAMED or name.endswith("_host") or name == "lara_meshtexture_atlas_size"
-    assert abi.header_structs(inc) == {}
-    text = open(os.path.join(inc, "lara_meshtexture.h")).read()
-    from lara_amd import meshray
+    own = {name: sig for name, sig in _native._SIGS.items() if name.startswith("lara_meshtexture_")}
+    assert len(own) == 7
+    for name, (_, _, has_stream) in own.items():
+        assert has_stream or name.endswith("_host") or name == "lara_meshtexture_atlas_size", name
+    text = open(os.path.join(abi.ROOT, "include", "lara_meshtexture.h")).read()
     for macro, value in (("MIN_PATCH", MT.MIN_PATCH), ("MAX_PATCH", MT.MAX_PATCH), ("MAX_VIEWS", MT.MAX_VIEWS), ("MAX_POWER", MT.MAX_POWER),
                          ("WEIGHTED", MT.BLENDS["weighted"]), ("BEST", MT.BLENDS["best"])):
         assert f"#define LARA_MESHTEXTURE_{macro} {value}\n" in text
     assert MT.MAX_VIEWS == meshray.MAX_EYES == X.MAX_VIEWS == 64
-    assert not set(table) & set(abi.header_functions())
-
-
-def test_library_exports_every_declared_symbol(hip_lib):
-    for name in _native._SIGS_MESHTEXTURE:
-        assert getattr(hip_lib, name) is not None
 
 
 def test_the_unit_is_built_without_contraction():
