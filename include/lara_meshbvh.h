@@ -70,7 +70,8 @@
  * One thread per query.  Seed: a binary search (at most 26 steps) of the query's own Morton code in the sorted keys, and the eight
  * records of the leaf it lands in: a first best.  (A greedy descent into the child of the smallest bound was tried as the seed in
  * the restatement: on the bench mesh it costs 25 x the triangle tests, because the boxes of siblings overlap and many bounds are 0.)
- * Then a fixed-order walk over the implicit tree by index arithmetic, with no stack:
+ * Then a fixed-order walk over the implicit tree by index arithmetic, with no stack (lara_bvhwalk of csrc/bvhwalk.h, the one walk
+ * of every unit on this buffer; mask 0, the stored order):
  * from the root, a slot whose box is not empty and whose bound is <= best.d2 is entered (its first child, or at level 0 its eight
  * records), any other is stepped over; after the last of eight siblings the walk continues behind their parent.  Every slot is met at
  * most once, so the walk ends after at most sum P(n_k) steps.  The seed's leaf is met again; the tie rule makes that harmless.

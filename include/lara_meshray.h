@@ -64,7 +64,7 @@
  * bary [R][3] f32 (may be NULL): the three weights rounded once.
  *     face = argmin t (lara_raytri) over the valid triangles the ray hits; an exact tie of t goes to the SMALLER triangle id.
  *     No hit: t = +inf, face = -1, bary = NaN.
- * One thread per ray; no LDS, no atomics, no stack, no seed: the index-arithmetic walk of lara_meshbvh_query from the root.  A slot
+ * One thread per ray; no LDS, no atomics, no stack, no seed: the walk of lara_meshbvh_query (csrc/bvhwalk.h) from the root.  A slot
  * is stepped over when its box is empty, when lara_raybox(window [t_min, t_max]) is +inf, or when that entry parameter is STRICTLY
  * greater than the best t so far; at equality the slot is entered, because the tie rule may prefer a smaller id there.  The answer
  * does not depend on the order in which eight siblings are met, the work does: of eight siblings the one at counter c = 0 .. 7 is

@@ -2,7 +2,7 @@
  * meshsign/lara_meshsign.h -- is a point inside a mesh: crossings of fixed rays counted on the triangle hierarchy of
  * meshbvh/lara_meshbvh.h, the vote over them, signed distances, lattice counts for a volume IoU and the mesh's own signed volume
  * (part of liblara2dgs.so; opt-in, python side: lara_amd/meshsign.py; kernels: csrc/meshsign.hip; the crossing: csrc/raycross.h on
- * csrc/raytri.h; the box test: csrc/raybox.h; the walk's step: csrc/bvhwalk.h).  `bvh` is the buffer lara_meshbvh_build wrote; nothing
+ * csrc/raytri.h; the box test: csrc/raybox.h; the walk: csrc/bvhwalk.h).  `bvh` is the buffer lara_meshbvh_build wrote; nothing
  * is added to it.  All pointers are device pointers unless a parameter says HOST.  Returns 0 or a negative LARA2DGS_E_* code.  Work
  * is enqueued on `stream`; no entry point reads anything back to the host.  Built with -ffp-contract=off: the sequences written
  * here and in meshray/lara_meshray.h are the instructions.
@@ -29,7 +29,7 @@
  * If an accepted crossing has touch, the ray is unusable: cross = -1, wind = 0; so is every ray of a point with a coordinate that is
  * not finite.  For an outward-oriented closed mesh wind is +1 inside and 0 outside, cross odd inside and even outside.
  * One thread per (point, ray), blockIdx.y = k, so that a wave holds neighbouring points under one direction; no LDS, no atomics, no
- * stack.  The walk is the index arithmetic of lara_meshbvh_query and lara_meshray_cast from the root, in the stored sibling order,
+ * stack.  The walk is the one of lara_meshbvh_query and lara_meshray_cast (csrc/bvhwalk.h) from the root, in the stored sibling order,
  * without a best-so-far, a skip id or an early end: a slot is entered exactly when it is non-empty and lara_raybox(ray, lo, hi, 0,
  * +inf) is finite.  By the bound's contract (meshray/lara_meshray.h) every triangle lara_raytri accepts lies in entered boxes only,
  * and a leaf's records are all tested, so the counts equal brute force over all triangles as integers.

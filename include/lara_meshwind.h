@@ -3,7 +3,7 @@
  * meshbvh/lara_meshbvh.h: w(q) = (1 / 4 pi) sum over the valid triangles of the signed solid angle Omega_t(q).  For an
  * outward-oriented closed mesh w is 1 inside and 0 outside; for a mesh with holes, open boundaries, duplicated or non-manifold
  * parts it degrades smoothly, where the crossing counts of meshsign/lara_meshsign.h have no meaning (part of liblara2dgs.so;
- * opt-in, python side: lara_amd/meshwind.py; kernels: csrc/meshwind.hip; the term: csrc/solidangle.h; the walk's step:
+ * opt-in, python side: lara_amd/meshwind.py; kernels: csrc/meshwind.hip; the term: csrc/solidangle.h; the walk:
  * csrc/bvhwalk.h).  `bvh` is the buffer lara_meshbvh_build wrote; nothing is added to it.  All pointers are device pointers unless a
  * parameter says HOST.  Returns 0 or a negative LARA2DGS_E_* code.  Work is enqueued on `stream`; no entry point reads anything
  * back to the host.  Built with -ffp-contract=off: the sequences written here are the instructions.
@@ -40,7 +40,7 @@
  *
  * ---- lara_meshwind_rows: the walk ------------------------------------------------------------------------------------------------------
  * points [N][3] f32, bvh as built, moments as built, beta > 0 (+inf allowed) -> w [N] f64, n_tri [N] i32 or NULL, n_far [N] i32 or
- * NULL.  One thread per point; the stackless step of csrc/bvhwalk.h with mask 0 (the stored order), from the root.  At a slot
+ * NULL.  One thread per point; the stackless walk of csrc/bvhwalk.h with mask 0 (the stored order), from the root.  At a slot
  * that is not flagged, with d = c - q, d2 = (d_x d_x + d_y d_y) + d_z d_z:
  *     if d2 > (beta beta) r2:   sum += ((d_x N_x + d_y N_y) + d_z N_z) / (d2 sqrt(d2)), n_far += 1, step over the slot
  *     else at level 0:          sum += Omega of each valid record in stored order, n_tri += 1 for each

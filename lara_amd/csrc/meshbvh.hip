@@ -16,7 +16,7 @@
 #include "unigrid.h"
 #include "tridist.h"
 #include "boxbound.h"
-#include "meshbvh_layout.h"      // MbLayout, MbHeader, mb_layout, mb_load_box: shared with meshray.hip
+#include "bvhwalk.h"      // the walk, and meshbvh_layout.h (MbLayout, MbHeader, mb_layout, mb_load_box): shared by every walker
 
 #include <cmath>
 
@@ -125,19 +125,10 @@ mb_leaf_kernel(const int T, const int padded, const float4 *__restrict__ rec, fl
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= padded) return;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = 0; k < 8; k++) {
-        const long long r = 8ll * j + k;
-        if (r >= T) break;
-        const TriRec m = tri_load(rec, (int)r);
-        if (m.id < 0) continue;
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                lo[a] = fminf(lo[a], m.p[c][a]);
-                hi[a] = fmaxf(hi[a], m.p[c][a]);
-            }
-    }
+    mb_leaf_records(rec, T, j, [&](const TriRec &m, const int) LARA_BVHWALK_INLINE {
+        box_grow(lo, hi, m.p);
+        return false;
+    });
     mb_store_box(box, (size_t)j, lo, hi);
 }
 
@@ -164,14 +155,11 @@ mb_level_kernel(const int n_child, const int padded, const float2 *__restrict__ 
 // the eight records of leaf `leaf`; pos = the record of the candidate
 __device__ __forceinline__ void mb_leaf(Nearest<double> &best, int &pos, const float q[3], const float4 *__restrict__ rec, const int T,
                                         const int leaf) {
-    for (int k = 0; k < 8; k++) {
-        const long long r = 8ll * leaf + k;
-        if (r >= T) break;
-        const TriRec m = tri_load(rec, (int)r);
-        if (m.id < 0) continue;
+    mb_leaf_records(rec, T, leaf, [&](const TriRec &m, const int r) LARA_BVHWALK_INLINE {
         double c[3];
-        if (best.take(lara_tridist(q, m.p[0], m.p[1], m.p[2], c), m.id)) pos = (int)r;
-    }
+        if (best.take(lara_tridist(q, m.p[0], m.p[1], m.p[2], c), m.id)) pos = r;
+        return false;
+    });
 }
 
 __global__ void __launch_bounds__(256)
@@ -179,44 +167,37 @@ mb_query_kernel(const int N, const float *__restrict__ q, const char *__restrict
                 int *__restrict__ face, float *__restrict__ closest) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const MbHeader *hdr = (const MbHeader *)bvh;
-    const int T = hdr->count[LARA_MESHBVH_HDR_TRIANGLES], n_valid = min(hdr->count[LARA_MESHBVH_HDR_VALID], T);
-    const int top = hdr->L.levels - 1;
-    const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
+    const MbWalk w = mb_walk_open(bvh);
+    const MbHeader *hdr = w.hdr;
     const float qf[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
     Nearest<double> best{INFINITY, NEAREST_NONE};
     int pos = 0;      // the candidate's record: the records are in sorted order, not by id
-    const bool finite = fabsf(qf[0]) < INFINITY && fabsf(qf[1]) < INFINITY && fabsf(qf[2]) < INFINITY;
-    if (finite && n_valid > 0 && top >= 0 && top < MB_LEVELS) {
+    if (tri_point_finite(qf) && w.n_valid > 0 && w.ok) {
         // the seed: the first valid key not below the query's own code, and the leaf it lies in
         const unsigned long long *keys = (const unsigned long long *)(bvh + hdr->L.keys);
         const float lo[3] = {hdr->lo[0], hdr->lo[1], hdr->lo[2]}, inv[3] = {hdr->inv[0], hdr->inv[1], hdr->inv[2]};
         const unsigned long long want = (unsigned long long)mb_morton(qf, lo, inv) << 26;
-        int a = 0, b = n_valid;      // the first position in [0, n_valid] whose key is >= want
+        int a = 0, b = w.n_valid;      // the first position in [0, n_valid] whose key is >= want
         for (int step = 0; step < 27 && a < b; step++) {
             const int mid = a + ((b - a) >> 1);
             if (keys[mid] < want) a = mid + 1; else b = mid;
         }
-        mb_leaf(best, pos, qf, rec, T, min(a, n_valid - 1) >> 3);
-        // the walk
-        const long long steps = hdr->L.steps;
-        int level = top, idx = 0;
-        for (long long step = 0; step < steps; step++) {
-            if (idx >= ((hdr->L.n[level] + 7) & ~7)) break;      // (never, on a buffer lara_meshbvh_build wrote)
-            const float2 *box = (const float2 *)(bvh + hdr->L.box[level]);
-            float blo[3], bhi[3];
-            mb_load_box(box, (size_t)idx, blo, bhi);
-            const double bound = lara_boxbound(qf, blo, bhi);
-            if (bound < (double)INFINITY && !(bound > best.d2)) {
-                if (level > 0) { level--; idx <<= 3; continue; }
-                mb_leaf(best, pos, qf, rec, T, idx);
-            }
-            idx++;
-            while (level < top && (idx & 7) == 0) { idx >>= 3; level++; }
-            if (level == top) break;
-        }
+        mb_leaf(best, pos, qf, w.rec, w.T, min(a, w.n_valid - 1) >> 3);
+        // the walk, in the stored order: a slot is entered unless it is empty or its bound is strictly above the best so far
+        lara_bvhwalk(
+            hdr->L, 0,
+            [&](const int level, const int slot) LARA_BVHWALK_INLINE {
+                float blo[3], bhi[3];
+                mb_load_box((const float2 *)(bvh + hdr->L.box[level]), (size_t)slot, blo, bhi);
+                const double bound = lara_boxbound(qf, blo, bhi);
+                return bound < (double)INFINITY && !(bound > best.d2);
+            },
+            [&](const int leaf) LARA_BVHWALK_INLINE {
+                mb_leaf(best, pos, qf, w.rec, w.T, leaf);
+                return false;
+            });
     }
-    tri_write_result(i, qf, best, rec, pos, dist, face, closest);
+    tri_write_result(i, qf, best, w.rec, pos, dist, face, closest);
 }
 
 }  // namespace

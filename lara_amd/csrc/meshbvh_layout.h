@@ -1,6 +1,7 @@
-// meshbvh_layout.h -- the buffer lara_meshbvh_build writes, as the units that walk it see it (meshbvh.hip, meshray.hip): the layout
-// as a function of T, the header's slot, and the load of a 24-byte box; the 48-byte record (TriRec, tri_load) is trimesh.h's.
-// Format and sizes in include/lara_meshbvh.h.  Include after common.h and unigrid.h.
+// meshbvh_layout.h -- the buffer lara_meshbvh_build writes, as the units that walk it see it (meshbvh.hip, meshray.hip, meshsign.hip,
+// meshwind.hip): the layout as a function of T, the header's slot, and the load of a 24-byte box; the 48-byte record (TriRec,
+// tri_load) is trimesh.h's, the walk itself bvhwalk.h's, which includes this file.  Format and sizes in include/lara_meshbvh.h.
+// Include after common.h and unigrid.h.
 #pragma once
 
 #include "trimesh.h"

@@ -1,6 +1,6 @@
 // meshray.hip -- ray queries on the triangle hierarchy of meshbvh.hip on gfx950: the first triangle a ray meets, whether it meets
-// any, and which of E eyes see a point.  A second walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records:
-// trimesh.h), with the ray-triangle function of raytri.h per record and the margined entry parameter of raybox.h per
+// any, and which of E eyes see a point.  The walk of bvhwalk.h over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its
+// records: trimesh.h), with the ray-triangle function of raytri.h per record and the margined entry parameter of raybox.h per
 // box.  Interface, the function, the bound's derivation and the tie rule in include/lara_meshray.h.
 //
 //   mr_cast_kernel<MASKED>        one thread per ray: the walk, then t, face and the barycentrics of the best record
@@ -11,7 +11,7 @@
 #include "unigrid.h"
 #include "raytri.h"
 #include "raybox.h"
-#include "meshbvh_layout.h"
+#include "bvhwalk.h"
 #include "../../include/lara_meshray.h"
 
 #include <cmath>
@@ -22,59 +22,33 @@ constexpr int64_t MR_MAX_RAYS = 1ll << 30;
 
 struct MrBest { double t; int id, pos; };
 
-// the eight records of leaf `leaf`; ANY: true at the first accepted triangle.  Triangle `skip` is ignored (-1: none is)
-template <bool ANY>
-__device__ __forceinline__ bool mr_leaf(MrBest &best, const LaraRay &ray, const double t_min, const double t_max, const int skip,
-                                        const float4 *__restrict__ rec, const int T, const int leaf) {
-    for (int k = 0; k < 8; k++) {
-        const long long r = 8ll * leaf + k;
-        if (r >= T) break;
-        const TriRec m = tri_load(rec, (int)r);
-        if (m.id < 0 || m.id == skip) continue;
-        double t, b[3];
-        if (!lara_raytri(ray, t_min, t_max, m.p[0], m.p[1], m.p[2], t, b)) continue;
-        if (ANY) return true;
-        if (t < best.t || (t == best.t && m.id < best.id)) { best.t = t; best.id = m.id; best.pos = (int)r; }      // (Nearest's rule, on t)
-    }
-    return false;
-}
-
 // The walk.  A slot is stepped over when it is empty, when the ray has no parameter of its window inside the inflated box, or when
 // the entry parameter is strictly greater than the best t so far; at equality it is entered.  MASKED: of eight siblings the
 // one at counter c is slot c ^ mask, mask = the signs of d (x -> bit 0, y -> bit 1, z -> bit 2, the order of the Morton code):
-// roughly front to back.  `pos` is the counter within the level; its upper bits are the parent's slot.  ANY: true when a
-// triangle was accepted.
+// roughly front to back.  Triangle `skip` is ignored (-1: none is).  ANY: ended by the first accepted triangle, and true then.
 template <bool ANY, bool MASKED>
 __device__ __forceinline__ bool mr_walk(MrBest &best, const LaraRay &ray, const double t_min, const double t_max, const int skip,
                                         const char *__restrict__ bvh) {
-    const MbHeader *hdr = (const MbHeader *)bvh;
-    const int T = hdr->count[LARA_MESHBVH_HDR_TRIANGLES], n_valid = min(hdr->count[LARA_MESHBVH_HDR_VALID], T);
-    const int top = hdr->L.levels - 1;
-    if (!ray.ok || n_valid <= 0 || top < 0 || top >= MB_LEVELS) return false;
-    const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
+    const MbWalk w = mb_walk_open(bvh);
+    if (!ray.ok || w.n_valid <= 0 || !w.ok) return false;
     const int mask = MASKED ? (ray.d[0] < 0.0 ? 1 : 0) | (ray.d[1] < 0.0 ? 2 : 0) | (ray.d[2] < 0.0 ? 4 : 0) : 0;
-    const long long steps = hdr->L.steps;
-    int level = top, pos = 0;
-    for (long long step = 0; step < steps; step++) {
-        const int slot = level < top ? pos ^ mask : pos;
-        if (slot >= ((hdr->L.n[level] + 7) & ~7)) break;      // (never, on a buffer lara_meshbvh_build wrote)
-        const float2 *box = (const float2 *)(bvh + hdr->L.box[level]);
-        float blo[3], bhi[3];
-        mb_load_box(box, (size_t)slot, blo, bhi);
-        const double entry = lara_raybox(ray, blo, bhi, t_min, t_max);
-        if (entry < (double)INFINITY && !(entry > best.t)) {
-            if (level > 0) { level--; pos = slot << 3; continue; }
-            if (mr_leaf<ANY>(best, ray, t_min, t_max, skip, rec, T, slot) && ANY) return true;
-        }
-        pos++;
-        while (level < top && (pos & 7) == 0) {      // behind the last of eight siblings: on behind their parent
-            const int parent = (pos >> 3) - 1;
-            level++;
-            pos = (level < top ? parent ^ mask : parent) + 1;
-        }
-        if (level == top) break;
-    }
-    return false;
+    return lara_bvhwalk(
+        w.hdr->L, mask,
+        [&](const int level, const int slot) LARA_BVHWALK_INLINE {
+            float blo[3], bhi[3];
+            mb_load_box((const float2 *)(bvh + w.hdr->L.box[level]), (size_t)slot, blo, bhi);
+            const double entry = lara_raybox(ray, blo, bhi, t_min, t_max);
+            return entry < (double)INFINITY && !(entry > best.t);
+        },
+        [&](const int leaf) LARA_BVHWALK_INLINE {
+            return mb_leaf_records(w.rec, w.T, leaf, [&](const TriRec &m, const int r) LARA_BVHWALK_INLINE {
+                double t, b[3];
+                if (m.id == skip || !lara_raytri(ray, t_min, t_max, m.p[0], m.p[1], m.p[2], t, b)) return false;
+                if (ANY) return true;
+                if (t < best.t || (t == best.t && m.id < best.id)) { best.t = t; best.id = m.id; best.pos = r; }      // (Nearest's rule, on t)
+                return false;
+            });
+        });
 }
 
 __device__ __forceinline__ LaraRay mr_ray(const float *__restrict__ o, const float *__restrict__ d, const size_t i) {
@@ -128,7 +102,7 @@ mr_visible_kernel(const int N, const float *__restrict__ p, const int *__restric
     const float pf[3] = {p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]};
     const int ignore = skip ? skip[i] : -1;
     unsigned long long word = 0ull;
-    if (fabsf(pf[0]) < INFINITY && fabsf(pf[1]) < INFINITY && fabsf(pf[2]) < INFINITY) {
+    if (tri_point_finite(pf)) {
         for (int e = 0; e < E; e++) {
             const float of[3] = {eyes[3 * e], eyes[3 * e + 1], eyes[3 * e + 2]};
             const float df[3] = {pf[0] - of[0], pf[1] - of[1], pf[2] - of[2]};

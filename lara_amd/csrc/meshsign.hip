@@ -1,7 +1,7 @@
 // meshsign.hip -- is a point inside a mesh, on the triangle hierarchy of meshbvh.hip on gfx950: the crossings of up to three fixed
 // rays per point counted with their orientation, the vote over them with the signed distance, the lattice counts of a volume IoU,
-// and the mesh's signed volume.  A third walk over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records: trimesh.h),
-// with the crossing of raycross.h per record and the margined entry parameter of raybox.h per box; the walk's step is bvhwalk.h's.
+// and the mesh's signed volume.  The walk of bvhwalk.h over the buffer lara_meshbvh_build wrote (meshbvh_layout.h; its records:
+// trimesh.h), with the crossing of raycross.h per record and the margined entry parameter of raybox.h per box.
 // Interface, the rules and the orders of summation in include/lara_meshsign.h.
 //
 //   ms_rows_kernel       one thread per (point, ray), blockIdx.y = ray: the walk without a best-so-far, every accepted record counted
@@ -15,7 +15,6 @@
 #include "raybox.h"
 #include "raycross.h"
 #include "bvhwalk.h"
-#include "meshbvh_layout.h"
 #include "rowsum.h"
 #include "../../include/lara_meshsign.h"
 
@@ -28,42 +27,29 @@ constexpr int MS_K = LARA_MESHSIGN_MAX_RAYS;
 
 struct MsCount { int cross, wind, touch; };
 
-// the eight records of leaf `leaf`: every accepted crossing counts
-__device__ __forceinline__ void ms_leaf(MsCount &c, const LaraRay &ray, const float4 *__restrict__ rec, const int T, const int leaf) {
-    for (int k = 0; k < 8; k++) {
-        const long long r = 8ll * leaf + k;
-        if (r >= T) break;
-        const TriRec m = tri_load(rec, (int)r);
-        if (m.id < 0) continue;
-        int orient, touch;
-        if (!lara_raycross(ray, m.p[0], m.p[1], m.p[2], orient, touch)) continue;
-        c.cross++;
-        c.wind += orient;
-        c.touch |= touch;
-    }
-}
-
 // The walk, in the stored sibling order: a slot is entered exactly when it is non-empty and the ray has a parameter of [0, +inf)
-// inside the inflated box.  `pos` is the counter within the level; its upper bits are the parent's slot.
+// inside the inflated box; every accepted crossing of a leaf's records counts.
 __device__ __forceinline__ void ms_walk(MsCount &c, const LaraRay &ray, const char *__restrict__ bvh) {
-    const MbHeader *hdr = (const MbHeader *)bvh;
-    const int T = hdr->count[LARA_MESHBVH_HDR_TRIANGLES], n_valid = min(hdr->count[LARA_MESHBVH_HDR_VALID], T);
-    const int top = hdr->L.levels - 1;
-    if (!ray.ok || n_valid <= 0 || top < 0 || top >= MB_LEVELS) return;
-    const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
-    const long long steps = hdr->L.steps;
-    int level = top, pos = 0;
-    for (long long step = 0; step < steps; step++) {
-        if (pos >= ((hdr->L.n[level] + 7) & ~7)) break;      // (never, on a buffer lara_meshbvh_build wrote)
-        const float2 *box = (const float2 *)(bvh + hdr->L.box[level]);
-        float blo[3], bhi[3];
-        mb_load_box(box, (size_t)pos, blo, bhi);
-        if (lara_raybox(ray, blo, bhi, 0.0, (double)INFINITY) < (double)INFINITY) {
-            if (level > 0) { level--; pos <<= 3; continue; }
-            ms_leaf(c, ray, rec, T, pos);
-        }
-        if (lara_bvhwalk_advance(level, pos, top, 0)) break;
-    }
+    const MbWalk w = mb_walk_open(bvh);
+    if (!ray.ok || w.n_valid <= 0 || !w.ok) return;
+    lara_bvhwalk(
+        w.hdr->L, 0,
+        [&](const int level, const int slot) LARA_BVHWALK_INLINE {
+            float blo[3], bhi[3];
+            mb_load_box((const float2 *)(bvh + w.hdr->L.box[level]), (size_t)slot, blo, bhi);
+            return lara_raybox(ray, blo, bhi, 0.0, (double)INFINITY) < (double)INFINITY;
+        },
+        [&](const int leaf) LARA_BVHWALK_INLINE {
+            return mb_leaf_records(w.rec, w.T, leaf, [&](const TriRec &m, const int) LARA_BVHWALK_INLINE {
+                int orient, touch;
+                if (lara_raycross(ray, m.p[0], m.p[1], m.p[2], orient, touch)) {
+                    c.cross++;
+                    c.wind += orient;
+                    c.touch |= touch;
+                }
+                return false;      // (no record ends this walk)
+            });
+        });
 }
 
 __global__ void __launch_bounds__(256)
@@ -76,7 +62,7 @@ ms_rows_kernel(const int N, const float *__restrict__ p, const int K, const char
     const float df[3] = {k == 0 ? dirs[0][0] : (k == 1 ? dirs[1][0] : dirs[2][0]), k == 0 ? dirs[0][1] : (k == 1 ? dirs[1][1] : dirs[2][1]),
                          k == 0 ? dirs[0][2] : (k == 1 ? dirs[1][2] : dirs[2][2])};
     MsCount c{0, 0, 0};
-    const bool finite = fabsf(pf[0]) < INFINITY && fabsf(pf[1]) < INFINITY && fabsf(pf[2]) < INFINITY;
+    const bool finite = tri_point_finite(pf);
     if (finite) ms_walk(c, lara_ray_setup(pf, df), bvh);
     const bool usable = finite && !c.touch;
     cross[(size_t)i * K + k] = usable ? c.cross : -1;

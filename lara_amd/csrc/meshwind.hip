@@ -1,8 +1,9 @@
 // meshwind.hip -- generalised (solid-angle) winding numbers of a mesh, on the triangle hierarchy of meshbvh.hip on gfx950: per-node
 // moments in a buffer of their own, a walk that sums the exact term of solidangle.h near the point and a node's dipole term far
-// from it, and the classification of the sums (the two host entries: meshwind_host.h).  A fourth walk over the buffer
-// lara_meshbvh_build wrote (meshbvh_layout.h; its records: trimesh.h), and the first that needs per-node data beyond boxes; the
-// walk's step is bvhwalk.h's.  Interface, the rules and the orders of summation in include/lara_meshwind.h.
+// from it, and the classification of the sums (the two host entries: meshwind_host.h).  The walk of bvhwalk.h over the buffer
+// lara_meshbvh_build wrote (meshbvh_layout.h; its records: trimesh.h), and the one walker that needs per-node data beyond boxes:
+// its three-way decision on a slot (empty, far, near) is the walk's `enter`.  Interface, the rules and the orders of summation
+// in include/lara_meshwind.h.
 //
 //   mw_leaf_kernel       one thread per stored slot of level 0: the sums over its up-to-8 valid records, in stored order
 //   mw_level_kernel      one thread per stored slot of level k: the sums over its 8 children, in slot order; one launch a level
@@ -12,7 +13,6 @@
 #include "common.h"
 #include "unigrid.h"
 #include "bvhwalk.h"
-#include "meshbvh_layout.h"
 #include "solidangle.h"
 #include "meshwind_host.h"
 #include "../../include/lara_meshwind.h"
@@ -75,11 +75,7 @@ mw_leaf_kernel(const int T, const int padded, const char *__restrict__ bvh, cons
     if (j == 0) *(MwHeader *)mom = h;
     const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
     double N[3] = {0.0, 0.0, 0.0}, A = 0.0, S[3] = {0.0, 0.0, 0.0};
-    for (int k = 0; k < 8; k++) {
-        const long long r = 8ll * j + k;
-        if (r >= T) break;
-        const TriRec m = tri_load(rec, (int)r);
-        if (m.id < 0) continue;
+    mb_leaf_records(rec, T, j, [&](const TriRec &m, const int) LARA_BVHWALK_INLINE {
         double u[3], v[3], c[3];
 #pragma unroll
         for (int a = 0; a < 3; a++) {
@@ -95,7 +91,8 @@ mw_leaf_kernel(const int T, const int padded, const char *__restrict__ bvh, cons
             N[a] += 0.5 * n[a];
             S[a] += At * c[a];
         }
-    }
+        return false;
+    });
     mw_store_slot((double2 *)(mom + h.off[0]) + 4 * (size_t)j, N, A, S, (const float2 *)(bvh + box_off), (size_t)j);
 }
 
@@ -117,56 +114,43 @@ mw_level_kernel(const int T, const int n_child, const int padded, const char *__
     mw_store_slot(out + 4 * (size_t)j, N, A, S, (const float2 *)(bvh + box_off), (size_t)j);
 }
 
-// The walk, in the stored sibling order.  `pos` is the counter within the level; its upper bits are the parent's slot.
+// The walk, in the stored sibling order.
 __global__ void __launch_bounds__(256)
 mw_rows_kernel(const int N, const float *__restrict__ p, const char *__restrict__ bvh, const char *__restrict__ mom, const double bb,
                double *__restrict__ w, int *__restrict__ n_tri, int *__restrict__ n_far) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const MbHeader *hdr = (const MbHeader *)bvh;
+    const MbWalk wk = mb_walk_open(bvh);
     const MwHeader *mh = (const MwHeader *)mom;
-    const int T = hdr->count[LARA_MESHBVH_HDR_TRIANGLES];
-    const int top = hdr->L.levels - 1;
-    const float4 *rec = (const float4 *)(bvh + hdr->L.rec);
     const float pf[3] = {p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]};
-    const bool finite = fabsf(pf[0]) < INFINITY && fabsf(pf[1]) < INFINITY && fabsf(pf[2]) < INFINITY;
-    const bool ok = finite && mh->T == (int64_t)T && top >= 0 && top < MB_LEVELS;
+    const bool ok = tri_point_finite(pf) && mh->T == (int64_t)wk.T && wk.ok;
     double sum = ok ? 0.0 : (double)NAN;
     int tested = 0, far = 0;
     if (ok) {
         const double q[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
-        const long long steps = hdr->L.steps;
-        int level = top, pos = 0;
-        for (long long step = 0; step < steps; step++) {
-            if (pos >= ((hdr->L.n[level] + 7) & ~7)) break;      // (never, on buffers the two builds wrote)
-            const double2 *slot = (const double2 *)(mom + mh->off[level]) + 4 * (size_t)pos;
-            const double2 s1 = slot[1];
-            if (s1.y > 0.0) {
+        lara_bvhwalk(
+            wk.hdr->L, 0,
+            // an empty slot: nothing; a far one: its dipole term; a near one: entered
+            [&](const int level, const int pos) LARA_BVHWALK_INLINE {
+                const double2 *slot = (const double2 *)(mom + mh->off[level]) + 4 * (size_t)pos;
+                const double2 s1 = slot[1];
+                if (!(s1.y > 0.0)) return false;
                 const double2 s2 = slot[2], s3 = slot[3];
                 const double d[3] = {s2.x - q[0], s2.y - q[1], s3.x - q[2]};
                 const double d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-                if (d2 > bb * s3.y) {
-                    const double2 s0 = slot[0];
-                    sum += ((d[0] * s0.x + d[1] * s0.y) + d[2] * s1.x) / (d2 * sqrt(d2));
-                    far++;
-                } else if (level > 0) {
-                    level--;
-                    pos <<= 3;
-                    continue;
-                } else {
-#pragma unroll 1
-                    for (int k = 0; k < 8; k++) {
-                        const long long r = 8ll * pos + k;
-                        if (r >= T) break;
-                        const TriRec m = tri_load(rec, (int)r);
-                        if (m.id < 0) continue;
-                        sum += lara_solidangle(pf, m.p[0], m.p[1], m.p[2]);
-                        tested++;
-                    }
-                }
-            }
-            if (lara_bvhwalk_advance(level, pos, top, 0)) break;
-        }
+                if (!(d2 > bb * s3.y)) return true;
+                const double2 s0 = slot[0];
+                sum += ((d[0] * s0.x + d[1] * s0.y) + d[2] * s1.x) / (d2 * sqrt(d2));
+                far++;
+                return false;
+            },
+            [&](const int leaf) LARA_BVHWALK_INLINE {
+                return mb_leaf_records(wk.rec, wk.T, leaf, [&](const TriRec &m, const int) LARA_BVHWALK_INLINE {
+                    sum += lara_solidangle(pf, m.p[0], m.p[1], m.p[2]);
+                    tested++;
+                    return false;      // (no record ends this walk)
+                });
+            });
     }
     w[i] = sum / MW_FOUR_PI;
     if (n_tri) n_tri[i] = tested;

@@ -40,6 +40,11 @@ __device__ __forceinline__ bool tri_fetch(const int Nv, const float *__restrict_
     return ok;
 }
 
+// a query point the searches take: every coordinate finite
+__device__ __forceinline__ bool tri_point_finite(const float p[3]) {
+    return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;
+}
+
 struct TriRec { float p[3][3]; int id; };
 __device__ __forceinline__ TriRec tri_unpack(const float4 a, const float4 b, const float4 c) {
     TriRec r;

@@ -59,34 +59,49 @@ def crossings(bvh, points, rays=3):
     return cross, wind
 
 
-def _vote(bvh, cross, wind, rule, dist=None):
+def verdicts(device, N, dist=None):
+    """Uninitialised (inside [N] uint8, status [N] uint8, sdf [N] fp32 or None without ``dist``) for a classifier to fill."""
+    inside = torch.empty(N, dtype=torch.uint8, device=device)
+    status = torch.empty(N, dtype=torch.uint8, device=device)
+    return inside, status, None if dist is None else torch.empty(N, dtype=torch.float32, device=device)
+
+
+def vote(bvh, cross, wind, rule, dist=None):
     """(inside [N] uint8, status [N] uint8, sdf [N] fp32 or None) of the rows under ``rule`` (its number)."""
     N, K = cross.shape
-    inside = torch.empty(N, dtype=torch.uint8, device=bvh.device)
-    status = torch.empty(N, dtype=torch.uint8, device=bvh.device)
-    sdf = None if dist is None else torch.empty(N, dtype=torch.float32, device=bvh.device)
-    call("lara_meshsign_vote", bvh.device, N, K, cross, wind, rule, dist, inside, status, sdf)
-    return inside, status, sdf
+    out = verdicts(bvh.device, N, dist)
+    call("lara_meshsign_vote", bvh.device, N, K, cross, wind, rule, dist, *out)
+    return out
+
+
+def _classifier(rays, rule):
+    """The rule as the shells below take it: (bvh, points[, dist]) -> (inside, status, sdf)."""
+    K, r = _checked(rays, rule)
+    return lambda bvh, P, dist=None: vote(bvh, *crossings(bvh, P, K), r, dist)
 
 
 @torch.no_grad()
 def contains(bvh, points, rays=3, rule="parity", return_status=False):
     """bool [N][, status [N] uint8]: the point lies inside the mesh by the vote of its usable rays."""
-    K, r = _checked(rays, rule)
-    inside, status, _ = _vote(bvh, *crossings(bvh, points, K), r)
+    inside, status, _ = _classifier(rays, rule)(bvh, points)
     return (inside.bool(), status) if return_status else inside.bool()
+
+
+def signed_distance_by(classify, mesh, bvh, points, who, return_face=False, return_status=False):
+    """``signed_distance`` under any rule: ``bvh.query``'s distance with the sign ``classify(mesh, points, dist)`` gives it;
+    ``mesh`` is what the classifier walks (``bvh``, or what was built on it), ``who`` the module a refusal names."""
+    P = rows3(points, bvh.device, "points", who)
+    dist, face = bvh.query(P)
+    _, status, sdf = classify(mesh, P, dist)
+    out = (sdf,) + ((face,) if return_face else ()) + ((status,) if return_status else ())
+    return out if len(out) > 1 else sdf
 
 
 @torch.no_grad()
 def signed_distance(bvh, points, rays=3, rule="parity", return_face=False, return_status=False):
     """sdf [N] fp32[, face [N] int32][, status [N] uint8]: ``bvh.query``'s distance, negative where ``contains``; NaN and +inf
     as ``query`` gives them."""
-    K, r = _checked(rays, rule)
-    P = rows3(points, bvh.device, "points", "meshsign")
-    dist, face = bvh.query(P)
-    _, status, sdf = _vote(bvh, *crossings(bvh, P, K), r, dist)
-    out = (sdf,) + ((face,) if return_face else ()) + ((status,) if return_status else ())
-    return out if len(out) > 1 else sdf
+    return signed_distance_by(_classifier(rays, rule), bvh, bvh, points, "meshsign", return_face, return_status)
 
 
 def lattice(lo, hi, resolution, device):
@@ -108,7 +123,7 @@ def root_box(bvh):
     return bvh.level_boxes(len(bvh.layout["levels"]) - 1)[0]
 
 
-def _union(boxes):
+def union_box(boxes):
     """(lo, hi) fp32 numpy of the union of [n,6] host boxes, the empty ones (lo > hi) left out; zeros when all are empty."""
     boxes = [b for b in np.asarray(boxes, np.float32).reshape(-1, 6) if b[0] <= b[3]]
     if not boxes:
@@ -116,15 +131,20 @@ def _union(boxes):
     return np.min([b[:3] for b in boxes], 0), np.max([b[3:] for b in boxes], 0)
 
 
+def own_box(bvh, lo=None, hi=None):
+    """``lo``, ``hi`` of a lattice over ``bvh``'s mesh: each as given, or the root box's (one host read of six floats)."""
+    if lo is None or hi is None:
+        blo, bhi = union_box(root_box(bvh).cpu().numpy())
+        lo, hi = blo if lo is None else lo, bhi if hi is None else hi
+    return lo, hi
+
+
 @torch.no_grad()
 def sdf_grid(bvh, resolution, lo=None, hi=None, rays=3, rule="parity"):
     """[R,R,R] fp32: ``signed_distance`` at the cell centres of ``lattice(lo, hi, R)``, index [x, y, z]; ``lo`` / ``hi`` default
     to the mesh's own box (one host read of six floats)."""
-    if lo is None or hi is None:
-        blo, bhi = _union(root_box(bvh).cpu().numpy())
-        lo, hi = blo if lo is None else lo, bhi if hi is None else hi
     R = int(resolution)
-    P, _ = lattice(lo, hi, R, bvh.device)
+    P, _ = lattice(*own_box(bvh, lo, hi), R, bvh.device)
     return signed_distance(bvh, P.view(-1, 3), rays, rule).view(R, R, R)
 
 
@@ -137,7 +157,8 @@ def mesh_volume(bvh):
     return out
 
 
-def _as_bvh(mesh, device):
+def as_bvh(mesh, device):
+    """``mesh`` as a ``TriangleBVH``: itself, or one built from a (vertices, triangles) pair, moved to ``device`` if one is given."""
     from .meshbvh import TriangleBVH
     if isinstance(mesh, TriangleBVH):
         return mesh
@@ -145,6 +166,28 @@ def _as_bvh(mesh, device):
     if device is not None:
         V, F = V.to(device), F.to(device)
     return TriangleBVH(V, F)
+
+
+def lattice_scores(classify, pred, gt, resolution, who):
+    """``volume_scores`` under any rule: ``pred`` and ``gt`` are (mesh, its ``TriangleBVH``) pairs, ``mesh`` what
+    ``classify(mesh, points)`` walks.  Returns the keys every rule shares; a rule adds its own, the shares of undisputed centres
+    (1 - counts[4] / n_lattice, 1 - counts[5] / n_lattice) under its own names among them.  Two host reads: the boxes, the results."""
+    (a, bvh_a), (b, bvh_b) = pred, gt
+    if bvh_a.device != bvh_b.device:
+        raise RuntimeError(f"lara_amd.{who}: the two meshes live on different devices")
+    dev, R = bvh_a.device, int(resolution)
+    lo, hi = union_box(torch.stack([root_box(bvh_a), root_box(bvh_b)]).cpu().numpy())
+    P, step = lattice(lo, hi, R, dev)
+    P = P.view(-1, 3)
+    N = P.shape[0]
+    sides = [classify(m, P)[:2] for m in (a, b)]
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    call("lara_meshsign_counts", dev, N, sides[0][0], sides[0][1], sides[1][0], sides[1][1], counts)
+    vols = torch.stack([mesh_volume(bvh_a), mesh_volume(bvh_b)])
+    counts, vols = counts.cpu().tolist(), vols.cpu().tolist()
+    cell = float(step[0]) * float(step[1]) * float(step[2])
+    return {"volume_iou": counts[2] / counts[3] if counts[3] else None, "volume_pred": counts[0] * cell, "volume_gt": counts[1] * cell,
+            "volume_pred_mesh": vols[0][0], "volume_gt_mesh": vols[1][0], "n_lattice": N, "resolution": R, "counts": counts}
 
 
 @torch.no_grad()
@@ -156,21 +199,8 @@ def volume_scores(pred, gt, resolution=128, rays=3, rule="parity", device=None):
     of centres on which the side's usable rays agreed: below 1 for a mesh that is not closed, and then the IoU is a number about
     a surface without an inside), ``n_lattice``, ``resolution``, ``rule``, ``rays``, and ``counts``: the eight integers of ``lara_meshsign_counts``.  Two host
     reads: the boxes, the results."""
-    K, r = _checked(rays, rule)
-    a, b = _as_bvh(pred, device), _as_bvh(gt, device)
-    if a.device != b.device:
-        raise RuntimeError("lara_amd.meshsign: the two meshes live on different devices")
-    dev, R = a.device, int(resolution)
-    lo, hi = _union(torch.stack([root_box(a), root_box(b)]).cpu().numpy())
-    P, step = lattice(lo, hi, R, dev)
-    P = P.view(-1, 3)
-    N = P.shape[0]
-    sides = [_vote(m, *crossings(m, P, K), r)[:2] for m in (a, b)]
-    counts = torch.empty(8, dtype=torch.int64, device=dev)
-    call("lara_meshsign_counts", dev, N, sides[0][0], sides[0][1], sides[1][0], sides[1][1], counts)
-    vols = torch.stack([mesh_volume(a), mesh_volume(b)])
-    counts, vols = counts.cpu().tolist(), vols.cpu().tolist()
-    cell = float(step[0]) * float(step[1]) * float(step[2])
-    return {"volume_iou": counts[2] / counts[3] if counts[3] else None, "volume_pred": counts[0] * cell, "volume_gt": counts[1] * cell,
-            "volume_pred_mesh": vols[0][0], "volume_gt_mesh": vols[1][0], "unanimous_pred": 1.0 - counts[4] / N,
-            "unanimous_gt": 1.0 - counts[5] / N, "n_lattice": N, "resolution": R, "rule": rule, "rays": K, "counts": counts}
+    classify = _classifier(rays, rule)
+    a, b = as_bvh(pred, device), as_bvh(gt, device)
+    s = lattice_scores(classify, (a, a), (b, b), resolution, "meshsign")
+    counts, N = s["counts"], s["n_lattice"]
+    return {**s, "unanimous_pred": 1.0 - counts[4] / N, "unanimous_gt": 1.0 - counts[5] / N, "rule": rule, "rays": int(rays)}

@@ -99,22 +99,22 @@ def winding(bvh_or_field, points, beta=2.0, return_counts=False, field=None):
     return (w, n_tri, n_far) if return_counts else w
 
 
-def _classify(dev, w, threshold, band, dist=None):
-    """(inside [N] uint8, status [N] uint8, sdf [N] fp32 or None) of the sums."""
-    N = w.shape[0]
-    inside = torch.empty(N, dtype=torch.uint8, device=dev)
-    status = torch.empty(N, dtype=torch.uint8, device=dev)
-    sdf = None if dist is None else torch.empty(N, dtype=torch.float32, device=dev)
-    call("lara_meshwind_classify", dev, N, w, float(threshold), float(band), dist, inside, status, sdf)
-    return inside, status, sdf
+def _classifier(beta, threshold, band):
+    """The rule as ``meshsign``'s shells take it: (field, points[, dist]) -> (inside [N] uint8, status [N] uint8, sdf [N] fp32
+    or None)."""
+    def classify(f, P, dist=None):
+        w = winding(f, P, beta)
+        out = meshsign.verdicts(f.device, w.shape[0], dist)
+        call("lara_meshwind_classify", f.device, w.shape[0], w, float(threshold), float(band), dist, *out)
+        return out
+    return classify
 
 
 @torch.no_grad()
 def contains(bvh_or_field, points, beta=2.0, threshold=0.5, band=0.05, return_status=False, field=None):
     """bool [N][, status [N] uint8]: w > ``threshold``."""
     beta, band = _checked(beta, band)
-    f = _field(bvh_or_field, field)
-    inside, status, _ = _classify(f.device, winding(f, points, beta), threshold, band)
+    inside, status, _ = _classifier(beta, threshold, band)(_field(bvh_or_field, field), points)
     return (inside.bool(), status) if return_status else inside.bool()
 
 
@@ -124,11 +124,7 @@ def signed_distance(bvh_or_field, points, beta=2.0, threshold=0.5, band=0.05, re
     ``query`` gives them."""
     beta, band = _checked(beta, band)
     f = _field(bvh_or_field, field)
-    P = rows3(points, f.device, "points", "meshwind")
-    dist, face = f.bvh.query(P)
-    _, status, sdf = _classify(f.device, winding(f, P, beta), threshold, band, dist)
-    out = (sdf,) + ((face,) if return_face else ()) + ((status,) if return_status else ())
-    return out if len(out) > 1 else sdf
+    return meshsign.signed_distance_by(_classifier(beta, threshold, band), f, f.bvh, points, "meshwind", return_face, return_status)
 
 
 @torch.no_grad()
@@ -136,11 +132,8 @@ def winding_grid(bvh_or_field, resolution, lo=None, hi=None, beta=2.0):
     """[R,R,R] float64: ``winding`` at the cell centres of ``meshsign.lattice(lo, hi, R)``, index [x, y, z]; ``lo`` / ``hi`` default
     to the mesh's own box (one host read of six floats)."""
     f = _field(bvh_or_field)
-    if lo is None or hi is None:
-        blo, bhi = meshsign._union(meshsign.root_box(f.bvh).cpu().numpy())
-        lo, hi = blo if lo is None else lo, bhi if hi is None else hi
     R = int(resolution)
-    P, _ = meshsign.lattice(lo, hi, R, f.device)
+    P, _ = meshsign.lattice(*meshsign.own_box(f.bvh, lo, hi), R, f.device)
     return winding(f, P.view(-1, 3), beta).view(R, R, R)
 
 
@@ -152,21 +145,8 @@ def volume_scores(pred, gt, resolution=128, beta=2.0, threshold=0.5, band=0.05, 
     outside the band around the threshold) where it has ``unanimous_*``, ``rule`` = "solid_angle", ``rays`` = 0, and the three
     parameters ``beta``, ``threshold``, ``band`` beside them.  Two host reads: the boxes, the results."""
     beta, band = _checked(beta, band)
-    a, b = (m if isinstance(m, WindingField) else WindingField(meshsign._as_bvh(m, device)) for m in (pred, gt))
-    if a.device != b.device:
-        raise RuntimeError("lara_amd.meshwind: the two meshes live on different devices")
-    dev, R = a.device, int(resolution)
-    lo, hi = meshsign._union(torch.stack([meshsign.root_box(a.bvh), meshsign.root_box(b.bvh)]).cpu().numpy())
-    P, step = meshsign.lattice(lo, hi, R, dev)
-    P = P.view(-1, 3)
-    N = P.shape[0]
-    sides = [_classify(dev, winding(m, P, beta), threshold, band)[:2] for m in (a, b)]
-    counts = torch.empty(8, dtype=torch.int64, device=dev)
-    call("lara_meshsign_counts", dev, N, sides[0][0], sides[0][1], sides[1][0], sides[1][1], counts)
-    vols = torch.stack([meshsign.mesh_volume(a.bvh), meshsign.mesh_volume(b.bvh)])
-    counts, vols = counts.cpu().tolist(), vols.cpu().tolist()
-    cell = float(step[0]) * float(step[1]) * float(step[2])
-    return {"volume_iou": counts[2] / counts[3] if counts[3] else None, "volume_pred": counts[0] * cell, "volume_gt": counts[1] * cell,
-            "volume_pred_mesh": vols[0][0], "volume_gt_mesh": vols[1][0], "decided_pred": 1.0 - counts[4] / N,
-            "decided_gt": 1.0 - counts[5] / N, "n_lattice": N, "resolution": R, "rule": RULE, "rays": 0, "counts": counts,
+    a, b = (m if isinstance(m, WindingField) else WindingField(meshsign.as_bvh(m, device)) for m in (pred, gt))
+    s = meshsign.lattice_scores(_classifier(beta, threshold, band), (a, a.bvh), (b, b.bvh), resolution, "meshwind")
+    counts, N = s["counts"], s["n_lattice"]
+    return {**s, "decided_pred": 1.0 - counts[4] / N, "decided_gt": 1.0 - counts[5] / N, "rule": RULE, "rays": 0,
             "beta": beta if math.isfinite(beta) else "inf", "threshold": float(threshold), "band": band}

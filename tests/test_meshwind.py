@@ -374,8 +374,8 @@ def test_add_volume_accepts_the_dict():
     import inspect
     from lara_amd import meshsign, meshwind
 
-    def keys(fn):
-        src = inspect.getsource(fn)
+    def keys(fn):      # the common part of the dict is meshsign.lattice_scores', the rule's own keys are added by `fn`
+        src = inspect.getsource(meshsign.lattice_scores) + inspect.getsource(fn)
         return [k for k in ("volume_iou", "volume_pred", "volume_gt", "volume_pred_mesh", "volume_gt_mesh", "unanimous_pred", "unanimous_gt",
                             "decided_pred", "decided_gt", "n_lattice", "resolution", "rule", "rays", "counts") if f'"{k}":' in src]
     swap = {"unanimous_pred": "decided_pred", "unanimous_gt": "decided_gt"}

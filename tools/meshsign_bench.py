@@ -110,16 +110,16 @@ def main():
     res["volume_scores"] = {k: scores[k] for k in ("volume_iou", "volume_pred", "volume_gt", "volume_pred_mesh", "volume_gt_mesh",
                                                    "unanimous_pred", "unanimous_gt", "n_lattice")}
     res["volume_scores_ms"] = timed(lambda: meshsign.volume_scores(bvh, bvh2, resolution=R), max(1, steps // 2), 1)
-    lo, hi = meshsign._union(torch.stack([meshsign.root_box(bvh), meshsign.root_box(bvh2)]).cpu().numpy())
+    lo, hi = meshsign.union_box(torch.stack([meshsign.root_box(bvh), meshsign.root_box(bvh2)]).cpu().numpy())
     L = meshsign.lattice(lo, hi, R, dev)[0].view(-1, 3)
     rows_a, rows_b = meshsign.crossings(bvh, L), meshsign.crossings(bvh2, L)
-    va, vb = meshsign._vote(bvh, *rows_a, 0), meshsign._vote(bvh2, *rows_b, 0)
+    va, vb = meshsign.vote(bvh, *rows_a, 0), meshsign.vote(bvh2, *rows_b, 0)
     counts = torch.empty(8, dtype=torch.int64, device=dev)
     res["volume_scores_stages_ms"] = {
         "lattice": timed(lambda: meshsign.lattice(lo, hi, R, dev), steps, warmup),
         "rows_pred": timed(lambda: meshsign.crossings(bvh, L), steps, warmup),
         "rows_gt": timed(lambda: meshsign.crossings(bvh2, L), steps, warmup),
-        "vote_each": timed(lambda: meshsign._vote(bvh, *rows_a, 0), steps, warmup),
+        "vote_each": timed(lambda: meshsign.vote(bvh, *rows_a, 0), steps, warmup),
         "counts": timed(lambda: _native.call("lara_meshsign_counts", dev, L.shape[0], va[0], va[1], vb[0], vb[1], counts), steps, warmup),
         "mesh_volume_each": res["mesh_volume_ms"]}
     res["lattice_rows_Mrays_per_s"] = L.shape[0] * K / res["volume_scores_stages_ms"]["rows_pred"] / 1e3
