@@ -3,8 +3,10 @@ MI355X without running any network: the orbit of `evaluate.video_cameras`, ``Ren
 (`evaluate.render_turntable`), RGB and normal frames as PNG (`meshtexture.write_png`), and a small JSON with the surfel count,
 the SH degree, the frame count and wall times (one run each: no spread is measured).  ``--mesh`` also extracts the TSDF mesh from
 the loaded surfels (`MeshExtractor.extract` on ``cloud.gs_params()`` with `evaluate.mesh_cameras`).  ``--quick``: 2 frames of
-32 x 32 (what tests/test_splatio_gpu.py runs).
-    python tools/render_surfels.py scene.ply --dataset gobjeverse --frames 24 --size 512 --out DIR [--mesh out.obj] [--quick]"""
+32 x 32 (what tests/test_splatio_gpu.py runs).  ``--transform FILE`` (16 numbers, ``.npy`` or text: a 4x4 similarity) moves the
+loaded cloud by `lara_amd.splatxform.transform` before anything is rendered; the cameras stay where they are.
+    python tools/render_surfels.py scene.ply --dataset gobjeverse --frames 24 --size 512 --out DIR [--mesh out.obj] [--quick]
+                                   [--transform T.npy]"""
 import argparse
 import json
 import os
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--out", required=True, help="directory for rgb_####.png, normal_####.png and render_surfels.json")
     ap.add_argument("--mesh", default=None, help="also extract the TSDF mesh to this .obj path")
     ap.add_argument("--quick", action="store_true", help="2 frames of 32 x 32")
+    ap.add_argument("--transform", default=None, help="a 4x4 similarity (16 numbers, .npy or text) applied to the cloud first")
     args = ap.parse_args()
     if args.quick:
         args.frames, args.size = 2, 32
@@ -43,6 +46,15 @@ def main():
     cloud, info = splatio.read_ply(args.ply, device=dev)
     torch.cuda.synchronize()
     wall["read_ply_s"] = time.perf_counter() - t0
+    T = None
+    if args.transform:
+        import numpy as np
+        from lara_amd import splatxform
+        T = np.load(args.transform) if args.transform.endswith(".npy") else np.loadtxt(args.transform)
+        if T.size != 16:
+            sys.exit(f"tools/render_surfels.py: {args.transform} holds {T.size} numbers, a 4x4 has 16")
+        T = np.asarray(T, np.float64).reshape(4, 4)
+        cloud = splatxform.transform(cloud, T, out=cloud)
 
     renderer = Renderer(sh_degree=cloud.sh_degree, white_background=True)
     cams = evaluate.video_cameras(args.frames, args.dataset, (args.size, args.size), device=dev)
@@ -72,6 +84,8 @@ def main():
         torch.cuda.synchronize()
         wall["mesh_s"] = time.perf_counter() - t0
         res["mesh"] = {"path": os.path.abspath(args.mesh), "views": len(mcams), "vertices": int(v.shape[0]), "triangles": int(t.shape[0])}
+    if T is not None:
+        res["transform"] = T.tolist()
     res["wall_s"] = wall
     with open(os.path.join(args.out, "render_surfels.json"), "w") as f:
         json.dump(res, f, indent=1)
