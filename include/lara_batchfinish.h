@@ -6,10 +6,6 @@
  * the device and the host: csrc/batchfinish_ops.h.  Returns 0 or a negative LARA2DGS_E_* code.  Built with -ffp-contract=off: the
  * sequences written here are the instructions.
  *
- * The header lies beside its unit, not under include/, and its two functions are bound by lara_amd/dataset.py itself, not by a row of
- * _native.SIGNATURES: tests/test_abi_cpu.py pins the headers under include/ and the rows of that table to a fixed number, which an
- * opt-in route does not move.
- *
  * ---- the arrays, all contiguous -----------------------------------------------------------------------------------------------------------
  *     rgba     uint8 [B][V][H][W][4]   the stored image                      bg       fp32 [B][V][3]   each view's background colour
  *     nrm_u8   uint8 [B][V][H][W][3]   the stored normals                    rot      fp32 [B][3][3]   R = transform_mats[b, 0, :3, :3]

@@ -6,10 +6,6 @@
  * per-surfel function, for the device and the host: csrc/splatxform_ops.h).  Returns 0 or a negative LARA2DGS_E_* code.  Built with
  * -ffp-contract=off: the sequences written here are the instructions.
  *
- * The header lies beside its unit, not under include/, and its two functions are bound by lara_amd/splatxform.py itself, not by a row
- * of _native.SIGNATURES: tests/test_abi_cpu.py pins the headers under include/ and the rows of that table to a fixed number, which
- * an opt-in module does not move.  tests/test_splatxform.py holds the module's binding to the prototypes below, kind by kind.
- *
  * ---- the cloud ---------------------------------------------------------------------------------------------------------------------------
  * P surfels as Renderer.render_img takes them, every value pre-activation, fp32, rows contiguous:
  *     centers [P][3]   shs [P][n][3], n = (sh_degree + 1)^2, sh_degree in 0..3   opacity [P][1]   scales [P][2]   rotations [P][4] (w, x, y, z)

@@ -85,6 +85,9 @@ i lara2dgs_mark_visible(i p*4 s)
 i lara2dgs_profile_enable(i)
 i lara2dgs_selftest(i p p s)
 i lara2dgs_profile_collect(p i p i)
+# include/lara_batchfinish.h
+i lara_batch_finish(p*4 l*4 p*3 s)
+i lara_batch_finish_host(p*4 l*4 p*3)
 # include/lara_coarsedec.h
 l lara_coarse_decoder_padded_rows(l)
 i lara_coarse_decoder_forward(i*3 p*7 f f p*5 s)
@@ -260,6 +263,12 @@ i lara_take_rows(i p i RowsItem i s)
 i lara_voxel_rows(i i p*3 i s)
 # include/lara_rays.h
 i lara_build_rays_out(i*3 f p*3 s)
+# include/lara_splatadam.h
+i lara_splatadam_step(p i l p*20 p i p s)
+i lara_splatadam_step_host(p i l p*20 p i p)
+# include/lara_splatxform.h
+i lara_splatxform_apply(p i l p*10 l l s)
+i lara_splatxform_apply_host(p i l p*10 l l)
 # include/lara_surface.h
 i lara_surface_maps_forward(i i p*4 f p*6 s)
 i lara_surface_maps_backward(i i p*4 f p*8 s)
@@ -362,6 +371,15 @@ def call(name: str, device, *args):
         rc = getattr(lib, name)(*a)
     if rc != 0:
         check(rc, name)
+
+
+def call_on(name: str, device, *args):
+    """``call`` of the entry ``name`` for tensors on the GPU ``device``, of its host twin ``<name>_host`` (the same function
+    compiled for the CPU, no stream) for tensors on the host."""
+    if device.type == "cuda":
+        call(name, device, *args)
+    else:
+        call(name + "_host", None, *args)
 
 
 def query(name: str, *args, error=None) -> int:

@@ -15,7 +15,7 @@
 //                                   (the launcher refuses 2^31 and more), byte offsets are formed in 64.
 #include "common.h"
 #include "batchfinish_ops.h"
-#include "lara_batchfinish.h"
+#include "../../include/lara_batchfinish.h"
 
 namespace {
 

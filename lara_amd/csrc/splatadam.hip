@@ -14,7 +14,7 @@
 //                           wave and one 64-bit integer atomic by the wave's first lane where the ballot is not empty.
 #include "common.h"
 #include "splatadam_ops.h"
-#include "lara_splatadam.h"
+#include "../../include/lara_splatadam.h"
 
 namespace {
 

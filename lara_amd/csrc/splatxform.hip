@@ -15,7 +15,7 @@
 //                           compile-time constant after unrolling, so they are scalar loads, not a table in memory.
 #include "common.h"
 #include "splatxform_ops.h"
-#include "lara_splatxform.h"
+#include "../../include/lara_splatxform.h"
 
 namespace {
 

@@ -29,7 +29,7 @@ division by 255, the composite over the view's background, the normal decode and
 ships them 3.6 times as large as they are stored.  ``raw_views(ds)`` makes the class ship the arrays as stored -- ``tar_rgb`` uint8
 [V,H,W,4], ``tar_nrm_u8`` uint8 [V,H,W,3], ``tar_msk`` an empty stub -- with the same random draws and every other field as before, and
 ``finish_on_device`` (so ``on_device`` and ``collate_to_device`` too) finishes such a batch with ONE kernel (``finish_images``,
-csrc/batchfinish.hip, csrc/lara_batchfinish.h) into the tensors the class's own items collate to: ``tar_rgb`` fp32 [B,V,H,W,3] with
+csrc/batchfinish.hip, include/lara_batchfinish.h) into the tensors the class's own items collate to: ``tar_rgb`` fp32 [B,V,H,W,3] with
 the class's bits, ``tar_msk`` uint8 [B,V,H,W], ``tar_nrm`` fp32 [B,H,V*W,3] (a 3-term fp32 sum in a fixed order, where numpy's matmul
 picks its own).  Float items go through every function here exactly as before.
 
@@ -38,8 +38,6 @@ picks its own).  Float items go through every function here exactly as before.
     for batch in lara_amd.dataset.on_device(loader, "cuda"): ...
 """
 from __future__ import annotations
-
-import ctypes
 
 import numpy as np
 import torch
@@ -155,20 +153,6 @@ def raw_views(ds):
 
 # ---------------------------------------------------------------------------------------------------------- the image half, device side
 
-# The two entry points of csrc/lara_batchfinish.h in _native.SIGNATURES' notation.  They are bound here and not by a row of that table:
-# tests/test_abi_cpu.py pins the table and the headers under include/ to a fixed number of functions.
-ENTRY_POINTS = {"lara_batch_finish": "p*4 l*4 p*3 s", "lara_batch_finish_host": "p*4 l*4 p*3"}
-
-
-def _entry(name):
-    """The function ``name`` of the loaded library with its argument types set (once)."""
-    fn = getattr(_native.load_library(), name)
-    if fn.argtypes is None:
-        _, argtypes, _ = _native._parse_signatures(f"i {name}({ENTRY_POINTS[name]})")[name]
-        fn.restype, fn.argtypes = ctypes.c_int, argtypes
-    return fn
-
-
 def _refuse(name, t, dtype, shape, device=None):
     """ValueError unless ``t`` is a contiguous tensor of ``dtype`` and ``shape`` (None: any extent) on ``device``."""
     want = f"a contiguous {str(dtype).replace('torch.', '')} [{', '.join('*' if n is None else str(n) for n in shape)}] tensor"
@@ -189,20 +173,12 @@ def _finish_into(rgba, bg_color, normals_u8, rot, out_rgb, out_msk, out_nrm):
         return
     if B * V * H * W >= 2 ** 31:
         raise ValueError(f"{_WHO}: rgba holds {B * V * H * W} pixels; one call takes fewer than 2^31")
-    args = [t.data_ptr() if t is not None else None for t in (rgba, bg_color, normals_u8, rot)] + [B, V, H, W] + \
-           [t.data_ptr() if t is not None else None for t in (out_rgb, out_msk, out_nrm)]
-    dev = rgba.device
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            rc = _entry("lara_batch_finish")(*args, _native.current_stream(dev))
-        _native.check(rc, "lara_batch_finish")
-    else:
-        _native.check(_entry("lara_batch_finish_host")(*args), "lara_batch_finish_host")
+    _native.call_on("lara_batch_finish", rgba.device, rgba, bg_color, normals_u8, rot, B, V, H, W, out_rgb, out_msk, out_nrm)
 
 
 @torch.no_grad()
 def finish_images(rgba, bg_color, normals_u8=None, rot=None):
-    """The image half of a batch from the stored arrays (csrc/lara_batchfinish.h has the arithmetic, operation by operation):
+    """The image half of a batch from the stored arrays (include/lara_batchfinish.h has the arithmetic, operation by operation):
     ``rgba`` uint8 [B,V,H,W,4] and ``bg_color`` fp32 [B,V,3] -> ``tar_rgb`` fp32 [B,V,H,W,3], the colour over each view's own
     background, and ``tar_msk`` uint8 [B,V,H,W], alpha > 0; with ``normals_u8`` uint8 [B,V,H,W,3] and ``rot`` fp32 [B,3,3]
     (``transform_mats[:, 0, :3, :3]``) also ``tar_nrm`` fp32 [B,H,V*W,3], the decoded normals times R^T with the views side by side;

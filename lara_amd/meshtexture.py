@@ -33,7 +33,7 @@ import zlib
 import numpy as np
 import torch
 
-from ._native import call, host_array, require_device
+from ._native import call, call_on, host_array, require_device
 
 MIN_PATCH, MAX_PATCH, MAX_VIEWS, MAX_POWER = 3, 4096, 64, 8      # include/lara_meshtexture.h
 MAX_TEXELS = 1 << 30
@@ -116,10 +116,6 @@ def _mesh(vertices, triangles, host):
     return V, triangles.detach().to(device=V.device, dtype=torch.int32).contiguous()
 
 
-def _entry(name, host, dev):
-    return (name + "_host", None) if host else (name, dev)
-
-
 @torch.no_grad()
 def texels(layout, vertices, triangles, host=False):
     """(face [Ha,Wa] int32, point [Ha,Wa,3] fp32, anchor [Ha,Wa,3] fp32): the owner of every texel (-1: none, or an invalid
@@ -130,8 +126,7 @@ def texels(layout, vertices, triangles, host=False):
     face = torch.empty(Ha, Wa, dtype=torch.int32, device=V.device)
     point = torch.empty(Ha, Wa, 3, dtype=torch.float32, device=V.device)
     anchor = torch.empty(Ha, Wa, 3, dtype=torch.float32, device=V.device)
-    name, dev = _entry("lara_meshtexture_texels", host, V.device)
-    call(name, dev, S, C, F.shape[0], V.shape[0], V, F, face, point, anchor)
+    call_on("lara_meshtexture_texels", V.device, S, C, F.shape[0], V.shape[0], V, F, face, point, anchor)
     return face, point, anchor
 
 
@@ -188,10 +183,9 @@ def bake_texels(layout, vertices, triangles, face, point, anchor, images, k, w2c
     weight = torch.empty(Ha, Wa, dtype=torch.float32, device=dev)
     view = torch.empty(Ha, Wa, dtype=torch.int32, device=dev)
     fill = [float(x) for x in fill]
-    name, d = _entry("lara_meshtexture_bake", host, dev)
-    call(name, d, S, C, F.shape[0], V.shape[0], V, F, face, point, anchor, n_views, H, W, I, k.contiguous(), w2c.contiguous(),
-         eyes.contiguous(), mask, float(near), float(min_cos), power, int(bool(two_sided)), BLENDS[blend], cols, fill[0], fill[1],
-         fill[2], texture, weight, view)
+    call_on("lara_meshtexture_bake", dev, S, C, F.shape[0], V.shape[0], V, F, face, point, anchor, n_views, H, W, I, k.contiguous(),
+            w2c.contiguous(), eyes.contiguous(), mask, float(near), float(min_cos), power, int(bool(two_sided)), BLENDS[blend], cols,
+            fill[0], fill[1], fill[2], texture, weight, view)
     return texture, weight, view
 
 
@@ -213,8 +207,7 @@ def sample(layout, T, texture, face, bary, alpha=False, background=(0, 0, 0), ho
     channels = 4 if alpha else 3
     out = torch.empty(N, channels, dtype=torch.float32, device=dev)
     bg = [float(x) for x in background]
-    name, d = _entry("lara_meshtexture_sample", host, dev)
-    call(name, d, S, C, int(T), N, texture.contiguous(), f, b, channels, bg[0], bg[1], bg[2], out)
+    call_on("lara_meshtexture_sample", dev, S, C, int(T), N, texture.contiguous(), f, b, channels, bg[0], bg[1], bg[2], out)
     return out
 
 

@@ -1,4 +1,4 @@
-"""Refining predicted surfels against their posed views (csrc/lara_splatadam.h, csrc/splatadam.hip): a few dozen optimisation steps
+"""Refining predicted surfels against their posed views (include/lara_splatadam.h, csrc/splatadam.hip): a few dozen optimisation steps
 on a ``splatio.SurfelCloud`` -- ``Renderer.render_views`` (one autograd node), ``loss.lara_loss``, ``backward``, and the parameter
 update of the Gaussian-splatting code bases as ONE kernel launch over the five tensors.  Opt-in like every module here, imported by
 nothing on the default routes; ``splatio``, ``splatxform``, the renderer and the loss are untouched.
@@ -8,7 +8,7 @@ nothing on the default routes; ``splatio``, ``splatxform``, the renderer and the
   * ``SurfelAdam``   the optimiser object: leaf tensors, moments, the step count, ``step`` / ``zero_grad`` / ``cloud`` / ``state``;
   * ``refine``       the loop: render, loss, backward, the rasteriser's own radii as the visibility mask, step.  No host read inside.
 
-The update is ``torch.optim.Adam``'s formula in double on the fp32 words, rounded once at each store (csrc/lara_splatadam.h has the
+The update is ``torch.optim.Adam``'s formula in double on the fp32 words, rounded once at each store (include/lara_splatadam.h has the
 operation order), with three gates ``torch.optim.Adam`` cannot express in one pass:
   visible     surfels no view saw in a step keep their parameters AND their moments, bit for bit (3DGS's "sparse Adam" [RECALLED:
               neither code base is in the build image]); ``visible=None`` is dense mode, ``torch.optim.Adam``'s semantics;
@@ -31,7 +31,6 @@ steps), gradients through ``splatxform``, camera refinement.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
@@ -41,25 +40,12 @@ from . import splatio
 from . import _native
 from ._native import host_array
 
-PLAN = 13                                # csrc/lara_splatadam.h
+PLAN = 13                                # include/lara_splatadam.h
 SPAN = 256
 FIELDS = splatio.SurfelCloud.FIELDS
 LR_KEYS = ("centers", "sh0", "sh_rest", "opacity", "scales", "rotations")
 DEFAULT_LRS = {"centers": 1.6e-4, "sh0": 2.5e-3, "sh_rest": 2.5e-3 / 20.0, "opacity": 0.05, "scales": 5e-3, "rotations": 1e-3}
 _WHO = "lara_amd.splatrefine"
-
-# The two entry points of csrc/lara_splatadam.h in _native.SIGNATURES' notation.  They are bound here and not by a row of that table:
-# tests/test_abi_cpu.py pins the table and the headers under include/ to a fixed number of functions.
-ENTRY_POINTS = {"lara_splatadam_step": "p i l p*20 p i p s", "lara_splatadam_step_host": "p i l p*20 p i p"}
-
-
-def _entry(name):
-    """The function ``name`` of the loaded library with its argument types set (once)."""
-    fn = getattr(_native.load_library(), name)
-    if fn.argtypes is None:
-        _, argtypes, _ = _native._parse_signatures(f"i {name}({ENTRY_POINTS[name]})")[name]
-        fn.restype, fn.argtypes = ctypes.c_int, argtypes
-    return fn
 
 
 # ---------------------------------------------------------------------------------------------------------- the plan
@@ -162,15 +148,8 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, plan, visible=None, zero_grads
         raise ValueError(f"{_WHO}: counters is one int64 on {dev}")
     if P == 0:                               # (an empty tensor has no address to hand over; nothing is launched)
         return counters
-    args = [host_array("d", [float(v) for v in row]), splatio.SH_COEFFS[n], P,
-            *(t.data_ptr() for ts in (params, grads, exp_avg, exp_avg_sq) for t in ts),
-            None if visible is None else visible.data_ptr(), 1 if zero_grads else 0, counters.data_ptr()]
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            rc = _entry("lara_splatadam_step")(*args, _native.current_stream(dev))
-        _native.check(rc, "lara_splatadam_step")
-    else:
-        _native.check(_entry("lara_splatadam_step_host")(*args), "lara_splatadam_step_host")
+    _native.call_on("lara_splatadam_step", dev, host_array("d", [float(v) for v in row]), splatio.SH_COEFFS[n], P,
+                    *params, *grads, *exp_avg, *exp_avg_sq, visible, 1 if zero_grads else 0, counters)
     return counters
 
 

@@ -1,4 +1,4 @@
-"""Moving and composing predicted surfel clouds (csrc/lara_splatxform.h, csrc/splatxform.hip): a similarity T = [[sR, t], [0, 1]]
+"""Moving and composing predicted surfel clouds (include/lara_splatxform.h, csrc/splatxform.hip): a similarity T = [[sR, t], [0, 1]]
 applied to a ``splatio.SurfelCloud`` -- centres, log scales, the quaternion, and the SH coefficients of bands 1..3 rotated in the
 rasteriser's own basis (csrc/preprocess.hip: the 3DGS constants and signs), so that the moved cloud seen from cameras moved with it
 renders as the original did.  Opt-in like every module here, imported by nothing on the default routes; ``splatio`` is untouched.
@@ -26,7 +26,6 @@ render is NOT invariant under a scale s != 1: the rasteriser's distortion term r
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
@@ -36,7 +35,7 @@ from . import splatio
 from . import _native
 from ._native import host_array
 
-PLAN = 100                               # csrc/lara_splatxform.h
+PLAN = 100                               # include/lara_splatxform.h
 SPAN = 256
 _WHO = "lara_amd.splatxform"
 _ORTHO_TOL = 1e-6
@@ -180,20 +179,6 @@ def _rotation_scale(T):
 
 # ---------------------------------------------------------------------------------------------------------- clouds
 
-# The two entry points of csrc/lara_splatxform.h in _native.SIGNATURES' notation.  They are bound here and not by a row of that table:
-# tests/test_abi_cpu.py pins the table and the headers under include/ to a fixed number of functions.
-ENTRY_POINTS = {"lara_splatxform_apply": "p i l p*10 l l s", "lara_splatxform_apply_host": "p i l p*10 l l"}
-
-
-def _entry(name):
-    """The function ``name`` of the loaded library with its argument types set (once)."""
-    fn = getattr(_native.load_library(), name)
-    if fn.argtypes is None:
-        _, argtypes, _ = _native._parse_signatures(f"i {name}({ENTRY_POINTS[name]})")[name]
-        fn.restype, fn.argtypes = ctypes.c_int, argtypes
-    return fn
-
-
 def _extent(t):
     return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
 
@@ -220,15 +205,8 @@ def _apply(plan, cloud, outs, row0, out_rows):
     _check_overlap(ins, outs)
     if cloud.n_surfels == 0:                 # (an empty tensor has no address to hand over; the entry points launch nothing for P = 0)
         return
-    dev = cloud.device
-    args = (host_array("d", [float(v) for v in plan]), cloud.sh_degree, cloud.n_surfels, *ins, *outs, int(row0), int(out_rows))
-    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            rc = _entry("lara_splatxform_apply")(*args, _native.current_stream(dev))
-        _native.check(rc, "lara_splatxform_apply")
-    else:
-        _native.check(_entry("lara_splatxform_apply_host")(*args), "lara_splatxform_apply_host")
+    _native.call_on("lara_splatxform_apply", cloud.device, host_array("d", [float(v) for v in plan]), cloud.sh_degree, cloud.n_surfels,
+                    *ins, *outs, int(row0), int(out_rows))
 
 
 def _empty_like_rows(cloud, rows):

@@ -1,4 +1,4 @@
-"""The arithmetic of csrc/lara_batchfinish.h restated in numpy float32, independent of the C code: every operation is one numpy
+"""The arithmetic of include/lara_batchfinish.h restated in numpy float32, independent of the C code: every operation is one numpy
 float32 operation on float32 arrays (numpy rounds each once and contracts nothing), in the order the header writes.  The division is
 numpy's own correctly rounded float32 division, not the header's reciprocal-and-correction form.  Shared by tests/test_batchfinish.py,
 tests/test_batchfinish_gpu.py and tools/batchfinish_hostcheck.py."""

@@ -1,4 +1,4 @@
-"""The update of csrc/lara_splatadam.h restated in numpy float64: the same formula in the same operation order, each operation one
+"""The update of include/lara_splatadam.h restated in numpy float64: the same formula in the same operation order, each operation one
 correctly rounded IEEE operation on arrays, one rounding to float32 per store.  The plan is built here from the step, the betas, eps
 and the six rates, without the module."""
 import math

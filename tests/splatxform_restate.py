@@ -1,6 +1,6 @@
 """`lara_amd.splatxform` restated in numpy float64, independently of the module: the rasteriser's SH basis from its constants, the
 rotation blocks by a least-squares fit of their defining identity over seeded directions, the per-surfel arithmetic in the order
-lara_amd/csrc/lara_splatxform.h writes, ``transform_points``, ``with_sh_degree`` and the camera rule.  numpy's elementwise float64
+include/lara_splatxform.h writes, ``transform_points``, ``with_sh_degree`` and the camera rule.  numpy's elementwise float64
 products and sums are single IEEE operations (nothing is contracted), so the restated words are the header's."""
 import numpy as np
 

@@ -118,22 +118,23 @@ def test_signature_table_equals_the_headers():
     """Every function the headers declare has a row, every row a declaration, and they agree in the return type and, position by
     position, in the kind of every parameter (pointer / int32 / int64 / float)."""
     assert table_mismatches() == []             # (first: it names the function, the count below only counts)
-    assert len(header_functions()) == len(_native._SIGS) == 183
+    assert len(header_functions()) == len(_native._SIGS) == 189
 
 
 # how many functions each header declares: a function that moves between headers, or a header that appears or goes, shows here
 FUNCTIONS_PER_HEADER = {
-    "lara2dgs.h": 16, "lara_coarsedec.h": 3, "lara_depthsurface.h": 8, "lara_eval.h": 3, "lara_featvol.h": 3, "lara_finedec.h": 8,
-    "lara_groupattn.h": 20, "lara_loss.h": 6, "lara_lpips.h": 4, "lara_meshalign.h": 3, "lara_meshbvh.h": 6, "lara_meshclean.h": 6,
+    "lara2dgs.h": 16, "lara_batchfinish.h": 2, "lara_coarsedec.h": 3, "lara_depthsurface.h": 8, "lara_eval.h": 3, "lara_featvol.h": 3,
+    "lara_finedec.h": 8, "lara_groupattn.h": 20, "lara_loss.h": 6, "lara_lpips.h": 4, "lara_meshalign.h": 3, "lara_meshbvh.h": 6, "lara_meshclean.h": 6,
     "lara_meshdist.h": 7, "lara_meshio.h": 8, "lara_meshmetrics.h": 7, "lara_meshray.h": 6, "lara_meshrender.h": 3,
     "lara_meshsign.h": 6, "lara_meshsimplify.h": 12, "lara_meshtexture.h": 7, "lara_meshtopo.h": 12, "lara_meshwind.h": 6,
-    "lara_pointfeat.h": 7, "lara_rays.h": 1, "lara_surface.h": 6, "lara_tsdf.h": 4, "lara_vit.h": 5,
+    "lara_pointfeat.h": 7, "lara_rays.h": 1, "lara_splatadam.h": 2, "lara_splatxform.h": 2, "lara_surface.h": 6, "lara_tsdf.h": 4,
+    "lara_vit.h": 5,
 }
 
 
 def test_each_header_declares_its_pinned_number_of_functions():
     assert {hdr: len(fns) for hdr, fns in header_functions_by_file().items()} == FUNCTIONS_PER_HEADER
-    assert sum(FUNCTIONS_PER_HEADER.values()) == 183
+    assert sum(FUNCTIONS_PER_HEADER.values()) == 189
     assert [d for d in os.listdir(os.path.join(ROOT, "include")) if not d.endswith(".h")] == [], "include/ is flat"
 
 
@@ -144,7 +145,7 @@ def test_stream_flag_follows_the_prototype():
         for name, params in re.findall(r"\b(lara2dgs_\w+|lara_\w+)\s*\(([^()]*)\)\s*;", text):
             assert _native._SIGS[name][2] == bool(re.search(r"void\s*\*\s*stream\s*$", params)), name
             seen += 1
-    assert seen == 183
+    assert seen == 189
 
 
 def test_a_changed_prototype_fails_the_table_check(tmp_path):
@@ -246,6 +247,25 @@ def test_call_and_query_raise_with_the_called_functions_own_name(fake_library):
         _native.query("lara_ms_ssim_workspace_floats", 1, 3, 8, 8, error=ValueError("too small"))
     fake_library.rc = 4096
     assert _native.query("lara_point_feats_workspace_bytes", 4, 8, 8) == 4096
+
+
+def test_call_on_picks_the_device_entry_or_its_host_twin(fake_library):
+    import torch
+    t = torch.zeros(4)
+    cuda, args = torch.device("cuda", 0), (t, t, None, None, 1, 2, 3, 4, t, t, None)
+    # a GPU device: the entry itself, on that device, the stream appended
+    _native.call_on("lara_batch_finish", cuda, *args)
+    p = t.data_ptr()
+    assert fake_library.calls.pop() == ("lara_batch_finish", (p, p, None, None, 1, 2, 3, 4, p, p, None, 0x5EED))
+    assert fake_library.entered == [cuda]
+    # the host: `<name>_host`, no stream, no device entered
+    _native.call_on("lara_batch_finish", torch.device("cpu"), *args)
+    assert fake_library.calls.pop() == ("lara_batch_finish_host", (p, p, None, None, 1, 2, 3, 4, p, p, None))
+    assert fake_library.entered == [cuda] and fake_library.calls == []
+    # a failed call carries the name of the function that was called
+    fake_library.rc = -1
+    with pytest.raises(RuntimeError, match=r"lara_amd: lara_batch_finish_host failed: invalid argument"):
+        _native.call_on("lara_batch_finish", torch.device("cpu"), *args)
 
 
 def test_no_cpu_path_check():

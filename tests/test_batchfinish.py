@@ -307,7 +307,8 @@ def test_finish_images_refuses_by_the_arguments_name(hip_lib):
 
 
 def test_an_empty_batch_launches_nothing(hip_lib, monkeypatch):
-    monkeypatch.setattr(D, "_entry", lambda name: pytest.fail(f"{name} was looked up for an empty batch"))
+    for through in ("call_on", "call"):
+        monkeypatch.setattr(D._native, through, lambda name, *a: pytest.fail(f"{name} was called for an empty batch"))
     for shape in ((0, 8, 4, 4), (2, 0, 4, 4), (2, 8, 0, 4), (2, 8, 4, 0)):
         B, V, H, W = shape
         rgb, msk, nrm = D.finish_images(torch.zeros(*shape, 4, dtype=torch.uint8), torch.ones(B, V, 3),
@@ -321,7 +322,7 @@ def test_the_entry_points_refuse_bad_arguments(hip_lib):
             np.eye(3, dtype=np.float32)[None].copy(), np.zeros((B, V, H, W, 3), np.float32), np.zeros((B, V, H, W), np.uint8),
             np.zeros((B, H, V * W, 3), np.float32)]
     p = [b.ctypes.data for b in bufs]
-    host, dev = D._entry("lara_batch_finish_host"), D._entry("lara_batch_finish")
+    host, dev = hip_lib.lara_batch_finish_host, hip_lib.lara_batch_finish
     assert host(*p[:4], B, V, H, W, *p[4:]) == 0
     assert host(p[0], p[1], None, None, B, V, H, W, p[4], p[5], None) == 0             # the rgb-only form
     for fn, tail in ((host, ()), (dev, (None,))):          # (the device entry refuses before it touches a device)
@@ -341,22 +342,16 @@ def test_the_entry_points_refuse_bad_arguments(hip_lib):
         D._finish_into(torch.zeros(1, dtype=torch.uint8).expand(2 ** 16, 2 ** 15, 1, 1, 4), None, None, None, None, None, None)
 
 
-def test_the_modules_binding_equals_the_headers_prototypes(hip_lib, tmp_path):
-    """The header lies beside its unit and the module binds its two functions itself (tests/test_abi_cpu.py pins include/ and the
-    signature table): held to each other here as the table is held to include/ there -- the same parser, kind by kind."""
-    import shutil
+def test_the_modules_binding_equals_the_headers_prototypes(hip_lib):
+    """The header lies under include/ and its two functions are rows of ``_native.SIGNATURES`` (tests/test_abi_cpu.py holds the rows
+    to the prototypes, kind by kind): the library exports both, the stream is on the device entry alone, the unit is built with
+    -ffp-contract=off."""
     from lara_amd import _native
-    from tests.test_abi_cpu import _ctypes_kind, header_functions
-    shutil.copy(os.path.join(ROOT, "lara_amd", "csrc", "lara_batchfinish.h"), tmp_path / "lara_batchfinish.h")
-    declared = header_functions(str(tmp_path))
-    assert sorted(declared) == sorted(D.ENTRY_POINTS) == ["lara_batch_finish", "lara_batch_finish_host"]
-    for name, row in D.ENTRY_POINTS.items():
-        fn = D._entry(name)
-        assert hasattr(hip_lib, name)
-        kinds = [_ctypes_kind(t) for t in fn.argtypes]
-        assert (_ctypes_kind(fn.restype), kinds) == declared[name], name
-        assert (kinds[-1] == "p" and row.endswith(" s")) == (name == "lara_batch_finish")        # the stream, on the device entry alone
-    assert not set(D.ENTRY_POINTS) & set(_native._SIGS)
+    from tests.test_abi_cpu import header_functions_by_file
+    names = ["lara_batch_finish", "lara_batch_finish_host"]
+    assert sorted(header_functions_by_file()["lara_batchfinish.h"]) == names
+    assert set(names) <= set(_native._SIGS) and all(hasattr(hip_lib, n) for n in names)
+    assert [_native._SIGS[n][2] for n in names] == [True, False]                                  # the stream, on the device entry alone
     text = open(os.path.join(ROOT, "lara_amd", "csrc", "Makefile")).read()
     assert "FLAGS_batchfinish := -ffp-contract=off\n" in text and " batchfinish " in text.split("OBJS")[1].splitlines()[0]
 

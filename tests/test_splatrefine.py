@@ -265,7 +265,8 @@ def test_adam_step_refuses_what_the_kernel_cannot_take(hip_lib):
 
 def test_an_empty_cloud_launches_nothing(hip_lib, monkeypatch):
     from lara_amd import splatrefine as R
-    monkeypatch.setattr(R, "_entry", lambda name: pytest.fail(f"{name} was looked up for an empty cloud"))
+    for through in ("call_on", "call"):
+        monkeypatch.setattr(R._native, through, lambda name, *a: pytest.fail(f"{name} was called for an empty cloud"))
     for degree in C.DEGREES:
         counters = R.adam_step(*tensors(C.case(0, degree, moments=False)), R.plan(1), visible=torch.zeros(0, dtype=torch.uint8), zero_grads=True)
         assert int(counters) == 0
@@ -278,7 +279,7 @@ def test_the_entry_points_refuse_bad_arguments(hip_lib):
     p = [b.ctypes.data for b in bufs]
     row = (ctypes.c_double * 13)(*R.plan(1))
     count = np.zeros(1, np.int64)
-    host, dev = R._entry("lara_splatadam_step_host"), R._entry("lara_splatadam_step")
+    host, dev = hip_lib.lara_splatadam_step_host, hip_lib.lara_splatadam_step
     assert host(row, 1, 4, *p, None, 0, count.ctypes.data) == 0
     for fn, tail in ((host, ()), (dev, (None,))):          # (the device entry refuses before it touches a device)
         for k in range(20):
@@ -335,25 +336,19 @@ def test_surfel_adam_on_the_host_steps_counts_and_restores(hip_lib):
 
 # ------------------------------------------------------------------------------------------------------------------ the binding, the build
 
-def test_the_modules_binding_equals_the_headers_prototypes(hip_lib, tmp_path):
-    """The header lies beside its unit and the module binds its two functions itself (tests/test_abi_cpu.py pins include/ and the
-    signature table): held to each other here as the table is held to include/ there -- the same parser, kind by kind."""
-    import shutil
+def test_the_modules_binding_equals_the_headers_prototypes(hip_lib):
+    """The header lies under include/ and its two functions are rows of ``_native.SIGNATURES`` (tests/test_abi_cpu.py holds the rows
+    to the prototypes, kind by kind): the library exports both, the stream is on the device entry alone, the unit is built with
+    -ffp-contract=off, and the header's plan and span are the module's."""
     from lara_amd import _native, splatrefine as R
-    from tests.test_abi_cpu import _ctypes_kind, header_functions
-    shutil.copy(os.path.join(ROOT, "lara_amd", "csrc", "lara_splatadam.h"), tmp_path / "lara_splatadam.h")
-    declared = header_functions(str(tmp_path))
-    assert sorted(declared) == sorted(R.ENTRY_POINTS) == ["lara_splatadam_step", "lara_splatadam_step_host"]
-    for name, row in R.ENTRY_POINTS.items():
-        fn = R._entry(name)
-        assert hasattr(hip_lib, name)
-        kinds = [_ctypes_kind(t) for t in fn.argtypes]
-        assert (_ctypes_kind(fn.restype), kinds) == declared[name], name
-        assert row.endswith(" s") == (name == "lara_splatadam_step")                   # the stream, on the device entry alone
-    assert not set(R.ENTRY_POINTS) & set(_native._SIGS)
+    from tests.test_abi_cpu import header_functions_by_file
+    names = ["lara_splatadam_step", "lara_splatadam_step_host"]
+    assert sorted(header_functions_by_file()["lara_splatadam.h"]) == names
+    assert set(names) <= set(_native._SIGS) and all(hasattr(hip_lib, n) for n in names)
+    assert [_native._SIGS[n][2] for n in names] == [True, False]                       # the stream, on the device entry alone
     text = open(os.path.join(ROOT, "lara_amd", "csrc", "Makefile")).read()
     assert "FLAGS_splatadam := -ffp-contract=off\n" in text and " splatadam" in text.split("OBJS")[1].splitlines()[0]
-    header = open(os.path.join(ROOT, "lara_amd", "csrc", "lara_splatadam.h")).read()
+    header = open(os.path.join(ROOT, "include", "lara_splatadam.h")).read()
     assert f"#define LARA_SPLATADAM_PLAN {R.PLAN}\n" in header and f"#define LARA_SPLATADAM_SPAN {R.SPAN}\n" in header
 
 

@@ -183,23 +183,20 @@ def test_partial_overlap_and_mismatched_outputs_are_refused(hip_lib):
         X.transform(c, C.RIGID, out=strided)
 
 
-def test_the_modules_binding_equals_the_headers_prototypes(hip_lib, tmp_path):
-    """The header lies beside its unit and the module binds its two functions itself (tests/test_abi_cpu.py pins include/ and the
-    signature table): held to each other here as the table is held to include/ there -- the same parser, kind by kind -- and the
-    library exports both symbols."""
-    import shutil
+def test_the_modules_binding_equals_the_headers_prototypes(hip_lib):
+    """The header lies under include/ and its two functions are rows of ``_native.SIGNATURES`` (tests/test_abi_cpu.py holds the rows
+    to the prototypes, kind by kind): the library exports both, the stream is on the device entry alone, the unit is built with
+    -ffp-contract=off, and the header's plan and span are the module's."""
     from lara_amd import _native
-    from tests.test_abi_cpu import _ctypes_kind, header_functions
-    shutil.copy(os.path.join(ROOT, "lara_amd", "csrc", "lara_splatxform.h"), tmp_path / "lara_splatxform.h")
-    declared = header_functions(str(tmp_path))
-    assert sorted(declared) == sorted(X.ENTRY_POINTS) == ["lara_splatxform_apply", "lara_splatxform_apply_host"]
-    for name, row in X.ENTRY_POINTS.items():
-        fn = X._entry(name)
-        assert hasattr(hip_lib, name)
-        kinds = [_ctypes_kind(t) for t in fn.argtypes]
-        assert (_ctypes_kind(fn.restype), kinds) == declared[name], name
-        assert (kinds[-1] == "p" and row.endswith(" s")) == name.endswith("_apply")          # the stream, on the device entry alone
-    assert not set(X.ENTRY_POINTS) & set(_native._SIGS)
+    from tests.test_abi_cpu import header_functions_by_file
+    names = ["lara_splatxform_apply", "lara_splatxform_apply_host"]
+    assert sorted(header_functions_by_file()["lara_splatxform.h"]) == names
+    assert set(names) <= set(_native._SIGS) and all(hasattr(hip_lib, n) for n in names)
+    assert [_native._SIGS[n][2] for n in names] == [True, False]                              # the stream, on the device entry alone
+    text = open(os.path.join(ROOT, "lara_amd", "csrc", "Makefile")).read()
+    assert "FLAGS_splatxform := -ffp-contract=off\n" in text and " splatxform " in text.split("OBJS")[1].splitlines()[0]
+    header = open(os.path.join(ROOT, "include", "lara_splatxform.h")).read()
+    assert f"#define LARA_SPLATXFORM_PLAN {X.PLAN}\n" in header and f"#define LARA_SPLATXFORM_SPAN {X.SPAN}\n" in header
 
 
 def test_the_entry_points_refuse_bad_arguments(hip_lib):
@@ -207,7 +204,7 @@ def test_the_entry_points_refuse_bad_arguments(hip_lib):
     c = C.cloud(4, 1)
     bufs = [np.ascontiguousarray(c[k]) for k in C.FIELDS] + [np.zeros_like(c[k]) for k in C.FIELDS]
     ptrs = [b.ctypes.data for b in bufs]
-    host, dev = X._entry("lara_splatxform_apply_host"), X._entry("lara_splatxform_apply")
+    host, dev = hip_lib.lara_splatxform_apply_host, hip_lib.lara_splatxform_apply
     assert host(plan, 1, 4, *ptrs, 0, 4) == 0
     for fn, tail in ((host, ()), (dev, (None,))):          # (the device entry refuses before it touches a device)
         assert fn(None, 1, 4, *ptrs, 0, 4, *tail) == -1

@@ -4,14 +4,12 @@ the rgb-only form) and the exhaustive (colour, alpha) plane: writes each case's 
 a temporary file, compiles tools/batchfinish_hostcheck.cpp with -fsanitize=address,undefined -ffp-contract=off, runs it, and prints
 (``--out``: also appends) the outcome.  CPU only: nothing is loaded into python's process but numpy, and no device is touched.
     python tools/batchfinish_hostcheck.py [--cxx g++] [--out FILE]"""
-import argparse
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,28 +38,10 @@ def _records():
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cxx", default=shutil.which("g++") or shutil.which("clang++") or "c++")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
     records = list(_records())
-    with tempfile.TemporaryDirectory() as tmp:
-        data, exe = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "batchfinish_hostcheck")
-        with open(data, "wb") as f:
-            f.write(np.int64(len(records)).tobytes())
-            for r in records:
-                f.write(r)
-        flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-        subprocess.check_call([a.cxx] + flags + [os.path.join(ROOT, "tools", "batchfinish_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe, data], capture_output=True, text=True)
-    lines = [f"tools/batchfinish_hostcheck.py: batchfinish_ops.h, stand-alone host program, {os.path.basename(a.cxx)} "
-             f"-fsanitize=address,undefined, {len(records)} cases of tests/batchfinish_cases.py and the (colour, alpha) plane",
-             run.stdout.strip(), f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    return hostcheck.run(__file__, "batchfinish_ops.h, stand-alone host program, {cxx} -fsanitize=address,undefined, "
+                         f"{len(records)} cases of tests/batchfinish_cases.py and the (colour, alpha) plane",
+                         np.int64(len(records)).tobytes() + b"".join(records))
 
 
 if __name__ == "__main__":

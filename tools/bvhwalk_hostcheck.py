@@ -5,36 +5,15 @@ header that holds the layout is HIP source, so the compiler is hipcc, for the ho
 with -fsanitize=address,undefined, runs it, and prints (``--out``: also appends) the outcome.  CPU only: nothing is loaded into
 python and no device is touched.
     python tools/bvhwalk_hostcheck.py [--hipcc /opt/rocm/bin/hipcc] [--out profiles/bvhwalk_parity.txt]"""
-import argparse
-import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import hostcheck
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--hipcc", default=shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "bvhwalk_hostcheck")
-        flags = ["-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
-                 "-fno-sanitize-recover=all", "-Wno-unused-function"]
-        subprocess.check_call([a.hipcc] + flags + [os.path.join(ROOT, "tools", "bvhwalk_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe], capture_output=True, text=True)
-    rows = run.stdout.strip().splitlines()
-    lines = [f"tools/bvhwalk_hostcheck.py: lara_bvhwalk of bvhwalk.h over mb_layout(T), stand-alone host program, "
-             f"{os.path.basename(a.hipcc)} --cuda-host-only -fsanitize=address,undefined"] + rows[-1:] + \
-            [f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(rows[:-1] + lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    return hostcheck.run(__file__, "lara_bvhwalk of bvhwalk.h over mb_layout(T), stand-alone host program, "
+                         "{cxx} --cuda-host-only -fsanitize=address,undefined", compiler="hipcc",
+                         flags=["-x", "hip", "--cuda-host-only", "-Wno-unused-function"], rows_first=True)
 
 
 if __name__ == "__main__":

@@ -145,7 +145,7 @@ def windowed(fn):
 
 
 def torch_finish(rgba, bg, n_u8, rot):
-    """The arithmetic of csrc/lara_batchfinish.h in torch operators on the device (fp32; the matmul sums in torch's order)."""
+    """The arithmetic of include/lara_batchfinish.h in torch operators on the device (fp32; the matmul sums in torch's order)."""
     f = rgba.float() / 255.0
     a = f[..., 3:4]
     rgb = f[..., :3] * a + bg[:, :, None, None, :] * (1.0 - a)

@@ -5,14 +5,12 @@ restatement's answers to a temporary file, compiles tools/meshsign_hostcheck.cpp
 -ffp-contract=off, runs it, and prints (``--out``: also appends) the outcome.  CPU only: nothing is loaded into python and no device
 is touched.
     python tools/meshsign_hostcheck.py [--cxx g++] [--out profiles/meshsign_parity.txt]"""
-import argparse
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,10 +26,6 @@ def _records(o, d, tri):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cxx", default=shutil.which("g++") or shutil.which("clang++") or "c++")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
     groups = MC.bound_groups()
     rows = [_records(o, d, tri) for o, d, _, _, tri, _, _ in groups.values()]
     V, F = SC.cube()
@@ -42,23 +36,9 @@ def main():
         rows.append(_records(o, np.broadcast_to(S.DIRECTIONS[k], o.shape).astype(np.float32), np.tile(tri, (len(P), 1, 1))))
         crafted += len(P)
     rows = np.concatenate(rows)
-    with tempfile.TemporaryDirectory() as tmp:
-        data, exe = os.path.join(tmp, "records.bin"), os.path.join(tmp, "meshsign_hostcheck")
-        with open(data, "wb") as f:
-            f.write(np.int64(len(rows)).tobytes())
-            f.write(np.ascontiguousarray(rows).tobytes())
-        flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-        subprocess.check_call([a.cxx] + flags + [os.path.join(ROOT, "tools", "meshsign_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe, data], capture_output=True, text=True)
-    lines = [f"tools/meshsign_hostcheck.py: raycross.h on raytri.h, stand-alone host program, {os.path.basename(a.cxx)} "
-             f"-fsanitize=address,undefined, {len(groups)} groups of tests/meshray_cases.bound_groups and {crafted} crafted rays x "
-             f"{len(tri)} triangles of the cube",
-             run.stdout.strip(), f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    return hostcheck.run(__file__, "raycross.h on raytri.h, stand-alone host program, {cxx} -fsanitize=address,undefined, "
+                         f"{len(groups)} groups of tests/meshray_cases.bound_groups and {crafted} crafted rays x {len(tri)} triangles of the cube",
+                         np.int64(len(rows)).tobytes() + np.ascontiguousarray(rows).tobytes())
 
 
 if __name__ == "__main__":

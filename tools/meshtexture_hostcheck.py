@@ -5,14 +5,13 @@ answers (tests/meshtexture_restate.py) to a temporary file, compiles tools/mesht
 -ffp-contract=off, runs it, and prints (``--out``: also appends) the outcome: every output must equal the restatement's bytes.  CPU
 only: nothing is loaded into python and no device is touched.
     python tools/meshtexture_hostcheck.py [--cxx g++] [--out profiles/meshtexture_parity.txt]"""
-import argparse
+import io
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,47 +25,32 @@ def block(f, a, dtype):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cxx", default=shutil.which("g++") or shutil.which("clang++") or "c++")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        data, exe = os.path.join(tmp, "records.bin"), os.path.join(tmp, "meshtexture_hostcheck")
-        with open(data, "wb") as f:
-            f.write(np.int64(len(TC.KEYS)).tobytes())
-            for key in TC.KEYS:
-                c = TC.case(key)
-                L, T = c["layout"], len(c["F"])
-                nv, H, W = c["images"].shape[:3]
-                block(f, [L[0], L[1], T, len(c["V"]), nv, H, W], np.int32)
-                for name, dtype in (("V", np.float32), ("F", np.int32), ("images", np.float32), ("k", np.float32), ("w2c", np.float32),
-                                    ("eyes", np.float32), ("colours", np.float32), ("mask", np.int64)):
-                    block(f, c[name], dtype)
-                face, point, anchor = X.texels(L, c["V"], c["F"])
-                block(f, face, np.int32), block(f, point, np.float32), block(f, anchor, np.float32)
-                block(f, [len(TC.VARIANTS)], np.int32)
-                for name, kw in TC.VARIANTS:
-                    fill = kw.get("fill", (0, 0, 0))
-                    block(f, [kw.get("near", 0.0), kw.get("min_cos", 0.1), kw.get("power", 2), kw.get("two_sided", False), kw["blend"] == "best",
-                              kw.get("mask", False), kw.get("colours", False), fill[0], fill[1], fill[2]], np.float32)
-                    texture, weight, view = TC.restated(key, name)
-                    block(f, texture, np.uint8), block(f, weight, np.float32), block(f, view, np.int32)
-                g = np.random.default_rng(11)
-                bary = np.concatenate([TC.dense_bary(12), (g.random((200, 3)) * 1.4 - 0.2).astype(np.float32), np.array([[np.nan, np.nan, 0.5]], np.float32)])
-                sf = g.integers(-1, T + 2, len(bary)).astype(np.int32)
-                block(f, sf, np.int32), block(f, bary, np.float32)
-                block(f, X.sample(L, T, texture, sf, bary, True, (0.1, 0.2, 0.3)), np.float32)
-        flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-        subprocess.check_call([a.cxx] + flags + [os.path.join(ROOT, "tools", "meshtexture_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe, data], capture_output=True, text=True)
-    lines = [f"tools/meshtexture_hostcheck.py: texatlas.h, stand-alone host program, {os.path.basename(a.cxx)} -fsanitize=address,undefined, "
-             f"{len(TC.KEYS)} cases x {len(TC.VARIANTS)} bake variants",
-             run.stdout.strip(), f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    f = io.BytesIO()
+    f.write(np.int64(len(TC.KEYS)).tobytes())
+    for key in TC.KEYS:
+        c = TC.case(key)
+        L, T = c["layout"], len(c["F"])
+        nv, H, W = c["images"].shape[:3]
+        block(f, [L[0], L[1], T, len(c["V"]), nv, H, W], np.int32)
+        for name, dtype in (("V", np.float32), ("F", np.int32), ("images", np.float32), ("k", np.float32), ("w2c", np.float32),
+                            ("eyes", np.float32), ("colours", np.float32), ("mask", np.int64)):
+            block(f, c[name], dtype)
+        face, point, anchor = X.texels(L, c["V"], c["F"])
+        block(f, face, np.int32), block(f, point, np.float32), block(f, anchor, np.float32)
+        block(f, [len(TC.VARIANTS)], np.int32)
+        for name, kw in TC.VARIANTS:
+            fill = kw.get("fill", (0, 0, 0))
+            block(f, [kw.get("near", 0.0), kw.get("min_cos", 0.1), kw.get("power", 2), kw.get("two_sided", False), kw["blend"] == "best",
+                      kw.get("mask", False), kw.get("colours", False), fill[0], fill[1], fill[2]], np.float32)
+            texture, weight, view = TC.restated(key, name)
+            block(f, texture, np.uint8), block(f, weight, np.float32), block(f, view, np.int32)
+        g = np.random.default_rng(11)
+        bary = np.concatenate([TC.dense_bary(12), (g.random((200, 3)) * 1.4 - 0.2).astype(np.float32), np.array([[np.nan, np.nan, 0.5]], np.float32)])
+        sf = g.integers(-1, T + 2, len(bary)).astype(np.int32)
+        block(f, sf, np.int32), block(f, bary, np.float32)
+        block(f, X.sample(L, T, texture, sf, bary, True, (0.1, 0.2, 0.3)), np.float32)
+    return hostcheck.run(__file__, "texatlas.h, stand-alone host program, {cxx} -fsanitize=address,undefined, "
+                         f"{len(TC.KEYS)} cases x {len(TC.VARIANTS)} bake variants", f.getvalue())
 
 
 if __name__ == "__main__":

@@ -4,14 +4,12 @@ for both weightings with their zero counts, one smoothing pass with lam and with
 temporary file, compiles tools/meshtopo_hostcheck.cpp with -fsanitize=address,undefined -ffp-contract=off, runs it, and prints
 (``--out``: also appends) the outcome.  CPU only: nothing is loaded into python and no device is touched.
     python tools/meshtopo_hostcheck.py [--cxx g++] [--out profiles/meshtopo_parity.txt]"""
-import argparse
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,27 +35,9 @@ def _record(key):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cxx", default=shutil.which("g++") or shutil.which("clang++") or "c++")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        data, exe = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "meshtopo_hostcheck")
-        with open(data, "wb") as f:
-            f.write(np.int64(len(C.CASES)).tobytes())
-            for key in C.CASES:
-                f.write(_record(key))
-        flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-        subprocess.check_call([a.cxx] + flags + [os.path.join(ROOT, "tools", "meshtopo_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe, data], capture_output=True, text=True)
-    lines = [f"tools/meshtopo_hostcheck.py: meshtopo_ops.h, stand-alone host program, {os.path.basename(a.cxx)} "
-             f"-fsanitize=address,undefined, the {len(C.CASES)} cases of tests/meshtopo_cases.py",
-             run.stdout.strip(), f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    return hostcheck.run(__file__, "meshtopo_ops.h, stand-alone host program, {cxx} -fsanitize=address,undefined, "
+                         f"the {len(C.CASES)} cases of tests/meshtopo_cases.py",
+                         np.int64(len(C.CASES)).tobytes() + b"".join(_record(key) for key in C.CASES))
 
 
 if __name__ == "__main__":

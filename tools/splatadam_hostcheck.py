@@ -5,14 +5,12 @@ restatement's answers to a temporary file, compiles tools/splatadam_hostcheck.cp
 -ffp-contract=off, runs it, and prints (``--out``: also appends) the outcome.  CPU only: nothing is loaded into python's process but
 numpy, and no device is touched.
     python tools/splatadam_hostcheck.py [--cxx g++] [--out profiles/splatrefine_parity.txt]"""
-import argparse
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
+
+import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,28 +33,9 @@ def _records():
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cxx", default=shutil.which("g++") or shutil.which("clang++") or "c++")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
     records = list(_records())
-    with tempfile.TemporaryDirectory() as tmp:
-        data, exe = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "splatadam_hostcheck")
-        with open(data, "wb") as f:
-            f.write(np.int64(len(records)).tobytes())
-            for r in records:
-                f.write(r)
-        flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-        subprocess.check_call([a.cxx] + flags + [os.path.join(ROOT, "tools", "splatadam_hostcheck.cpp"), "-o", exe])
-        run = subprocess.run([exe, data], capture_output=True, text=True)
-    lines = [f"tools/splatadam_hostcheck.py: splatadam_ops.h, stand-alone host program, {os.path.basename(a.cxx)} "
-             f"-fsanitize=address,undefined, {len(records)} cases of tests/splatrefine_cases.py",
-             run.stdout.strip(), f"exit code {run.returncode}; sanitizer reports: {'none' if not run.stderr.strip() else run.stderr.strip()}"]
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    return run.returncode
+    return hostcheck.run(__file__, "splatadam_ops.h, stand-alone host program, {cxx} -fsanitize=address,undefined, "
+                         f"{len(records)} cases of tests/splatrefine_cases.py", np.int64(len(records)).tobytes() + b"".join(records))
 
 
 if __name__ == "__main__":
