@@ -280,7 +280,8 @@ class Renderer(nn.Module):
                 f"depth_normal{prex}": dnorm, f"rend_dist{prex}": rdist}
 
     def render_views(self, cams, rays, centers, shs, opacity, scales, rotations, device, bg_colors=None,
-                     cov3D_precomp=None, prex='', depth_ratio=0.0, concat=False, into=None, raster_out=None, subset_of=None):
+                     cov3D_precomp=None, prex='', depth_ratio=0.0, concat=False, into=None, raster_out=None, subset_of=None,
+                     means2D=None):
         """All views of a scene in ONE rasteriser call (one autograd node, per-camera state carved from one
         allocation, gradients summed over the views inside the library): what the reference's inner loop
         (lightning/network.py:486-497 coarse, :516-525 fine) does with one ``render_img`` per view.  ``cams`` is a
@@ -291,7 +292,8 @@ class Renderer(nn.Module):
         written by one post-processing launch for all views -- into the caller's buffers when ``into`` ({key+prex: [H, n*W, C]})
         is given.  ``raster_out`` (a list) receives the rasteriser's own (color, radii, allmap); ``subset_of = (color, idx)`` names
         an earlier call's colour output and this call's rows in it (`rasterize_gaussians_views`: the fine pass filters the coarse
-        pass's lists instead of binning again)."""
+        pass's lists instead of binning again).  ``means2D`` ([P,3], requires grad) goes to the rasteriser in place of the shared
+        zero constant, and receives the screen-space gradient summed over the views (`lara_amd.splatdensify`'s statistic)."""
         n = len(cams)
         if torch.is_tensor(bg_colors) and bg_colors.dim() == 2 and not (
                 bg_colors.dtype == torch.float32 and bg_colors.stride() == (4, 1) and bg_colors.data_ptr() % 16 == 0):
@@ -299,7 +301,7 @@ class Renderer(nn.Module):
         bgs = [None] * n if bg_colors is None else list(bg_colors)
         settings = [self._settings(cam, device=device, bg=bg) for cam, bg in zip(cams, bgs)]
         opacity, scales, rotations = self._activated(opacity, scales, rotations)
-        color, radii, allmap = rasterize_gaussians_views(settings, centers, self._zero_means2D(centers), opacity, shs=shs,
+        color, radii, allmap = rasterize_gaussians_views(settings, centers, self._zero_means2D(centers) if means2D is None else means2D, opacity, shs=shs,
                                                          scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
                                                          subset_of=subset_of, tight_tiles=self.tight_tiles)
         if raster_out is not None:

@@ -25,7 +25,10 @@ The trap: the kernel writes through ``data_ptr()``, which does not advance torch
 reuses its cached sigmoid / exp / normalize while address and version are unchanged.  ``SurfelAdam.step`` bumps the version of every
 parameter; a caller of ``adam_step`` on tensors a renderer has seen calls ``bump_version`` (or ``invalidate_activations``) itself.
 
-Out of scope: densification (clone, split, opacity reset), per-surfel step counts (one ``t`` for the cloud: a surfel first seen at
+Densification (clone, split, prune, opacity reset) is ``lara_amd.splatdensify``: ``refine(..., densify=DensifySchedule(...))``,
+``SurfelAdam.densify`` and ``SurfelAdam.reset_opacity`` import it when they are used, nothing else here does.
+
+Out of scope: per-surfel step counts (one ``t`` for the cloud: a surfel first seen at
 step 50 is bias-corrected as at step 50), weight decay, learning-rate schedules (beyond an ``lrs`` the caller may change between
 steps), gradients through ``splatxform``, camera refinement.
 """
@@ -218,6 +221,23 @@ class SurfelAdam:
         self.steps = int(state["steps"])
         self.lrs, self.betas, self.eps, self.sparse = dict(state["lrs"]), tuple(state["betas"]), float(state["eps"]), bool(state["sparse"])
 
+    def densify(self, stats, plan, noise=None, seed=0, max_surfels=None):
+        """One round of ``splatdensify.densify`` on this optimiser's cloud: the leaf tensors and the moments are REPLACED by the new
+        ones (another row count; kept rows carry their moments, clones and split children start from zero), ``steps`` stays, the
+        gradients are gone.  Returns the round's report.  ``stats`` no longer fits afterwards: ``stats.reset(report["P_out"])``."""
+        from . import splatdensify
+        p, m, v, report = splatdensify.densify([t.detach() for t in self._params], self.exp_avg, self.exp_avg_sq, stats, plan, noise=noise,
+                                               seed=seed, max_surfels=max_surfels)
+        self._params = [t.requires_grad_(True) for t in p]
+        self.exp_avg, self.exp_avg_sq = m, v
+        bump_version(self._params)
+        return report
+
+    def reset_opacity(self, ceiling=0.01):
+        """``splatdensify.reset_opacity`` on this optimiser's opacity and its two moments, in place."""
+        from . import splatdensify
+        splatdensify.reset_opacity(self._params, self.exp_avg, self.exp_avg_sq, ceiling=ceiling)
+
 
 # ---------------------------------------------------------------------------------------------------------- the loop
 
@@ -231,7 +251,7 @@ def _default_loss(batch, output, it):
 
 
 def refine(cloud, cams, rays, targets, *, steps, lrs=None, sparse=True, bg_colors=None, renderer=None, regularise_after=None, loss_fn=None,
-           views_per_step=None, seed=0, callback=None):
+           views_per_step=None, seed=0, callback=None, densify=None):
     """``steps`` optimisation steps of ``cloud`` against ``targets`` [V,H,W,3] (fp32 in 0..1, on the cloud's device) seen from
     ``cams`` (``cameras.make_cameras``) with ``rays`` [V,H,W,6] (``batch.build_rays``).  Returns (the refined ``SurfelCloud``,
     history).  Per step: ``render_views(..., concat=True, raster_out=...)``, the loss, ``backward``, ``visible = (radii > 0).any(0)``
@@ -243,7 +263,14 @@ def refine(cloud, cams, rays, targets, *, steps, lrs=None, sparse=True, bg_color
     (below, the five-scale pyramid is undefined).  ``views_per_step``: that many views drawn per step (a host generator seeded with
     ``seed``; None: all).  ``bg_colors``: [V,3] per-view backgrounds.  ``callback(step, optimiser, loss)`` after every step.
     ``history``: ``loss`` and ``mse`` [steps] as device tensors (read them once, at the end), ``skipped`` (the non-finite counter),
-    ``steps``, and ``optimiser`` (the ``SurfelAdam``, for its ``state()``)."""
+    ``steps``, and ``optimiser`` (the ``SurfelAdam``, for its ``state()``).
+
+    ``densify``: a ``splatdensify.DensifySchedule`` (None: the loop above, exactly).  With one, every render gets a ``means2D`` that
+    requires grad, ``splatdensify.DensifyStats.accumulate`` runs after each backward on its gradient and the radii (per render call,
+    not per view: ``views_per_step=1`` gives 3DGS's statistic), and after the update of the steps the schedule names the cloud is
+    densified (``SurfelAdam.densify``) -- the statistics start again at the new surfel count -- or its opacity reset.
+    ``history["densify"]`` gets one entry per round: ``step`` (1-based), ``counts`` (kept, cloned, split parents, pruned, P_out as an
+    int64 device tensor), ``row_source`` and ``capped``.  The one host read a round needs is the allocation's."""
     from .renderer import Renderer
     dev = cloud.device
     _native.require_device(dev)
@@ -263,7 +290,16 @@ def refine(cloud, cams, rays, targets, *, steps, lrs=None, sparse=True, bg_color
     draw = torch.Generator().manual_seed(int(seed))
     history = {"loss": torch.zeros(int(steps), dtype=torch.float32, device=dev), "mse": torch.zeros(int(steps), dtype=torch.float32, device=dev),
                "skipped": opt.skipped, "steps": int(steps), "optimiser": opt}
+    stats = means2D = None
+    if densify is not None:
+        from . import splatdensify
+        if not isinstance(densify, splatdensify.DensifySchedule):
+            raise ValueError(f"{_WHO}: densify is a splatdensify.DensifySchedule, got {type(densify).__name__}")
+        stats = splatdensify.DensifyStats(cloud.n_surfels, dev)
+        history["densify"] = []
     for k in range(int(steps)):
+        if stats is not None:
+            means2D = torch.zeros_like(opt.params()[0], requires_grad=True)
         if n_step == V:
             v_cams, v_rays, v_tar, v_bg = list(cams), rays, targets, bg_colors
         else:
@@ -271,15 +307,25 @@ def refine(cloud, cams, rays, targets, *, steps, lrs=None, sparse=True, bg_color
             v_cams, v_rays, v_tar = [cams[i] for i in idx], rays[idx], targets[idx]
             v_bg = None if bg_colors is None else bg_colors[idx]
         raster_out = []
-        out = renderer.render_views(v_cams, v_rays, *opt.params(), dev, bg_colors=v_bg, concat=True, raster_out=raster_out)
+        out = renderer.render_views(v_cams, v_rays, *opt.params(), dev, bg_colors=v_bg, concat=True, raster_out=raster_out, means2D=means2D)
         output = {name: m[None] for name, m in out.items()}
         it = 10000 if regularise_after is not None and k >= int(regularise_after) else 0      # (loss.py:47 switches at it > 1000)
-        loss, stats = loss_fn({"tar_rgb": v_tar[None]}, output, it)
+        loss, terms = loss_fn({"tar_rgb": v_tar[None]}, output, it)
         loss.backward()
         visible = (raster_out[0][1] > 0).any(0) if sparse else None
+        if stats is not None:
+            stats.accumulate(means2D.grad, raster_out[0][1])
         opt.step(visible, zero_grads=True)
         history["loss"][k] = loss.detach()
-        history["mse"][k] = stats["mse"]
+        history["mse"][k] = terms["mse"]
+        if stats is not None and densify.fires(k + 1):
+            report = opt.densify(stats, densify.plan(), seed=int(densify.seed) + k, max_surfels=densify.max_surfels)
+            if report["P_out"] == 0:
+                raise RuntimeError(f"{_WHO}: the densification round of step {k + 1} pruned every surfel")
+            stats.reset(report["P_out"])
+            history["densify"].append({"step": k + 1, "counts": report["counts"], "row_source": report["row_source"], "capped": report["capped"]})
+        if stats is not None and densify.resets(k + 1):
+            opt.reset_opacity()
         if callback is not None:
             callback(k, opt, loss.detach())
     return opt.cloud(), history

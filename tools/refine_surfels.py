@@ -9,6 +9,11 @@ says so).
 ``--lr KEY=VALUE`` (repeatable; KEY one of centers, sh0, sh_rest, opacity, scales, rotations) replaces a default learning rate;
 ``--dense`` updates every surfel in every step; ``--regularise-after N`` switches the distortion and normal terms on after N steps.
 ``--quick``: at most 10 steps (what tests/test_splatrefine_gpu.py runs).
+``--densify-from N`` switches densification on (`lara_amd.splatdensify`: clone, split, prune between steps, from step N every
+``--densify-interval`` steps until ``--densify-until``); ``--densify-grad-threshold``, ``--densify-percent-dense``,
+``--densify-extent`` (the scene's radius), ``--densify-min-opacity``, ``--densify-max-screen-radius``,
+``--densify-opacity-reset-interval``, ``--densify-n-split``, ``--densify-max-surfels`` and ``--densify-seed`` are the fields of
+`splatdensify.DensifySchedule`; the JSON then lists every round's counts.
     python tools/refine_surfels.py scene.ply views.npz --steps 30 --out refined.ply [--json refined.json] [--quick]"""
 import argparse
 import json
@@ -66,6 +71,18 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--regularise-after", type=int, default=None)
     ap.add_argument("--quick", action="store_true", help="at most 10 steps")
+    ap.add_argument("--densify-from", type=int, default=None, help="densify from this step on (default: never)")
+    ap.add_argument("--densify-until", type=int, default=10 ** 9)
+    ap.add_argument("--densify-interval", type=int, default=100)
+    ap.add_argument("--densify-grad-threshold", type=float, default=2e-4)
+    ap.add_argument("--densify-percent-dense", type=float, default=0.01)
+    ap.add_argument("--densify-extent", type=float, default=1.0)
+    ap.add_argument("--densify-min-opacity", type=float, default=0.005)
+    ap.add_argument("--densify-max-screen-radius", type=float, default=0.0)
+    ap.add_argument("--densify-opacity-reset-interval", type=int, default=0)
+    ap.add_argument("--densify-n-split", type=int, default=2)
+    ap.add_argument("--densify-max-surfels", type=int, default=None)
+    ap.add_argument("--densify-seed", type=int, default=0)
     args = ap.parse_args()
     if args.quick:
         args.steps = min(args.steps, 10)
@@ -82,6 +99,16 @@ def main():
             sys.exit(f"tools/refine_surfels.py: --lr takes KEY=VALUE with KEY in {splatrefine.LR_KEYS}, got {item!r}")
         lrs[key] = float(value)
 
+    schedule = None
+    if args.densify_from is not None:
+        from lara_amd import splatdensify
+        schedule = splatdensify.DensifySchedule(
+            from_step=args.densify_from, until_step=args.densify_until, interval=args.densify_interval,
+            grad_threshold=args.densify_grad_threshold, percent_dense=args.densify_percent_dense, extent=args.densify_extent,
+            min_opacity=args.densify_min_opacity, max_screen_radius=args.densify_max_screen_radius,
+            opacity_reset_interval=args.densify_opacity_reset_interval, n_split=args.densify_n_split, max_surfels=args.densify_max_surfels,
+            seed=args.densify_seed)
+
     dev = torch.device("cuda", 0)
     cloud, info = splatio.read_ply(args.ply, device=dev)
     targets, cams, rays = load_views(args.views, dev)
@@ -90,7 +117,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     refined, history = splatrefine.refine(cloud, cams, rays, targets, steps=args.steps, lrs=lrs, sparse=not args.dense, renderer=renderer,
-                                          regularise_after=args.regularise_after)
+                                          regularise_after=args.regularise_after, densify=schedule)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     after = evaluate(renderer, refined, cams, rays, targets)
@@ -105,6 +132,10 @@ def main():
            "loss_per_step": history["loss"].cpu().tolist(), "non_finite_gradient_words_skipped": int(history["skipped"].item()),
            "dropped_third_scale": info["dropped_third_scale"], "wall_s": wall,
            "wall_note": "the loop's wall time from ONE run, first-launch costs included; no spread was measured"}
+    if schedule is not None:
+        from lara_amd.splatdensify import COUNT_KEYS
+        res["n_surfels_after"] = refined.n_surfels
+        res["densify_rounds"] = [dict(zip(COUNT_KEYS, r["counts"].tolist()), step=r["step"], capped=r["capped"]) for r in history["densify"]]
     with open(args.json or os.path.splitext(args.out)[0] + ".json", "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({k: v for k, v in res.items() if k != "loss_per_step"}))
