@@ -3,8 +3,7 @@
  * where the screen-space gradient is high, prune the transparent and the oversized, and carry the Adam moments with the rows that
  * survive (part of liblara2dgs.so; opt-in, python side: lara_amd/splatdensify.py; kernels: csrc/splatdensify.hip; the per-row functions,
  * for the device and the host: csrc/splatdensify_ops.h).  Returns 0 or a negative LARA2DGS_E_* code.  Built with -ffp-contract=off: the
- * sequences written here are the instructions.  This header lies beside its unit and lara_amd/splatdensify.py binds its functions
- * itself: tests/test_abi_cpu.py pins the headers under include/ and the rows of _native.SIGNATURES to a fixed number of functions.
+ * sequences written here are the instructions.
  *
  * The rules are those of 3DGS's / 2DGS's densify_and_prune as recalled [RECALLED: neither code base is in the build image; nothing pins
  * them], with ONE deliberate difference: 3DGS applies its prune test after the new rows exist, with a zero screen radius for them; here

@@ -266,6 +266,14 @@ i lara_build_rays_out(i*3 f p*3 s)
 # include/lara_splatadam.h
 i lara_splatadam_step(p i l p*20 p i p s)
 i lara_splatadam_step_host(p i l p*20 p i p)
+# include/lara_splatdensify.h
+i lara_splatdensify_accumulate(l i p*5 s)
+i lara_splatdensify_accumulate_host(l i p*5)
+l lara_splatdensify_workspace_bytes(l)
+i lara_splatdensify_decide(p l p*9 s)
+i lara_splatdensify_decide_host(p l p*9)
+i lara_splatdensify_apply(p i l*3 p*7 s)
+i lara_splatdensify_apply_host(p i l*3 p*7)
 # include/lara_splatxform.h
 i lara_splatxform_apply(p i l p*10 l l s)
 i lara_splatxform_apply_host(p i l p*10 l l)

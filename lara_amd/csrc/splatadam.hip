@@ -19,7 +19,7 @@
 namespace {
 
 constexpr int SA_SPAN = LARA_SPLATADAM_SPAN;
-constexpr int SA_F = LARA_SPLATADAM_FIELDS;
+constexpr int SA_F = LARA_SURFEL_FIELDS;
 static_assert(SA_SPAN == 256 && SA_SPAN % 64 == 0, "whole waves");
 
 struct SaArgs {
@@ -84,17 +84,10 @@ int lara_splatadam_step(const double *plan, int32_t sh_degree, int64_t P, float 
     if (P == 0) return LARA2DGS_OK;
     SaArgs a;
     for (int i = 0; i < LARA_SPLATADAM_PLAN; ++i) a.plan[i] = plan[i];
-    int64_t blocks = 0;
-    for (int f = 0; f < SA_F; ++f) {
-        a.p[f] = ptrs[f], a.g[f] = ptrs[SA_F + f], a.m[f] = ptrs[2 * SA_F + f], a.v[f] = ptrs[3 * SA_F + f];
-        a.words[f] = (long long)(P * lara_splatadam_width(f, sh_degree));
-        a.first[f] = (unsigned)blocks;
-        blocks += (a.words[f] + SA_SPAN - 1) / SA_SPAN;
-        if (blocks > 0x7fffffffll) return LARA2DGS_E_INVALID;
-    }
-    a.first[SA_F] = (unsigned)blocks;
-#define SA_GO(DEG)                                                                                                                \
-    L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, sa_step_kernel<DEG>, dim3((unsigned)blocks), dim3(SA_SPAN), 0, a, visible, (int)zero_grads, \
+    for (int f = 0; f < SA_F; ++f) a.p[f] = ptrs[f], a.g[f] = ptrs[SA_F + f], a.m[f] = ptrs[2 * SA_F + f], a.v[f] = ptrs[3 * SA_F + f];
+    if (!lara_surfel_grid(P, sh_degree, SA_SPAN, a.words, a.first)) return LARA2DGS_E_INVALID;
+#define SA_GO(DEG)                                                                                                             \
+    L2D_LAUNCH_IN_SCOPE((hipStream_t)stream, sa_step_kernel<DEG>, dim3(a.first[SA_F]), dim3(SA_SPAN), 0, a, visible, (int)zero_grads, \
                         (unsigned long long *)skipped)
     switch (sh_degree) {
     case 0: SA_GO(0); break;

@@ -6,11 +6,9 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define LARA_SPLATADAM_HD __host__ __device__ __forceinline__
-#else
-#define LARA_SPLATADAM_HD inline
-#endif
+#include "surfel_ops.h"                          // the five fields and their widths, lara_surfel_finite, lara_surfel_round
+
+#define LARA_SPLATADAM_HD LARA_SURFEL_HD
 
 // offsets into the plan (lara_splatadam.h)
 #define LARA_SPLATADAM_B1 0
@@ -21,12 +19,6 @@
 #define LARA_SPLATADAM_SQRT_BC2 5
 #define LARA_SPLATADAM_EPS 6
 #define LARA_SPLATADAM_LR 7                      // centres, SH coefficient 0, SH coefficients >= 1, opacity, scales, rotations
-#define LARA_SPLATADAM_FIELDS 5
-
-// words per surfel of field f (centers, shs, opacity, scales, rotations) at an SH degree
-LARA_SPLATADAM_HD int64_t lara_splatadam_width(const int field, const int sh_degree) {
-    return field == 0 ? 3 : field == 1 ? 3 * (int64_t)(sh_degree + 1) * (sh_degree + 1) : field == 2 ? 1 : field == 3 ? 2 : 4;
-}
 
 // the learning rate of word r of a surfel's row of field f (r < 3 of shs: coefficient 0); selects, no indexed read of the plan
 LARA_SPLATADAM_HD double lara_splatadam_rate(const double *plan, const int field, const int64_t r) {
@@ -34,35 +26,20 @@ LARA_SPLATADAM_HD double lara_splatadam_rate(const double *plan, const int field
     return field == 0 ? lr[0] : field == 1 ? (r < 3 ? lr[1] : lr[2]) : field == 2 ? lr[3] : field == 3 ? lr[4] : lr[5];
 }
 
-// a finite fp32 word: its exponent field is not all ones
-LARA_SPLATADAM_HD bool lara_splatadam_finite(const float g) {
-    uint32_t w;
-    __builtin_memcpy(&w, &g, sizeof w);
-    return (w & 0x7F800000u) != 0x7F800000u;
-}
-
-// the one rounding; a NaN (from a moment or a parameter that came in non-finite) becomes 0x7FC00000 on either side
-LARA_SPLATADAM_HD float lara_splatadam_round(const double v) {
-    const float f = (float)v;
-    const uint32_t qnan = 0x7FC00000u;
-    float n;
-    __builtin_memcpy(&n, &qnan, sizeof n);
-    return f == f ? f : n;
-}
-
-// One word whose surfel is visible.  Returns 1 where the gradient is not finite: p, m and v then stay as they are.
+// One word whose surfel is visible.  Returns 1 where the gradient is not finite: p, m and v then stay as they are.  A NaN (from a
+// moment or a parameter that came in non-finite) is stored as 0x7FC00000 on either side.
 LARA_SPLATADAM_HD int lara_splatadam_word(const double *plan, const double lr, float *p, float *g, float *m, float *v, const int zero_grads) {
     const float gf = *g;
     if (zero_grads) *g = 0.0f;
-    if (!lara_splatadam_finite(gf)) return 1;
+    if (!lara_surfel_finite(gf)) return 1;
     const double gd = (double)gf, md = (double)*m, vd = (double)*v, pd = (double)*p;
     const double m1 = md + (gd - md) * plan[LARA_SPLATADAM_1MB1];
     const double v1 = plan[LARA_SPLATADAM_B2] * vd + (plan[LARA_SPLATADAM_1MB2] * gd) * gd;
     const double denom = __builtin_sqrt(v1) / plan[LARA_SPLATADAM_SQRT_BC2] + plan[LARA_SPLATADAM_EPS];
     const double p1 = pd - (lr / plan[LARA_SPLATADAM_BC1]) * (m1 / denom);
-    *m = lara_splatadam_round(m1);
-    *v = lara_splatadam_round(v1);
-    *p = lara_splatadam_round(p1);
+    *m = lara_surfel_round(m1);
+    *v = lara_surfel_round(v1);
+    *p = lara_surfel_round(p1);
     return 0;
 }
 
@@ -71,8 +48,8 @@ LARA_SPLATADAM_HD int lara_splatadam_word(const double *plan, const double lr, f
 inline int64_t lara_splatadam_host_words(const double *plan, const int sh_degree, const int64_t P, float *const *params, float *const *grads,
                                          float *const *exp_avg, float *const *exp_avg_sq, const uint8_t *visible, const int zero_grads) {
     int64_t skipped = 0;
-    for (int f = 0; f < LARA_SPLATADAM_FIELDS; ++f) {
-        const int64_t W = lara_splatadam_width(f, sh_degree);
+    for (int f = 0; f < LARA_SURFEL_FIELDS; ++f) {
+        const int64_t W = lara_surfel_width(f, sh_degree);
         for (int64_t s = 0; s < P; ++s)
             for (int64_t r = 0; r < W; ++r) {
                 const int64_t i = s * W + r;

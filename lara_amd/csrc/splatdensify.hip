@@ -18,12 +18,12 @@
 #include "common.h"
 #include "unigrid.h"
 #include "splatdensify_ops.h"
-#include "lara_splatdensify.h"
+#include "../../include/lara_splatdensify.h"
 
 namespace {
 
 constexpr int SD_SPAN = LARA_SPLATDENSIFY_SPAN;
-constexpr int SD_F = LARA_SPLATDENSIFY_FIELDS;
+constexpr int SD_F = LARA_SURFEL_FIELDS;
 constexpr int64_t SD_MAX_P = (int64_t)1 << 27;       // 9 P (a survivor and 8 children each) stays inside int32
 static_assert(SD_SPAN == 256 && SD_SPAN % 64 == 0, "whole waves");
 
@@ -211,20 +211,13 @@ int lara_splatdensify_apply(const double *plan, int32_t sh_degree, int64_t P, in
     SdGather a;
     for (int i = 0; i < LARA_SPLATDENSIFY_PLAN; ++i) a.plan[i] = plan[i];
     for (int i = 0; i < 3 * SD_F; ++i) a.in[i] = in[i], a.out[i] = out[i];
-    int64_t blocks = 0;
-    for (int f = 0; f < SD_F; ++f) {
-        a.words[f] = (long long)(P_out * lara_splatdensify_width(f, sh_degree));
-        a.first[f] = (unsigned)blocks;
-        blocks += (a.words[f] + SD_SPAN - 1) / SD_SPAN;
-        if (blocks > 0x7fffffffll) return LARA2DGS_E_INVALID;
-    }
-    a.first[SD_F] = (unsigned)blocks;
+    if (!lara_surfel_grid(P_out, sh_degree, SD_SPAN, a.words, a.first)) return LARA2DGS_E_INVALID;
     a.P = P, a.P_out = P_out, a.survivors = survivors;
     a.row_source = row_source, a.row_child = row_child, a.noise = noise;
     a.n_split = lara_splatdensify_children(plan);
     L2D_LAUNCH_IN_SCOPE(s, sd_rows_kernel, dim3(sd_blocks(P)), dim3(SD_SPAN), 0, (long long)P, a.n_split, action, offset, (long long)P_out,
                         row_source, row_child);
-#define SD_GO(DEG) L2D_LAUNCH_IN_SCOPE(s, sd_gather_kernel<DEG>, dim3((unsigned)blocks), dim3(SD_SPAN), 0, a)
+#define SD_GO(DEG) L2D_LAUNCH_IN_SCOPE(s, sd_gather_kernel<DEG>, dim3(a.first[SD_F]), dim3(SD_SPAN), 0, a)
     switch (sh_degree) {
     case 0: SD_GO(0); break;
     case 1: SD_GO(1); break;

@@ -8,11 +8,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define LARA_SPLATDENSIFY_HD __host__ __device__ __forceinline__
-#else
-#define LARA_SPLATDENSIFY_HD inline
-#endif
+#include "surfel_ops.h"                          // the five fields and their widths, lara_surfel_finite, lara_surfel_round
+
+#define LARA_SPLATDENSIFY_HD LARA_SURFEL_HD
 
 // offsets into the plan (lara_splatdensify.h)
 #define LARA_SPLATDENSIFY_GRAD 0
@@ -23,7 +21,6 @@
 #define LARA_SPLATDENSIFY_LOG_SHRINK 5
 #define LARA_SPLATDENSIFY_N 6
 #define LARA_SPLATDENSIFY_FLAGS 7
-#define LARA_SPLATDENSIFY_FIELDS 5
 
 #define LARA_SPLATDENSIFY_ALLOW_CLONE 1
 #define LARA_SPLATDENSIFY_ALLOW_SPLIT 2
@@ -34,27 +31,6 @@
 #define LARA_SPLATDENSIFY_SPLIT 2
 #define LARA_SPLATDENSIFY_PRUNE 3
 #define LARA_SPLATDENSIFY_NO_CHILD 255
-
-// words per surfel of field f (centers, shs, opacity, scales, rotations) at an SH degree
-LARA_SPLATDENSIFY_HD int64_t lara_splatdensify_width(const int field, const int sh_degree) {
-    return field == 0 ? 3 : field == 1 ? 3 * (int64_t)(sh_degree + 1) * (sh_degree + 1) : field == 2 ? 1 : field == 3 ? 2 : 4;
-}
-
-// a finite fp32 word: its exponent field is not all ones
-LARA_SPLATDENSIFY_HD bool lara_splatdensify_finite(const float g) {
-    uint32_t w;
-    __builtin_memcpy(&w, &g, sizeof w);
-    return (w & 0x7F800000u) != 0x7F800000u;
-}
-
-// fl32 of the header: the one rounding; a NaN becomes 0x7FC00000
-LARA_SPLATDENSIFY_HD float lara_splatdensify_round(const double v) {
-    const float f = (float)v;
-    const uint32_t qnan = 0x7FC00000u;
-    float n;
-    __builtin_memcpy(&n, &qnan, sizeof n);
-    return f == f ? f : n;
-}
 
 // The children per split of a plan, clamped to 1..8 (the entries refuse a plan outside it).
 LARA_SPLATDENSIFY_HD int lara_splatdensify_children(const double *plan) {
@@ -74,10 +50,10 @@ LARA_SPLATDENSIFY_HD void lara_splatdensify_accumulate_row(const int64_t P, cons
     }
     if (!any) return;
     const float gx = grad[0], gy = grad[1];
-    if (lara_splatdensify_finite(gx) && lara_splatdensify_finite(gy)) {      // (n is finite exactly then: a square of an fp32 is far inside double)
+    if (lara_surfel_finite(gx) && lara_surfel_finite(gy)) {      // (n is finite exactly then: a square of an fp32 is far inside double)
         const double x = (double)gx, y = (double)gy;
         const double n = __builtin_sqrt(x * x + y * y);
-        *grad_sum = lara_splatdensify_round((double)*grad_sum + n);
+        *grad_sum = lara_surfel_round((double)*grad_sum + n);
         *seen += 1;
     }
     if (most > *max_radius) *max_radius = most;
@@ -93,7 +69,7 @@ LARA_SPLATDENSIFY_HD int lara_splatdensify_action(const double *plan, const floa
     const double smax = a > b ? a : b;
     if (flags & LARA_SPLATDENSIFY_ALLOW_PRUNE) {
         bool gone = (double)opacity < plan[LARA_SPLATDENSIFY_LOGIT_MIN];
-        gone = gone || !lara_splatdensify_finite(opacity) || !lara_splatdensify_finite(s0) || !lara_splatdensify_finite(s1);
+        gone = gone || !lara_surfel_finite(opacity) || !lara_surfel_finite(s0) || !lara_surfel_finite(s1);
         if (plan[LARA_SPLATDENSIFY_MAX_SCREEN] > 0.0)
             gone = gone || (double)max_radius > plan[LARA_SPLATDENSIFY_MAX_SCREEN] || smax > plan[LARA_SPLATDENSIFY_LOG_WORLD];
         if (gone) return LARA_SPLATDENSIFY_PRUNE;
@@ -160,7 +136,7 @@ LARA_SPLATDENSIFY_HD float lara_splatdensify_child_center(const int r, const flo
     }
     const double u = exp((double)scale[0]) * (double)z[0];
     const double v = exp((double)scale[1]) * (double)z[1];
-    return lara_splatdensify_round((double)center[r] + (r0 * u + r1 * v));
+    return lara_surfel_round((double)center[r] + (r0 * u + r1 * v));
 }
 
 // One output word: word r of row o of field F (width W), with its two moments.  `in` and `out` are the field's parameter, exp_avg and
@@ -182,7 +158,7 @@ LARA_SPLATDENSIFY_HD void lara_splatdensify_word(const double *plan, const int f
         out[0][i] = lara_splatdensify_child_center((int)r, centers + 3 * src, scales + 2 * src, rotations + 4 * src,
                                                    noise + (src * n_split + child) * 2);
     else if (child != LARA_SPLATDENSIFY_NO_CHILD && field == 3)
-        out[0][i] = lara_splatdensify_round((double)in[0][j] - plan[LARA_SPLATDENSIFY_LOG_SHRINK]);
+        out[0][i] = lara_surfel_round((double)in[0][j] - plan[LARA_SPLATDENSIFY_LOG_SHRINK]);
     else
         __builtin_memcpy(out[0] + i, in[0] + j, sizeof(float));
     if (o < survivors) {
@@ -225,10 +201,10 @@ inline void lara_splatdensify_host_apply(const double *plan, const int sh_degree
                                          float *const *out, int32_t *row_source, uint8_t *row_child) {
     const int n_split = lara_splatdensify_children(plan);
     for (int64_t s = 0; s < P; ++s) lara_splatdensify_rows_of(P, n_split, s, action[s], offset, P_out, row_source, row_child);
-    for (int f = 0; f < LARA_SPLATDENSIFY_FIELDS; ++f) {
-        const int64_t W = lara_splatdensify_width(f, sh_degree);
-        const float *const fin[3] = {in[f], in[LARA_SPLATDENSIFY_FIELDS + f], in[2 * LARA_SPLATDENSIFY_FIELDS + f]};
-        float *const fout[3] = {out[f], out[LARA_SPLATDENSIFY_FIELDS + f], out[2 * LARA_SPLATDENSIFY_FIELDS + f]};
+    for (int f = 0; f < LARA_SURFEL_FIELDS; ++f) {
+        const int64_t W = lara_surfel_width(f, sh_degree);
+        const float *const fin[3] = {in[f], in[LARA_SURFEL_FIELDS + f], in[2 * LARA_SURFEL_FIELDS + f]};
+        float *const fout[3] = {out[f], out[LARA_SURFEL_FIELDS + f], out[2 * LARA_SURFEL_FIELDS + f]};
         for (int64_t o = 0; o < P_out; ++o)
             for (int64_t r = 0; r < W; ++r)
                 lara_splatdensify_word(plan, f, W, o, r, P, survivors, n_split, row_source, row_child, noise, in[0], in[3], in[4], fin, fout);

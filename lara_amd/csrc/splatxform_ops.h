@@ -8,11 +8,9 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define LARA_SPLATXFORM_HD __host__ __device__ __forceinline__
-#else
-#define LARA_SPLATXFORM_HD inline
-#endif
+#include "surfel_ops.h"                          // lara_surfel_round: fl32 of the header, the one rounding; a NaN becomes 0x7FC00000
+
+#define LARA_SPLATXFORM_HD LARA_SURFEL_HD
 
 // offsets into the plan (lara_splatxform.h)
 #define LARA_SPLATXFORM_A 0
@@ -22,15 +20,6 @@
 #define LARA_SPLATXFORM_D1 17
 #define LARA_SPLATXFORM_D2 26
 #define LARA_SPLATXFORM_D3 51
-
-// fl32 of the header: the one rounding; a NaN becomes 0x7FC00000
-LARA_SPLATXFORM_HD float lara_splatxform_round(const double v) {
-    const float f = (float)v;
-    const uint32_t qnan = 0x7FC00000u;
-    float n;
-    __builtin_memcpy(&n, &qnan, sizeof n);
-    return f == f ? f : n;
-}
 
 LARA_SPLATXFORM_HD void lara_splatxform_copy_word(const float *src, float *dst) {
     if (dst != src) __builtin_memcpy(dst, src, sizeof(float));
@@ -50,7 +39,7 @@ LARA_SPLATXFORM_HD void lara_splatxform_band(const double *D, const float *sh, f
             double acc = D[W * i] * c[0];
 #pragma unroll
             for (int j = 1; j < W; ++j) acc = acc + D[W * i + j] * c[j];
-            out[3 * (L * L + i) + ch] = lara_splatxform_round(acc);
+            out[3 * (L * L + i) + ch] = lara_surfel_round(acc);
         }
     }
 }
@@ -64,21 +53,21 @@ LARA_SPLATXFORM_HD void lara_splatxform_surfel(const double *plan, const float *
         const double *A = plan + LARA_SPLATXFORM_A, *t = plan + LARA_SPLATXFORM_T;
         const double x = (double)center[0], y = (double)center[1], z = (double)center[2];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) out_center[i] = lara_splatxform_round(((A[3 * i] * x + A[3 * i + 1] * y) + A[3 * i + 2] * z) + t[i]);
+        for (int i = 0; i < 3; ++i) out_center[i] = lara_surfel_round(((A[3 * i] * x + A[3 * i + 1] * y) + A[3 * i + 2] * z) + t[i]);
     }
     {
         const double *r = plan + LARA_SPLATXFORM_R;
         const double w = (double)rot[0], x = (double)rot[1], y = (double)rot[2], z = (double)rot[3];
-        out_rot[0] = lara_splatxform_round(((r[0] * w - r[1] * x) - r[2] * y) - r[3] * z);
-        out_rot[1] = lara_splatxform_round(((r[0] * x + r[1] * w) + r[2] * z) - r[3] * y);
-        out_rot[2] = lara_splatxform_round(((r[0] * y - r[1] * z) + r[2] * w) + r[3] * x);
-        out_rot[3] = lara_splatxform_round(((r[0] * z + r[1] * y) - r[2] * x) + r[3] * w);
+        out_rot[0] = lara_surfel_round(((r[0] * w - r[1] * x) - r[2] * y) - r[3] * z);
+        out_rot[1] = lara_surfel_round(((r[0] * x + r[1] * w) + r[2] * z) - r[3] * y);
+        out_rot[2] = lara_surfel_round(((r[0] * y - r[1] * z) + r[2] * w) + r[3] * x);
+        out_rot[3] = lara_surfel_round(((r[0] * z + r[1] * y) - r[2] * x) + r[3] * w);
     }
     {
         const double log_s = plan[LARA_SPLATXFORM_LOGS];
         const double a = (double)scale[0], b = (double)scale[1];
-        out_scale[0] = lara_splatxform_round(a + log_s);
-        out_scale[1] = lara_splatxform_round(b + log_s);
+        out_scale[0] = lara_surfel_round(a + log_s);
+        out_scale[1] = lara_surfel_round(b + log_s);
     }
     lara_splatxform_copy_word(opacity, out_opacity);
 #pragma unroll

@@ -1,4 +1,4 @@
-"""Densifying a cloud of surfels under refinement (csrc/lara_splatdensify.h, csrc/splatdensify.hip): the other half of the
+"""Densifying a cloud of surfels under refinement (include/lara_splatdensify.h, csrc/splatdensify.hip): the other half of the
 Gaussian-splatting optimisation loop beside ``splatrefine``'s Adam step.  Surfels whose screen-space gradient is high are cloned (the
 small ones) or split into ``N`` children (the large ones), the transparent and the oversized are pruned, and the Adam moments travel
 with the rows that survive.  Opt-in like every module here, imported by nothing on the default routes (``splatrefine`` imports it
@@ -27,7 +27,8 @@ z from a caller-supplied ``noise`` [P,N,2] (``torch.randn`` under a seeded gener
 the kernel, so a round is reproducible.
 
 Tensors on the GPU go through the kernels.  Tensors on the host go through the ``*_host`` entries, the same per-row functions compiled
-for the CPU (csrc/splatdensify_ops.h): the reference the kernels are held to, not a fast path.
+for the CPU (csrc/splatdensify_ops.h): the reference the kernels are held to, not a fast path.  Either way through
+``_native.call_on``: the seven functions are rows of ``_native.SIGNATURES`` like every other.
 
 Out of scope: learning-rate schedules, 3DGS's prune-after-append ordering, absolute-gradient statistics, per-view statistics inside a
 multi-view call, merging of surfels.
@@ -45,7 +46,7 @@ from . import splatrefine
 from . import _native
 from ._native import host_array
 
-PLAN = 8                                 # csrc/lara_splatdensify.h
+PLAN = 8                                 # include/lara_splatdensify.h
 SPAN = 256
 MAX_SURFELS = 1 << 27
 KEEP, CLONE, SPLIT, PRUNE = 0, 1, 2, 3
@@ -54,43 +55,7 @@ ALLOW_CLONE, ALLOW_SPLIT, ALLOW_PRUNE = 1, 2, 4
 COUNT_KEYS = ("kept", "cloned", "split", "pruned", "P_out")
 FIELDS = splatio.SurfelCloud.FIELDS
 _WHO = "lara_amd.splatdensify"
-
-# The entry points of csrc/lara_splatdensify.h in _native.SIGNATURES' notation.  They are bound here and not by rows of that table:
-# tests/test_abi_cpu.py pins the table and the headers under include/ to a fixed number of functions.
-ENTRY_POINTS = """
-i lara_splatdensify_accumulate(l i p*5 s)
-i lara_splatdensify_accumulate_host(l i p*5)
-l lara_splatdensify_workspace_bytes(l)
-i lara_splatdensify_decide(p l p*9 s)
-i lara_splatdensify_decide_host(p l p*9)
-i lara_splatdensify_apply(p i l*3 p*7 s)
-i lara_splatdensify_apply_host(p i l*3 p*7)
-"""
-_SIGS = _native._parse_signatures(ENTRY_POINTS)
 _workspace = _native.StreamWorkspace()
-
-
-def _entry(name):
-    """The function ``name`` of the loaded library with its types set (once)."""
-    fn = getattr(_native.load_library(), name)
-    if fn.argtypes is None:
-        fn.restype, fn.argtypes = _SIGS[name][0], _SIGS[name][1]
-    return fn
-
-
-def _call_on(name, device, *args):
-    """``_native.call_on`` for the entries bound here: the device entry on the device's current stream for tensors on the GPU, its
-    ``_host`` twin for tensors on the host; a tensor goes as its ``data_ptr()``, None as NULL."""
-    on_gpu = device.type == "cuda"
-    name = name if on_gpu else name + "_host"
-    a = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
-    if on_gpu:
-        with torch.cuda.device(device):
-            rc = _entry(name)(*a, _native.current_stream(device))
-    else:
-        rc = _entry(name)(*a)
-    if rc != 0:
-        _native.check(rc, name)
 
 
 # ---------------------------------------------------------------------------------------------------------- the plan
@@ -118,13 +83,6 @@ def _plan_row(plan):
     if row.shape != (PLAN,) or not (1.0 <= row[6] <= 8.0 and row[6] == int(row[6]) and 0.0 <= row[7] <= 7.0 and row[7] == int(row[7])):
         raise ValueError(f"{_WHO}: a plan is {PLAN} doubles (splatdensify.plan) with n_split in 1..8 and flags in 0..7")
     return row
-
-
-def _fields(what, ts, like=None):
-    try:
-        return splatrefine._check_fields(what, ts, like)
-    except ValueError as e:
-        raise ValueError(str(e).replace(splatrefine._WHO, _WHO)) from None
 
 
 def _row(what, t, shape, dtype, dev):
@@ -166,7 +124,8 @@ class DensifyStats:
             raise ValueError(f"{_WHO}: radii is an int32 tensor [V,{P}] with V >= 1")
         _row("radii", radii, (radii.shape[0], P), torch.int32, dev)
         if P:
-            _call_on("lara_splatdensify_accumulate", dev, P, radii.shape[0], grad_means2D, radii, self.grad_sum, self.seen, self.max_radius)
+            _native.call_on("lara_splatdensify_accumulate", dev, P, radii.shape[0], grad_means2D, radii, self.grad_sum, self.seen,
+                            self.max_radius)
 
 
 # ---------------------------------------------------------------------------------------------------------- the decision
@@ -177,7 +136,7 @@ def decide(params, stats, plan):
     ``SPLIT``, ``PRUNE``) from its stored opacity and scales and its statistics under ``plan``, the exclusive scan of
     [1 per keep or clone | 1 per clone | N per split], and the counts ``COUNT_KEYS``: kept, cloned, split parents, pruned, P_out.
     No host read."""
-    params = _fields("params", [p.detach() for p in params])
+    params = splatio.check_fields(_WHO, "params", [p.detach() for p in params])
     dev, P = params[0].device, params[0].shape[0]
     row = _plan_row(plan)
     if not isinstance(stats, DensifyStats) or stats.n_surfels != P or stats.device != dev:
@@ -191,9 +150,9 @@ def decide(params, stats, plan):
         return action, offset, counts
     ws = None
     if dev.type == "cuda":
-        ws = _workspace(dev, int(_entry("lara_splatdensify_workspace_bytes")(P)))
-    _call_on("lara_splatdensify_decide", dev, host_array("d", [float(v) for v in row]), P, params[2], params[3], stats.grad_sum, stats.seen,
-             stats.max_radius, action, offset, counts, ws)
+        ws = _workspace(dev, _native.query("lara_splatdensify_workspace_bytes", P))
+    _native.call_on("lara_splatdensify_decide", dev, host_array("d", row.tolist()), P, params[2], params[3], stats.grad_sum, stats.seen,
+                    stats.max_radius, action, offset, counts, ws)
     return action, offset, counts
 
 
@@ -214,8 +173,8 @@ def apply(params, exp_avg, exp_avg_sq, action, offset, counts, plan, noise=None,
     for bit, kept rows their moment words too; clones and split children start from zero moments; a split child's scales shrink by
     0.8 N and its centre moves by ``noise`` [P,N,2] (None: ``torch.randn`` under a generator seeded with ``seed``).  ``row_child``
     is ``NO_CHILD`` (255) for rows that are not split children.  The inputs are left as they are."""
-    params = _fields("params", [p.detach() for p in params])
-    exp_avg, exp_avg_sq = _fields("exp_avg", exp_avg, like=params), _fields("exp_avg_sq", exp_avg_sq, like=params)
+    params = splatio.check_fields(_WHO, "params", [p.detach() for p in params])
+    exp_avg, exp_avg_sq = (splatio.check_fields(_WHO, w, ts, like=params) for w, ts in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)))
     dev, P, n_coeffs = params[0].device, params[0].shape[0], params[1].shape[1]
     row = _plan_row(plan)
     n = int(row[6])
@@ -231,9 +190,9 @@ def apply(params, exp_avg, exp_avg_sq, action, offset, counts, plan, noise=None,
     row_source = torch.empty(P_out, dtype=torch.int32, device=dev)
     row_child = torch.empty(P_out, dtype=torch.uint8, device=dev)
     if P and P_out:
-        _call_on("lara_splatdensify_apply", dev, host_array("d", [float(v) for v in row]), splatio.SH_COEFFS[n_coeffs], P, P_out, survivors,
-                 action, offset, noise, host_array("p", params + exp_avg + exp_avg_sq), host_array("p", outs[0] + outs[1] + outs[2]),
-                 row_source, row_child)
+        _native.call_on("lara_splatdensify_apply", dev, host_array("d", row.tolist()), splatio.SH_COEFFS[n_coeffs], P, P_out, survivors,
+                        action, offset, noise, host_array("p", params + exp_avg + exp_avg_sq), host_array("p", outs[0] + outs[1] + outs[2]),
+                        row_source, row_child)
     return outs[0], outs[1], outs[2], row_source, row_child, five
 
 

@@ -10,6 +10,7 @@ render of the original tensors.
   * ``SurfelCloud``           the five tensors, ``from_render_pkg`` / ``render_args`` / ``gs_params`` / ``to``;
   * ``scene_item``            one scene's coarse or fine entry of ``render_pkg``;
   * ``select`` / ``concatenate``  ordered row selection (opacity, box) and joining;
+  * ``check_fields``          the five tensors of a cloud as ``splatrefine``'s and ``splatdensify``'s kernels take them;
   * ``ply_header`` / ``ply_bytes`` / ``write_ply``  one packed [P, F] fp32 buffer where the tensors lie, one copy to the host;
   * ``read_ply``              properties by name in any order, other scalar properties skipped, a third scale dropped and reported.
 
@@ -126,6 +127,34 @@ def concatenate(clouds):
     if len({c.sh_degree for c in clouds}) != 1:
         raise ValueError(f"{_WHO}: the clouds have SH degrees {[c.sh_degree for c in clouds]}; they must share one")
     return SurfelCloud(*(torch.cat(ts) for ts in zip(*(c.render_args() for c in clouds))))
+
+
+def check_fields(who, what, ts, like=None):
+    """The five tensors of ``what`` as the surfel kernels take them (``splatrefine``, ``splatdensify``): fp32, contiguous, one
+    device, a cloud's shapes (or ``like``'s).  ``who`` is the calling module's name, the head of every message."""
+    FIELDS = SurfelCloud.FIELDS
+    ts = list(ts)
+    if len(ts) != len(FIELDS) or not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError(f"{who}: {what} is five tensors {FIELDS}")
+    if like is None:
+        P = ts[0].shape[0] if ts[0].dim() == 2 else -1
+        n = ts[1].shape[1] if ts[1].dim() == 3 else -1
+        if n not in SH_COEFFS:
+            raise ValueError(f"{who}: {what}: shs is [P,n,3] with n in (1, 4, 9, 16), got {tuple(ts[1].shape)}")
+        shapes = ((P, 3), (P, n, 3), (P, 1), (P, 2), (P, 4))
+    else:
+        shapes = [tuple(t.shape) for t in like]
+    dev = (like or ts)[0].device
+    for name, t, shape in zip(FIELDS, ts, shapes):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {what}.{name} is {tuple(t.shape)}, expected {tuple(shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {what}.{name} is {t.dtype}; the update works on fp32 words")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {what}.{name} is not contiguous")
+        if t.device != dev:
+            raise ValueError(f"{who}: {what}.{name} lies on {t.device}, params.centers on {dev}")
+    return ts
 
 
 # ---------------------------------------------------------------------------------------------------------- writing

@@ -85,32 +85,6 @@ def plan(step, lrs=None, betas=(0.9, 0.999), eps=1e-15):
 
 # ---------------------------------------------------------------------------------------------------------- the step
 
-def _check_fields(what, ts, like=None):
-    """The five tensors of ``what`` as the kernel takes them: fp32, contiguous, one device, a cloud's shapes (or ``like``'s)."""
-    ts = list(ts)
-    if len(ts) != len(FIELDS) or not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError(f"{_WHO}: {what} is five tensors {FIELDS}")
-    if like is None:
-        P = ts[0].shape[0] if ts[0].dim() == 2 else -1
-        n = ts[1].shape[1] if ts[1].dim() == 3 else -1
-        if n not in splatio.SH_COEFFS:
-            raise ValueError(f"{_WHO}: {what}: shs is [P,n,3] with n in (1, 4, 9, 16), got {tuple(ts[1].shape)}")
-        shapes = ((P, 3), (P, n, 3), (P, 1), (P, 2), (P, 4))
-    else:
-        shapes = [tuple(t.shape) for t in like]
-    dev = (like or ts)[0].device
-    for name, t, shape in zip(FIELDS, ts, shapes):
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{_WHO}: {what}.{name} is {tuple(t.shape)}, expected {tuple(shape)}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{_WHO}: {what}.{name} is {t.dtype}; the update works on fp32 words")
-        if not t.is_contiguous():
-            raise ValueError(f"{_WHO}: {what}.{name} is not contiguous")
-        if t.device != dev:
-            raise ValueError(f"{_WHO}: {what}.{name} lies on {t.device}, params.centers on {dev}")
-    return ts
-
-
 def bump_version(tensors):
     """Advance torch's version counter of every tensor: what a write through ``data_ptr()`` does not do."""
     inc = getattr(torch.autograd.graph, "increment_version", None)
@@ -131,8 +105,8 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, plan, visible=None, zero_grads
     non-finite gradient is ADDED (None: a fresh zero).  Returns ``counters``.  One kernel launch, no host read, on the GPU; the host
     entry for host tensors.  The version counters are not advanced (``bump_version``).  ValueError: a non-contiguous tensor, a wrong
     dtype, mixed devices, a gradient or moment whose shape differs from its field's."""
-    params = _check_fields("params", params)
-    grads, exp_avg, exp_avg_sq = (_check_fields(w, ts, like=params) for w, ts in (("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)))
+    params = splatio.check_fields(_WHO, "params", params)
+    grads, exp_avg, exp_avg_sq = (splatio.check_fields(_WHO, w, ts, like=params) for w, ts in (("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)))
     dev, P, n = params[0].device, params[0].shape[0], params[1].shape[1]
     row = np.asarray(plan, np.float64)
     if row.shape != (PLAN,):
@@ -151,7 +125,7 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, plan, visible=None, zero_grads
         raise ValueError(f"{_WHO}: counters is one int64 on {dev}")
     if P == 0:                               # (an empty tensor has no address to hand over; nothing is launched)
         return counters
-    _native.call_on("lara_splatadam_step", dev, host_array("d", [float(v) for v in row]), splatio.SH_COEFFS[n], P,
+    _native.call_on("lara_splatadam_step", dev, host_array("d", row.tolist()), splatio.SH_COEFFS[n], P,
                     *params, *grads, *exp_avg, *exp_avg_sq, visible, 1 if zero_grads else 0, counters)
     return counters
 
@@ -214,7 +188,7 @@ class SurfelAdam:
         """Take over a ``state()``: the words are copied into this optimiser's own tensors (same shapes), the versions advance."""
         dev = self._params[0].device
         for mine, key in ((self._params, "params"), (self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-            theirs = _check_fields(f"state[{key!r}]", [t.to(dev) for t in state[key]], like=mine)
+            theirs = splatio.check_fields(_WHO, f"state[{key!r}]", [t.to(dev) for t in state[key]], like=mine)
             for a, b in zip(mine, theirs):
                 a.copy_(b)
         self.skipped.copy_(state["skipped"].to(dev))

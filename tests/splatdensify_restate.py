@@ -1,4 +1,4 @@
-"""The rules of csrc/lara_splatdensify.h restated in numpy, float64 and integers: the statistics of a render call, every surfel's
+"""The rules of include/lara_splatdensify.h restated in numpy, float64 and integers: the statistics of a render call, every surfel's
 action with the exclusive offsets and the counts, and the output cloud with its moments -- the same formulas in the same operation
 order, each one correctly rounded IEEE operation on arrays, one rounding to float32 per store.  Written from the header, without
 the module.  The one step that is not correctly rounded on either side is the float64 exp of a split child's centre."""

@@ -118,7 +118,7 @@ def test_signature_table_equals_the_headers():
     """Every function the headers declare has a row, every row a declaration, and they agree in the return type and, position by
     position, in the kind of every parameter (pointer / int32 / int64 / float)."""
     assert table_mismatches() == []             # (first: it names the function, the count below only counts)
-    assert len(header_functions()) == len(_native._SIGS) == 189
+    assert len(header_functions()) == len(_native._SIGS) == 196
 
 
 # how many functions each header declares: a function that moves between headers, or a header that appears or goes, shows here
@@ -127,14 +127,14 @@ FUNCTIONS_PER_HEADER = {
     "lara_finedec.h": 8, "lara_groupattn.h": 20, "lara_loss.h": 6, "lara_lpips.h": 4, "lara_meshalign.h": 3, "lara_meshbvh.h": 6, "lara_meshclean.h": 6,
     "lara_meshdist.h": 7, "lara_meshio.h": 8, "lara_meshmetrics.h": 7, "lara_meshray.h": 6, "lara_meshrender.h": 3,
     "lara_meshsign.h": 6, "lara_meshsimplify.h": 12, "lara_meshtexture.h": 7, "lara_meshtopo.h": 12, "lara_meshwind.h": 6,
-    "lara_pointfeat.h": 7, "lara_rays.h": 1, "lara_splatadam.h": 2, "lara_splatxform.h": 2, "lara_surface.h": 6, "lara_tsdf.h": 4,
-    "lara_vit.h": 5,
+    "lara_pointfeat.h": 7, "lara_rays.h": 1, "lara_splatadam.h": 2, "lara_splatdensify.h": 7, "lara_splatxform.h": 2,
+    "lara_surface.h": 6, "lara_tsdf.h": 4, "lara_vit.h": 5,
 }
 
 
 def test_each_header_declares_its_pinned_number_of_functions():
     assert {hdr: len(fns) for hdr, fns in header_functions_by_file().items()} == FUNCTIONS_PER_HEADER
-    assert sum(FUNCTIONS_PER_HEADER.values()) == 189
+    assert sum(FUNCTIONS_PER_HEADER.values()) == 196
     assert [d for d in os.listdir(os.path.join(ROOT, "include")) if not d.endswith(".h")] == [], "include/ is flat"
 
 
@@ -145,7 +145,7 @@ def test_stream_flag_follows_the_prototype():
         for name, params in re.findall(r"\b(lara2dgs_\w+|lara_\w+)\s*\(([^()]*)\)\s*;", text):
             assert _native._SIGS[name][2] == bool(re.search(r"void\s*\*\s*stream\s*$", params)), name
             seen += 1
-    assert seen == 189
+    assert seen == 196
 
 
 def test_a_changed_prototype_fails_the_table_check(tmp_path):

@@ -6,7 +6,6 @@ bit for bit, the children's centres within one fp32 spacing --; the rows that si
 import ctypes
 import math
 import os
-import shutil
 import subprocess
 import sys
 
@@ -290,7 +289,7 @@ def test_an_empty_cloud_and_an_empty_result_launch_nothing(hip_lib, monkeypatch)
     gone = C.round_case(65, 1, 2, "prune", seed=0)
     params, m, v = (fields(gone[k]) for k in ("params", "exp_avg", "exp_avg_sq"))
     action, offset, counts = D.decide(params, make_stats(D, gone), gone["plan"])
-    monkeypatch.setattr(D, "_call_on", lambda name, *a: pytest.fail(f"{name} was called"))
+    monkeypatch.setattr(D._native, "call_on", lambda name, *a: pytest.fail(f"{name} was called"))
     out = D.apply(params, m, v, action, offset, counts, gone["plan"])
     assert out[5]["P_out"] == 0 and out[5]["pruned"] == 65 and out[3].shape == (0,) and out[4].dtype == torch.uint8
     assert [tuple(t.shape) for t in out[0]] == [(0, 3), (0, 4, 3), (0, 1), (0, 2), (0, 4)]
@@ -304,10 +303,10 @@ def test_an_empty_cloud_and_an_empty_result_launch_nothing(hip_lib, monkeypatch)
 
 
 def test_the_entry_points_refuse_bad_arguments(hip_lib):
-    from lara_amd import splatdensify as D
+    from tests.test_abi_cpu import header_functions_by_file
     case = C.round_case(8, 1, 2, "mix", seed=0)
-    host = {n: D._entry(n) for n in D._SIGS}
-    row = (ctypes.c_double * 8)(*case["plan"])
+    host = {n: getattr(hip_lib, n) for n in header_functions_by_file()["lara_splatdensify.h"]}
+    row =(ctypes.c_double * 8)(*case["plan"])
     bufs = [case[g][k].copy() for g in ("params", "exp_avg", "exp_avg_sq") for k in C.FIELDS]
     outs = [np.zeros((40,) + b.shape[1:], np.float32) for b in bufs]
     ins_p, outs_p = (ctypes.c_void_p * 15)(*[b.ctypes.data for b in bufs]), (ctypes.c_void_p * 15)(*[b.ctypes.data for b in outs])
@@ -375,8 +374,8 @@ CARVE_OFFSETS = (1, 3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25, 27, 29)
 
 def apply_into_carved(case, device="cpu"):
     """`decide`, then the apply entry writing into rows carved out of sentinel-filled buffers at odd offsets (the module's `apply`
-    allocates its own outputs, so this goes through the module's binding): (the 15 views, row_source, row_child, all sentinels kept)."""
-    from lara_amd import splatdensify as D
+    allocates its own outputs, so this goes through the shared binding): (the 15 views, row_source, row_child, all sentinels kept)."""
+    from lara_amd import _native, splatdensify as D
     from lara_amd._native import host_array
     dev = torch.device(device)
     params, m, v = (fields(case[k], device) for k in ("params", "exp_avg", "exp_avg_sq"))
@@ -387,9 +386,9 @@ def apply_into_carved(case, device="cpu"):
     rows_whole = torch.full((P_out + 11,), -7, dtype=torch.int32, device=dev)
     child_whole = torch.full((P_out + 11,), 77, dtype=torch.uint8, device=dev)
     noise = torch.from_numpy(case["noise"].copy()).to(dev)
-    D._call_on("lara_splatdensify_apply", dev, host_array("d", [float(x) for x in case["plan"]]), case["degree"], case["P"], P_out,
-               five["kept"] + five["cloned"], action, offset, noise, host_array("p", params + m + v), host_array("p", views),
-               rows_whole[3:3 + P_out], child_whole[5:5 + P_out])
+    _native.call_on("lara_splatdensify_apply", dev, host_array("d", [float(x) for x in case["plan"]]), case["degree"], case["P"], P_out,
+                    five["kept"] + five["cloned"], action, offset, noise, host_array("p", params + m + v), host_array("p", views),
+                    rows_whole[3:3 + P_out], child_whole[5:5 + P_out])
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
     kept = sentinels_kept(wholes, CARVE_OFFSETS, P_out)
@@ -411,24 +410,21 @@ def test_outputs_carved_out_of_sentinel_buffers_leave_every_sentinel(hip_lib):
 
 # ------------------------------------------------------------------------------------------------------------------ the binding, the build
 
-def test_the_modules_binding_equals_the_headers_prototypes(hip_lib, tmp_path):
-    """The header lies beside its unit and the module binds its seven functions itself (tests/test_abi_cpu.py pins include/ and the
-    signature table to a fixed number of functions): the module's rows equal the header's prototypes kind by kind, none of them is a
-    row of the shared table, the library exports all, the stream is on the device entries alone, the unit is built with
+def test_the_modules_binding_equals_the_headers_prototypes(hip_lib):
+    """The header lies under include/ and its seven functions are rows of ``_native.SIGNATURES`` (tests/test_abi_cpu.py holds the rows
+    to the prototypes, kind by kind): the library exports all, the stream is on the device entries alone, the unit is built with
     -ffp-contract=off, and the header's plan and span are the module's."""
     from lara_amd import _native, splatdensify as D
-    from tests.test_abi_cpu import _ctypes_kind, header_functions
-    shutil.copy(os.path.join(ROOT, "lara_amd", "csrc", "lara_splatdensify.h"), tmp_path)
-    declared = header_functions(str(tmp_path))
-    assert sorted(declared) == sorted(D._SIGS) and len(declared) == 7
-    for name, (restype, argtypes, has_stream) in D._SIGS.items():
-        assert (_ctypes_kind(restype), [_ctypes_kind(t) for t in argtypes]) == declared[name], name
-        assert has_stream == (not name.endswith(("_host", "_bytes"))), name
-        assert hasattr(hip_lib, name), name
-    assert not set(D._SIGS) & set(_native._SIGS)
+    from tests.test_abi_cpu import header_functions_by_file
+    names = ["lara_splatdensify_accumulate", "lara_splatdensify_accumulate_host", "lara_splatdensify_apply", "lara_splatdensify_apply_host",
+             "lara_splatdensify_decide", "lara_splatdensify_decide_host", "lara_splatdensify_workspace_bytes"]
+    assert sorted(header_functions_by_file()["lara_splatdensify.h"]) == names
+    assert set(names) <= set(_native._SIGS) and all(hasattr(hip_lib, n) for n in names)
+    for name in names:
+        assert _native._SIGS[name][2] == (not name.endswith(("_host", "_bytes"))), name
     text = open(os.path.join(ROOT, "lara_amd", "csrc", "Makefile")).read()
     assert "FLAGS_splatdensify := -ffp-contract=off\n" in text and " splatdensify" in text.split("OBJS")[1].splitlines()[0]
-    header = open(os.path.join(ROOT, "lara_amd", "csrc", "lara_splatdensify.h")).read()
+    header = open(os.path.join(ROOT, "include", "lara_splatdensify.h")).read()
     assert f"#define LARA_SPLATDENSIFY_PLAN {D.PLAN}\n" in header and f"#define LARA_SPLATDENSIFY_SPAN {D.SPAN}\n" in header
     assert "[RECALLED" in header and "PER RENDER CALL" in header and "leaves no descendants" in header
 

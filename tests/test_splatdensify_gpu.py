@@ -60,7 +60,7 @@ def test_the_accumulation_kernel_equals_the_host_entry(hip_lib):
 
 
 def test_outputs_carved_out_of_sentinel_buffers_leave_every_sentinel(hip_lib):
-    from lara_amd import splatdensify as D
+    from lara_amd import _native, splatdensify as D
     from lara_amd._native import host_array
     for P, degree, n in ((1, 0, 2), (65, 1, 3), (257, 3, 2), (1025, 1, 2)):
         case = C.round_case(P, degree, n, "mix" if P > 1 else "split", seed=4)
@@ -77,9 +77,9 @@ def test_outputs_carved_out_of_sentinel_buffers_leave_every_sentinel(hip_lib):
         offset = torch.full((3 * P + 11,), -7, dtype=torch.int32, device=DEV)
         counts = torch.full((5 + 6,), -7, dtype=torch.int64, device=DEV)
         st = make_stats(D, case, DEV)
-        ws = torch.empty(int(D._entry("lara_splatdensify_workspace_bytes")(P)), dtype=torch.uint8, device=DEV)
-        D._call_on("lara_splatdensify_decide", DEV, host_array("d", [float(x) for x in case["plan"]]), P, params[2], params[3], st.grad_sum,
-                   st.seen, st.max_radius, action[5:5 + P], offset[3:3 + 3 * P], counts[3:8], ws)
+        ws = torch.empty(_native.query("lara_splatdensify_workspace_bytes", P), dtype=torch.uint8, device=DEV)
+        _native.call_on("lara_splatdensify_decide", DEV, host_array("d", [float(x) for x in case["plan"]]), P, params[2], params[3],
+                        st.grad_sum, st.seen, st.max_radius, action[5:5 + P], offset[3:3 + 3 * P], counts[3:8], ws)
         torch.cuda.synchronize()
         assert np.array_equal(action[5:5 + P].cpu().numpy(), want["action"]) and np.array_equal(offset[3:3 + 3 * P].cpu().numpy(), want["offset"])
         assert np.array_equal(counts[3:8].cpu().numpy(), want["counts"])

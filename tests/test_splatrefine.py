@@ -293,6 +293,19 @@ def test_the_entry_points_refuse_bad_arguments(hip_lib):
     assert dev(row, 1, 0, *p, None, 0, count.ctypes.data, None) == 0                   # empty: nothing is launched
 
 
+def test_the_device_entry_refuses_a_grid_beyond_the_launch_limit(hip_lib):
+    """2^40 surfels at SH degree 3 are 2^40 * 48 / 256 workgroups of the shs field alone, far beyond the 2^31 - 1 a launch takes: the
+    device entry passes its argument check (P <= 2^40, no null pointer) and refuses while it lays out the grid, before it touches a
+    device.  The 22 addresses are never dereferenced.  This is the one route to that refusal: splatdensify caps P at 2^27."""
+    from lara_amd import splatrefine as R
+    row = (ctypes.c_double * 13)(*R.plan(1))
+    addresses = [4096 * (k + 1) for k in range(22)]
+    assert len(set(addresses)) == 22
+    dev = hip_lib.lara_splatadam_step
+    assert dev(row, 3, 2 ** 40, *addresses[:20], addresses[20], 0, addresses[21], None) == -1
+    assert dev(row, 3, 0, *addresses[:20], addresses[20], 0, addresses[21], None) == 0
+
+
 # ------------------------------------------------------------------------------------------------------------------ the optimiser object
 
 def test_surfel_adam_on_the_host_steps_counts_and_restores(hip_lib):

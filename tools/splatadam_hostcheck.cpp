@@ -42,7 +42,7 @@ int main(int argc, char **argv) {
         std::vector<float> in[20], want[20];
         std::vector<uint8_t> visible((size_t)P);
         bool ok = std::fread(plan.data(), sizeof(double), 13, f) == 13;
-        for (int k = 0; ok && k < 20; ++k) ok = take(f, in[k], (size_t)(lara_splatadam_width(k % 5, (int)degree) * P));
+        for (int k = 0; ok && k < 20; ++k) ok = take(f, in[k], (size_t)(lara_surfel_width(k % 5, (int)degree) * P));
         if (ok && has_visible && P) ok = std::fread(visible.data(), 1, (size_t)P, f) == (size_t)P;
         for (int k = 0; ok && k < 20; ++k) ok = take(f, want[k], in[k].size());
         if (!ok) { std::fprintf(stderr, "splatadam_hostcheck: short case %lld\n", (long long)c); std::fclose(f); return 2; }

@@ -91,7 +91,7 @@ def torch_round(w, row):
 
 
 def rows(P, degree, dev, rounds, rate):
-    from lara_amd import splatdensify as D
+    from lara_amd import _native, splatdensify as D
     from lara_amd._native import host_array
     w = workload(P, degree, dev)
     row = D.plan(THRESHOLD, 1.0, 1.0, 0.005)
@@ -101,15 +101,15 @@ def rows(P, degree, dev, rounds, rate):
     scratch = D.DensifyStats(P, dev)
     action, offset, counts = D.decide(w["params"], stats, row)
     p2, m2, v2, source, child, five = D.apply(w["params"], w["exp_avg"], w["exp_avg_sq"], action, offset, counts, row, noise=w["noise"])
-    ws = torch.empty(int(D._entry("lara_splatdensify_workspace_bytes")(P)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_native.query("lara_splatdensify_workspace_bytes", P), dtype=torch.uint8, device=dev)
     plan_c, ins, outs = host_array("d", [float(x) for x in row]), host_array("p", w["params"] + w["exp_avg"] + w["exp_avg_sq"]), host_array("p", p2 + m2 + v2)
     survivors, P_out = five["kept"] + five["cloned"], five["P_out"]
     variants = {
         "accumulate_ms": lambda: scratch.accumulate(w["grad"], w["radii"]),
-        "decide_ms": lambda: D._call_on("lara_splatdensify_decide", dev, plan_c, P, w["params"][2], w["params"][3], stats.grad_sum, stats.seen,
-                                        stats.max_radius, action, offset, counts, ws),
-        "apply_ms": lambda: D._call_on("lara_splatdensify_apply", dev, plan_c, degree, P, P_out, survivors, action, offset, w["noise"], ins, outs,
-                                       source, child),
+        "decide_ms": lambda: _native.call_on("lara_splatdensify_decide", dev, plan_c, P, w["params"][2], w["params"][3], stats.grad_sum,
+                                             stats.seen, stats.max_radius, action, offset, counts, ws),
+        "apply_ms": lambda: _native.call_on("lara_splatdensify_apply", dev, plan_c, degree, P, P_out, survivors, action, offset, w["noise"], ins,
+                                            outs, source, child),
         "densify_ms": lambda: D.densify(w["params"], w["exp_avg"], w["exp_avg_sq"], stats, row, noise=w["noise"]),
         "torch_ms": lambda: torch_round(w, row),
     }

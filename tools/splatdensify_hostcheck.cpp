@@ -68,11 +68,11 @@ int main(int argc, char **argv) {
         std::vector<int64_t> counts(5), want_counts;
         bool ok = take(f, plan, 8);
         const int n_split = ok ? lara_splatdensify_children(plan.data()) : 1;
-        for (int k = 0; ok && k < 15; ++k) ok = take(f, in[k], (size_t)(lara_splatdensify_width(k % 5, (int)degree) * P));
+        for (int k = 0; ok && k < 15; ++k) ok = take(f, in[k], (size_t)(lara_surfel_width(k % 5, (int)degree) * P));
         ok = ok && take(f, grad_sum, (size_t)P) && take(f, seen, (size_t)P) && take(f, max_radius, (size_t)P) && take(f, noise, (size_t)(P * n_split * 2));
         ok = ok && take(f, want_action, (size_t)P) && take(f, want_offset, (size_t)(3 * P)) && take(f, want_counts, 5) &&
              take(f, want_source, (size_t)P_out) && take(f, want_child, (size_t)P_out);
-        for (int k = 0; ok && k < 15; ++k) ok = take(f, want[k], (size_t)(lara_splatdensify_width(k % 5, (int)degree) * P_out));
+        for (int k = 0; ok && k < 15; ++k) ok = take(f, want[k], (size_t)(lara_surfel_width(k % 5, (int)degree) * P_out));
         if (!ok) { std::fprintf(stderr, "splatdensify_hostcheck: short case %lld\n", (long long)c); std::fclose(f); return 2; }
         action.assign((size_t)P, 0xEE);
         offset.assign((size_t)(3 * P), -1);
