@@ -314,14 +314,20 @@ def render_mesh_turntable(mesh, cams, chunk=8):
     return render_mesh_views(cams, mesh[0], mesh[1], mesh[2] if len(mesh) > 2 else None, chunk=chunk)["frames"]
 
 
-def save_surfels(path, render_pkg_item, min_opacity=None, thickness=None):
+def save_surfels(path, render_pkg_item, min_opacity=None, thickness=None, format="ply"):
     """One entry of ``output['render_pkg']`` (the coarse 5-tuple or the fine 6-tuple) as a 2DGS ``point_cloud.ply`` beside the
     mesh (`lara_amd.splatio`: the pre-activation values, bit for bit); ``min_opacity`` drops the surfels at or below it first,
-    ``thickness`` adds a third scale for 3DGS viewers.  Returns the number of surfels written."""
+    ``thickness`` adds a third scale for 3DGS viewers.  ``format`` "compressed" or "splat" writes the lossy packed files of
+    `lara_amd.splatpack` for web viewers instead (thickness 1e-3 when None; rows with non-finite words are dropped there and not
+    counted here).  Returns the number of surfels written."""
     from . import splatio
     cloud = splatio.SurfelCloud.from_render_pkg(render_pkg_item)
     cloud = cloud if min_opacity is None else splatio.select(cloud, min_opacity=min_opacity)[0]
-    splatio.write_ply(path, cloud, thickness)
+    if format == "ply":
+        splatio.write_ply(path, cloud, thickness)
+    else:
+        from . import splatpack
+        splatpack.write(path, cloud, format=format, thickness=thickness)
     return cloud.n_surfels
 
 

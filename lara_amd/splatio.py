@@ -20,7 +20,8 @@ binary little-endian, every property ``float``, in the order ``x y z  nx ny nz  
 stored order, which the reference's ``build_rotation`` reads as w, x, y, z; normals zero.
 
 No kernel of the library is launched: the module works on tensors on any device (torch operators only), the write is a host step.
-ASCII and big-endian files, the 32-byte ``.splat`` format and the web viewers' compressed PLY are out of scope.
+The 32-byte ``.splat`` format and the web viewers' compressed PLY (both lossy) are ``lara_amd.splatpack``'s; ASCII and big-endian
+files are out of scope.
 """
 from __future__ import annotations
 

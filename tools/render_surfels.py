@@ -1,4 +1,5 @@
-"""Renders a 2DGS ``point_cloud.ply`` -- one `lara_amd.splatio.write_ply` wrote, or one trained by the 2DGS code base -- on one
+"""Renders a 2DGS ``point_cloud.ply`` -- one `lara_amd.splatio.write_ply` wrote, or one trained by the 2DGS code base -- or a packed
+cloud of `lara_amd.splatpack` (a compressed PLY, a ``.splat`` file; the input is loaded through `splatpack.read`) on one
 MI355X without running any network: the orbit of `evaluate.video_cameras`, ``Renderer.render_views`` in chunks of 8
 (`evaluate.render_turntable`), RGB and normal frames as PNG (`meshtexture.write_png`), and a small JSON with the surfel count,
 the SH degree, the frame count and wall times (one run each: no spread is measured).  ``--mesh`` also extracts the TSDF mesh from
@@ -37,13 +38,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("tools/render_surfels.py needs an MI355X")
 
-    from lara_amd import evaluate, meshtexture, splatio
+    from lara_amd import evaluate, meshtexture, splatpack
     from lara_amd.renderer import Renderer
 
     dev = torch.device("cuda", 0)
     wall = {}
     t0 = time.perf_counter()
-    cloud, info = splatio.read_ply(args.ply, device=dev)
+    cloud, info = splatpack.read(args.ply, device=dev)           # (a plain point_cloud.ply goes to splatio.read_ply as before)
     torch.cuda.synchronize()
     wall["read_ply_s"] = time.perf_counter() - t0
     T = None
@@ -74,7 +75,7 @@ def main():
 
     res = {"ply": os.path.abspath(args.ply), "n_surfels": cloud.n_surfels, "sh_degree": cloud.sh_degree, "frames": len(cams),
            "size": args.size, "dataset": args.dataset, "chunk": CHUNK, "dropped_third_scale": info["dropped_third_scale"],
-           "skipped_properties": info["skipped_properties"], "mesh": None}
+           "skipped_properties": info.get("skipped_properties", []), "mesh": None}
     if args.mesh:
         from lara_amd.mesh import MeshExtractor
         t0 = time.perf_counter()
